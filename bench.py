@@ -11,6 +11,12 @@ STRONG scaling (fixed SF split across segments, the reference's MPP model).
 Single: python bench.py --gpus 1 --steps K --warmup W
 Multi:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
             --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run does only what the headline figure needs: setup, warmup, the K
+timed steps, the JSON line.  --full adds the side legs (CPU baseline,
+rocprofv3 FETCH_SIZE traffic side-run, pure scan+filter kernel GB/s); without
+it those fields of the JSON line are null.  --dump-outputs DIR writes the
+last timed step's result groups as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -90,20 +96,69 @@ def cpu_baseline_leg(sample_sf=8.0, full=False):
                       f"{cores} OpenMP threads)"}
 
 
+DUMP_SAMPLE_ROWS = 500_000   # 9 float64 arrays x 4 MB = 36 MB (cap: 64 MB)
+DUMP_SAMPLE_SEED = 20260915
+
+
+def dump_outputs(gx, q, outdir, suffix=""):
+    """--dump-outputs: what a caller of the timed path receives after its
+    last step — the Q3 result groups, sorted by l_orderkey (NULL-key group
+    last) — one float64 DIR/<field><suffix>.npy per result field.  This is
+    the call Q3.result() makes, read through a numpy view of the returned
+    struct array instead of a per-row Python loop (12.8 M groups at SF100).
+    Above DUMP_SAMPLE_ROWS groups a fixed seeded sample of rows is kept
+    (same rows on every run; their indices go to sample_index.npy)."""
+    import ctypes
+    import numpy as np
+    gp = ctypes.POINTER(gx._Group)()
+    ng = ctypes.c_int64()
+    q.ctx._chk(q.ctx._lib.gx_q3_result(q._q, ctypes.byref(gp), ctypes.byref(ng)))
+    ng = ng.value
+    try:
+        if ng > DUMP_SAMPLE_ROWS:
+            rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+            idx = np.sort(rng.choice(ng, DUMP_SAMPLE_ROWS, replace=False))
+        else:
+            idx = np.arange(ng, dtype=np.int64)
+        rows = (np.ctypeslib.as_array(gp, shape=(ng,))[idx] if ng
+                else np.zeros(0, np.dtype(gx._Group)))
+    finally:
+        q.ctx._lib.gx_free(gp)
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {f: rows[f].astype(np.float64)
+              for f in rows.dtype.names if f != "_pad"}
+    arrays["sample_index"] = idx.astype(np.float64)
+    arrays["ngroups"] = np.array([ng], np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, f"{name}{suffix}.npy"), a)
+    return ng, len(idx)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--sf", type=float, default=100.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side legs a plain run leaves out: the "
+                         "CPU baseline, the rocprofv3 --pmc FETCH_SIZE "
+                         "side-run (roofline.traffic) and the pure "
+                         "scan+filter kernel (scan_filter_kernel_gbps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's "
+                         "result groups as DIR/<field>.npy (float64; a fixed "
+                         "seeded row sample above "
+                         f"{DUMP_SAMPLE_ROWS} groups)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline leg")
     ap.add_argument("--full-cpu-baseline", action="store_true",
-                    help="time the oracle on the FULL workload SF (one pass, "
-                         "no extrapolation) instead of the bounded sample")
+                    help="with --full: time the oracle on the FULL workload "
+                         "SF (one pass, no extrapolation) instead of the "
+                         "bounded sample")
     ap.add_argument("--no-traffic", action="store_true",
-                    help="skip the rocprofv3 --pmc FETCH_SIZE side-run that "
-                         "fills roofline.traffic (used by the side-run "
-                         "itself to avoid recursion)")
+                    help="with --full: skip the rocprofv3 --pmc FETCH_SIZE "
+                         "side-run that fills roofline.traffic")
     ap.add_argument("--rle-keys", action="store_true",
                     help="store l_orderkey RLE-compressed (rle_type); the fused "
                          "probe kernel then scans runs, not rows (extra mode — "
@@ -113,6 +168,10 @@ def main():
                          "even at 1 rank (self send/recv) — the multi-GPU code "
                          "path, testable on one GPU (extra mode)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.full_cpu_baseline and not args.full:
+        ap.error("--full-cpu-baseline is a --full leg: pass --full as well")
     if args.force_motion:
         os.environ["GX_FORCE_MOTION"] = "1"
 
@@ -202,6 +261,11 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t[0])
 
+    if args.dump_outputs:
+        ng, kept = dump_outputs(gx, q, args.dump_outputs,
+                                suffix=f".rank{rank}" if n > 1 else "")
+        log(rank, f"dumped {kept} of {ng} result groups to {args.dump_outputs}")
+
     st = q.stats()
     ms_step = elapsed * 1000.0 / args.steps
     rows_per_sec = li_rows_total / (elapsed / args.steps)
@@ -216,8 +280,9 @@ def main():
     # traffic: DRAM-side read bytes of the dominant kernel from a separate
     # rocprofv3 --pmc FETCH_SIZE pass (counters only), with the documented
     # gfx950 x2 correction — tools/pmc_traffic.py.  Fail-soft: null.
+    # (--full only: the side-run is a second bench process)
     traffic = None
-    if rank == 0 and n == 1 and not args.no_traffic:
+    if args.full and rank == 0 and n == 1 and not args.no_traffic:
         try:
             from tools.pmc_traffic import probe_kernel_fetch_bytes
             log(rank, "PMC side-run (rocprofv3 --pmc FETCH_SIZE)...")
@@ -234,15 +299,15 @@ def main():
                 "traffic": traffic}
 
     # config-2 evidence: the pure scan+filter kernel's GB/s on the widest
-    # filter column (untimed extra; printed into config below)
+    # filter column (untimed extra, --full only; printed into config below)
     scan_gbps = None
-    if rank == 0 and n == 1:
+    if args.full and rank == 0 and n == 1:
         cnt, sf_ms = li.scan_filter(3, ">", gx.CUTOFF_19950315)
         if sf_ms > 0:
             scan_gbps = round(li_rows_local * 4.0 / 1e9 / (sf_ms / 1000.0), 1)
 
     cpu = None
-    if rank == 0 and n == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and n == 1 and not args.no_cpu_baseline:
         if args.full_cpu_baseline:
             log(rank, f"timing CPU baseline (oracle, FULL sf={args.sf:g})...")
             cpu = cpu_baseline_leg(args.sf, full=True)

@@ -13,7 +13,8 @@ def test_bench_help_parses():
                         "--help"], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0
     for flag in ("--gpus", "--steps", "--warmup", "--sf", "--rle-keys",
-                 "--force-motion", "--full-cpu-baseline", "--no-traffic"):
+                 "--force-motion", "--full-cpu-baseline", "--no-traffic",
+                 "--full", "--dump-outputs"):
         assert flag in r.stdout
 
 
