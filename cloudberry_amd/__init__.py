@@ -63,6 +63,24 @@ class _KvGroup(ctypes.Structure):
                 ("count", ctypes.c_int64)]
 
 
+# numpy mirror of gx_kv_group (the two-stage GROUP BY wire row, 32 B)
+KV_GROUP_DTYPE = np.dtype([("key", np.int64), ("key_is_null", np.uint8),
+                           ("_pad", np.uint8, (7,)), ("sum", np.float64),
+                           ("count", np.int64)])
+
+
+class _GbStats(ctypes.Structure):
+    _fields_ = [("ms_partial", ctypes.c_double),
+                ("ms_partition", ctypes.c_double),
+                ("ms_exchange", ctypes.c_double),
+                ("ms_combine", ctypes.c_double),
+                ("rows_in", ctypes.c_int64),
+                ("partial_groups", ctypes.c_int64),
+                ("sent_rows", ctypes.c_int64),
+                ("recv_rows", ctypes.c_int64),
+                ("final_groups", ctypes.c_int64)]
+
+
 class _Filter(ctypes.Structure):
     _fields_ = [("col", ctypes.c_int32), ("op", ctypes.c_int32),
                 ("literal", ctypes.c_int64)]
@@ -150,6 +168,20 @@ def _load():
                                ctypes.c_int,
                                ctypes.POINTER(ctypes.POINTER(_KvGroup)),
                                ctypes.POINTER(ctypes.c_int64)]
+    lib.gx_groupby_dist.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
+                                    ctypes.c_int, ctypes.c_int,
+                                    ctypes.POINTER(ctypes.POINTER(_KvGroup)),
+                                    ctypes.POINTER(ctypes.c_int64),
+                                    ctypes.POINTER(_GbStats)]
+    lib.gx_test_gb_partial.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_int64,
+                                       ctypes.POINTER(ctypes.c_int64)]
+    lib.gx_test_gb_combine.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_int64,
+                                       ctypes.POINTER(ctypes.POINTER(_KvGroup)),
+                                       ctypes.POINTER(ctypes.c_int64)]
     lib.gx_partition_multi.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_int32, ctypes.c_int64,
@@ -280,6 +312,53 @@ class Context:
                "count": np.array([gp[i].count for i in range(n)], np.int64)}
         self._lib.gx_free(gp)
         return res
+
+    def _kv_result(self, gp, n):
+        """gx_kv_group array -> the groupby dict shape; frees gp."""
+        raw = ctypes.string_at(gp, n * KV_GROUP_DTYPE.itemsize) if n else b""
+        self._lib.gx_free(gp)
+        g = np.frombuffer(raw, KV_GROUP_DTYPE)
+        return {"key": g["key"].copy(),
+                "key_is_null": g["key_is_null"].astype(np.bool_),
+                "sum": g["sum"].copy(), "count": g["count"].copy()}
+
+    def groupby_dist(self, table, key_col, val_col, stats=False):
+        """Two-stage GROUP BY across all segments of this context (partial
+        agg, hash Motion of the partial groups by key, combine agg): returns
+        the groups THIS segment owns, in the same dict shape as groupby();
+        with stats=True returns (groups, gx_gb_stats as a dict)."""
+        gp = ctypes.POINTER(_KvGroup)()
+        n = ctypes.c_int64()
+        st = _GbStats()
+        self._chk(self._lib.gx_groupby_dist(self._h, table._t, key_col, val_col,
+                                            ctypes.byref(gp), ctypes.byref(n),
+                                            ctypes.byref(st)))
+        res = self._kv_result(gp, n.value)
+        if stats:
+            return res, {f: getattr(st, f) for f, _ in st._fields_}
+        return res
+
+    def test_gb_partial(self, table, key_col, val_col, nsegs):
+        """Partial agg + partition kernels on one GPU: returns (counts,
+        rows) — rows is a KV_GROUP_DTYPE array grouped by destination."""
+        cap = table.nrows + 1              # distinct keys + the NULL group
+        counts = np.zeros(nsegs, np.int64)
+        rows = np.zeros(cap, KV_GROUP_DTYPE)
+        total = ctypes.c_int64()
+        self._chk(self._lib.gx_test_gb_partial(
+            self._h, table._t, key_col, val_col, nsegs, counts.ctypes.data,
+            rows.ctypes.data, cap, ctypes.byref(total)))
+        return counts, rows[:total.value]
+
+    def test_gb_combine(self, rows):
+        """Combine agg over partial rows (KV_GROUP_DTYPE array)."""
+        rows = np.ascontiguousarray(rows, KV_GROUP_DTYPE)
+        gp = ctypes.POINTER(_KvGroup)()
+        n = ctypes.c_int64()
+        self._chk(self._lib.gx_test_gb_combine(
+            self._h, rows.ctypes.data if len(rows) else None, len(rows),
+            ctypes.byref(gp), ctypes.byref(n)))
+        return self._kv_result(gp, n.value)
 
     def test_motion1(self, orders, nsegs, cutoff=CUTOFF_19950315):
         """Run the Motion-1 partition kernels; returns (counts, rows dict)."""

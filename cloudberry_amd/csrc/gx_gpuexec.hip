@@ -15,6 +15,9 @@
  *                 layout/internal hash parity-irrelevant)
  *   hash agg      executor/nodeAgg.c:836,2288,2743 + float.c:769 float8pl
  *                 (per-row transition → here: f64 atomic add per group slot)
+ *   two-stage agg cdb/cdbgroupingpaths.c:251 + executor/nodeAgg.c:2305,2321
+ *                 (partial agg → Redistribute Motion → combine agg → here:
+ *                 the partial table's groups routed and merged on device)
  *   Motion        executor/nodeMotion.c:1088,1181 + cdb/cdbhash.c:189-285,
  *                 530-541 (bit-exact routing), cdb/motion/* + contrib/
  *                 interconnect UDP (→ RCCL grouped send/recv, columnar batches)
@@ -2213,6 +2216,159 @@ __global__ void k_kv_extract(const unsigned long long *tkey,
     }
 }
 
+/* ----- two-stage GROUP BY (partial agg → Motion → combine agg) -----
+ * The plan cdbgroupingpaths.c:251 builds when the group key is not the
+ * distribution key: k_groupby's table is the PARTIAL agg state; its groups
+ * are hash-redistributed by the group key and merged on the owning segment
+ * with the aggregates' combine functions (nodeAgg.c:2305,2321). */
+
+/* partial-agg table → per-destination histogram by route(group key).
+ * Same two-pass hist/emit shape as k_ord_m1_hist/k_ord_m1_emit, scanning
+ * table slots instead of rows.  Claims are aggregated twice: one LDS atomic
+ * per wave per destination, then ONE global atomic per workgroup per
+ * destination.  (Per-wave GLOBAL claims were measured first: a 2^28-slot
+ * table is 4.2M wave iterations, and at one destination their same-address
+ * atomics serialized to 45.7 ms per kernel — G12.)  The NULL-key group
+ * (k_groupby's separate accumulators) is one extra row for null_dest — the
+ * segment cdbhash assigns a NULL attribute (rotation only, computed on the
+ * host with gx_cdbhash_multi) — when its count is > 0.
+ * Dynamic LDS: nsegs u64 (hist), 2·nsegs u64 (emit). */
+static constexpr int GB_MAX_SEGS = 2048;   /* emit LDS = 32 KiB at the cap */
+
+/* one workgroup's per-destination group counts into LDS cnt[nsegs] */
+__device__ __forceinline__ void d_gb_block_hist(const unsigned long long *tkey,
+                                                uint64_t tslots, int nsegs,
+                                                unsigned long long *cnt)
+{
+    int lane = threadIdx.x & 63;
+    for (int j = threadIdx.x; j < nsegs; j += blockDim.x) cnt[j] = 0ULL;
+    __syncthreads();
+    int64_t base0 = blockIdx.x * (int64_t) blockDim.x + threadIdx.x - lane;
+    int64_t stride = gridDim.x * (int64_t) blockDim.x;
+    for (int64_t base = base0; base < (int64_t) tslots; base += stride)
+    {
+        int64_t i = base + lane;
+        unsigned long long bk = i < (int64_t) tslots ? tkey[i] : 0ULL;
+        bool keep = bk != 0ULL;
+        if (__ballot(keep) == 0ULL) continue;            /* wave-uniform */
+        int32_t d = keep ? gx_route_i64((int64_t) (bk ^ (1ULL << 63)), nsegs)
+                         : 0;
+        for (int dd = 0; dd < nsegs; dd++)
+        {
+            unsigned long long m = __ballot(keep && d == dd);
+            if (m && lane == __ffsll((long long) m) - 1)
+                atomicAdd(&cnt[dd], (unsigned long long) __popcll(m));
+        }
+    }
+    __syncthreads();
+}
+
+__global__ void k_gb_part_hist(const unsigned long long *tkey, uint64_t tslots,
+                               const unsigned long long *null_cnt,
+                               int null_dest, int nsegs,
+                               unsigned long long *hist)
+{
+    extern __shared__ unsigned long long gb_lds[];
+    d_gb_block_hist(tkey, tslots, nsegs, gb_lds);
+    for (int j = threadIdx.x; j < nsegs; j += blockDim.x)
+        if (gb_lds[j]) atomicAdd(&hist[j], gb_lds[j]);
+    if (blockIdx.x == 0 && threadIdx.x == 0 && *null_cnt != 0ULL)
+        atomicAdd(&hist[null_dest], 1ULL);
+}
+
+/* partial-agg table → packed gx_kv_group wire rows (unbiased key), grouped
+ * contiguously by destination; cursors are pre-set to the region starts.
+ * Each workgroup counts its groups per destination, claims one contiguous
+ * piece of every destination's region, then its waves claim inside those
+ * pieces through LDS cursors. */
+__global__ void k_gb_part_emit(const unsigned long long *tkey,
+                               const double *tsum,
+                               const unsigned long long *tcnt, uint64_t tslots,
+                               const double *null_sum,
+                               const unsigned long long *null_cnt,
+                               int null_dest, int nsegs,
+                               unsigned long long *cursors, gx_kv_group *out)
+{
+    extern __shared__ unsigned long long gb_lds[];
+    unsigned long long *cnt = gb_lds, *cur = gb_lds + nsegs;
+    d_gb_block_hist(tkey, tslots, nsegs, cnt);
+    for (int j = threadIdx.x; j < nsegs; j += blockDim.x)
+        cur[j] = cnt[j] ? atomicAdd(&cursors[j], cnt[j]) : 0ULL;
+    __syncthreads();
+
+    int lane = threadIdx.x & 63;
+    int64_t base0 = blockIdx.x * (int64_t) blockDim.x + threadIdx.x - lane;
+    int64_t stride = gridDim.x * (int64_t) blockDim.x;
+    for (int64_t base = base0; base < (int64_t) tslots; base += stride)
+    {
+        int64_t i = base + lane;
+        unsigned long long bk = i < (int64_t) tslots ? tkey[i] : 0ULL;
+        bool keep = bk != 0ULL;
+        if (__ballot(keep) == 0ULL) continue;            /* wave-uniform */
+        int64_t key = (int64_t) (bk ^ (1ULL << 63));
+        int32_t d = keep ? gx_route_i64(key, nsegs) : 0;
+        for (int dd = 0; dd < nsegs; dd++)
+        {
+            unsigned long long w;
+            unsigned long long m = d_wave_claim(&cur[dd], keep && d == dd,
+                                                lane, &w);
+            if (m && keep && d == dd)
+            {
+                gx_kv_group g{};
+                g.key = key;
+                g.sum = tsum[i];
+                g.count = (int64_t) tcnt[i];
+                out[w] = g;
+            }
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0 && *null_cnt != 0ULL)
+    {
+        unsigned long long w = atomicAdd(&cursors[null_dest], 1ULL);
+        gx_kv_group g{};
+        g.key_is_null = 1;
+        g.sum = *null_sum;
+        g.count = (int64_t) *null_cnt;
+        out[w] = g;
+    }
+}
+
+/* combine agg: merge received partial states into a fresh table with the
+ * two-stage plan's combine functions — sum += partial.sum (float8pl),
+ * count += partial.count (int8pl).  Same biased-key/sentinel-0/atomicCAS
+ * walk as k_groupby, so duplicate keys merge whichever sender they came
+ * from; key_is_null rows merge into the single NULL group. */
+__global__ void k_gb_combine(const gx_kv_group *rows, int64_t n,
+                             unsigned long long *tkey, double *tsum,
+                             unsigned long long *tcnt, uint64_t tmask,
+                             double *null_sum, unsigned long long *null_cnt,
+                             int *err)
+{
+    int64_t i = blockIdx.x * (int64_t) blockDim.x + threadIdx.x;
+    int64_t stride = gridDim.x * (int64_t) blockDim.x;
+    for (; i < n; i += stride)
+    {
+        gx_kv_group g = rows[i];
+        if (g.key_is_null)
+        {
+            atomicAdd(null_sum, g.sum);
+            atomicAdd(null_cnt, (unsigned long long) g.count);
+            continue;
+        }
+        uint64_t bk = (uint64_t) g.key ^ (1ULL << 63);
+        if (bk == 0) { atomicOr(err, 4); continue; }
+        uint64_t slot = gx_hmix64(bk) & tmask;
+        while (true)
+        {
+            unsigned long long prev = atomicCAS(&tkey[slot], 0ULL, bk);
+            if (prev == 0ULL || prev == bk) break;
+            slot = (slot + 1) & tmask;
+        }
+        atomicAdd(&tsum[slot], g.sum);
+        atomicAdd(&tcnt[slot], (unsigned long long) g.count);
+    }
+}
+
 /* filtered orders → per-destination histogram by route(o_custkey) (Motion 1) */
 /* Motion-1 histogram/emit carry an optional DESTINATION-AWARE bloom
  * prefilter (bloom_all = all ranks' dim blooms, all-gathered): an order
@@ -3870,53 +4026,79 @@ static gx_status gb_flat(gx_ctx *ctx, const gx_col &c, devbuf &flat,
     return GX_OK;
 }
 
-extern "C" gx_status gx_groupby(gx_ctx *ctx, const gx_table *t, int key_col,
-                                int val_col, gx_kv_group **out,
-                                int64_t *ngroups)
+/* device hash-agg state: SoA open-addressing table (biased keys, sentinel
+ * 0) plus the separate NULL-group accumulators (nacc: [sum f64, count u64])
+ * and the error flag.  Shared by the one-stage agg, the partial agg and the
+ * combine agg of the two-stage plan. */
+struct gb_table {
+    devbuf kflat, kval, vflat, vval;   /* flattened Dense/RLE inputs */
+    devbuf tk, ts, tc, nacc, errb;
+    uint64_t tslots = 0;
+    int64_t cap = 0;                   /* most groups the table can hold */
+};
+
+/* budget-check, allocate and clear a table for up to n input rows */
+static gx_status gb_table_alloc(gx_ctx *ctx, gb_table &T, int64_t n,
+                                const char *what)
+{
+    hipStream_t s = ctx->stream;
+    uint64_t tslots = (uint64_t) pow2_at_least(n * 2);
+    T.tslots = tslots;
+    T.cap = std::min<int64_t>((int64_t) tslots, std::max<int64_t>(n, 1));
+    gx_status bs = hbm_budget_check(ctx, tslots * 24 + (uint64_t) T.cap * 24 + 64,
+                                    what);
+    if (bs != GX_OK) return bs;
+    HIP_CHK(ctx, T.tk.alloc(tslots * 8));
+    HIP_CHK(ctx, T.ts.alloc(tslots * 8));
+    HIP_CHK(ctx, T.tc.alloc(tslots * 8));
+    HIP_CHK(ctx, T.nacc.alloc(16));
+    HIP_CHK(ctx, T.errb.alloc(4));
+    HIP_CHK(ctx, hipMemsetAsync(T.tk.p, 0, tslots * 8, s));
+    HIP_CHK(ctx, hipMemsetAsync(T.ts.p, 0, tslots * 8, s));
+    HIP_CHK(ctx, hipMemsetAsync(T.tc.p, 0, tslots * 8, s));
+    HIP_CHK(ctx, hipMemsetAsync(T.nacc.p, 0, 16, s));
+    HIP_CHK(ctx, hipMemsetAsync(T.errb.p, 0, 4, s));
+    return GX_OK;
+}
+
+/* scan key_col/val_col of t into a fresh table (enqueue only, no sync) */
+static gx_status gb_build(gx_ctx *ctx, const gx_table *t, int key_col,
+                          int val_col, gb_table &T)
 {
     if (!ctx || !t || key_col < 0 || key_col >= (int) t->cols.size() ||
-        val_col < 0 || val_col >= (int) t->cols.size() || !out || !ngroups)
+        val_col < 0 || val_col >= (int) t->cols.size())
         return GX_ERR_INVALID;
     const gx_col &kc = t->cols[key_col], &vc = t->cols[val_col];
     if (kc.m.width != 8 || vc.m.width != 8) return GX_ERR_INVALID;
-    hipStream_t s = ctx->stream;
-    devbuf kflat, kval, vflat, vval;
     const uint8_t *k_s, *v_s, *k_val, *v_val;
     gx_colmeta k_m, v_m;
-    gx_status st = gb_flat(ctx, kc, kflat, kval, &k_s, &k_m, &k_val);
+    gx_status st = gb_flat(ctx, kc, T.kflat, T.kval, &k_s, &k_m, &k_val);
     if (st != GX_OK) return st;
-    st = gb_flat(ctx, vc, vflat, vval, &v_s, &v_m, &v_val);
+    st = gb_flat(ctx, vc, T.vflat, T.vval, &v_s, &v_m, &v_val);
     if (st != GX_OK) return st;
-
-    int64_t n = t->nrows;
-    uint64_t tslots = (uint64_t) pow2_at_least(n * 2);
-    {
-        uint64_t out_cap = (uint64_t) std::min<int64_t>((int64_t) tslots,
-                                                        std::max<int64_t>(n, 1));
-        gx_status bs = hbm_budget_check(ctx, tslots * 24 + out_cap * 24 + 64,
-                                        "groupby table");
-        if (bs != GX_OK) return bs;
-    }
-    devbuf tk, ts, tc, nacc, errb;
-    HIP_CHK(ctx, tk.alloc(tslots * 8));
-    HIP_CHK(ctx, ts.alloc(tslots * 8));
-    HIP_CHK(ctx, tc.alloc(tslots * 8));
-    HIP_CHK(ctx, nacc.alloc(16));
-    HIP_CHK(ctx, errb.alloc(4));
-    HIP_CHK(ctx, hipMemsetAsync(tk.p, 0, tslots * 8, s));
-    HIP_CHK(ctx, hipMemsetAsync(ts.p, 0, tslots * 8, s));
-    HIP_CHK(ctx, hipMemsetAsync(tc.p, 0, tslots * 8, s));
-    HIP_CHK(ctx, hipMemsetAsync(nacc.p, 0, 16, s));
-    HIP_CHK(ctx, hipMemsetAsync(errb.p, 0, 4, s));
-    hipLaunchKernelGGL(k_groupby, dim3(GRID), dim3(TPB), 0, s,
+    st = gb_table_alloc(ctx, T, t->nrows, "groupby table");
+    if (st != GX_OK) return st;
+    hipLaunchKernelGGL(k_groupby, dim3(GRID), dim3(TPB), 0, ctx->stream,
                        k_s, k_m, k_val, v_s, v_m, v_val, t->dvmap,
-                       tk.as<unsigned long long>(), ts.as<double>(),
-                       tc.as<unsigned long long>(), tslots - 1,
-                       nacc.as<double>(),
-                       nacc.as<unsigned long long>() + 1, errb.as<int>());
+                       T.tk.as<unsigned long long>(), T.ts.as<double>(),
+                       T.tc.as<unsigned long long>(), T.tslots - 1,
+                       T.nacc.as<double>(),
+                       T.nacc.as<unsigned long long>() + 1, T.errb.as<int>());
+    return GX_OK;
+}
+
+/* compact a table's groups on device, bring them to the host, sort by key
+ * asc and append the NULL group last; ev_done (optional) is recorded after
+ * the last kernel.  Caller frees *out with gx_free. */
+static gx_status gb_extract_sorted(gx_ctx *ctx, gb_table &T, hipEvent_t ev_done,
+                                   gx_kv_group **out, int64_t *ngroups)
+{
+    hipStream_t s = ctx->stream;
+    uint64_t tslots = T.tslots;
+    devbuf &tk = T.tk, &ts = T.ts, &tc = T.tc, &nacc = T.nacc, &errb = T.errb;
     /* device-side compaction: only the actual groups travel to the host
      * (the slot table itself can be tens of GB at SF-scale inputs) */
-    int64_t cap = std::min<int64_t>((int64_t) tslots, std::max<int64_t>(n, 1));
+    int64_t cap = T.cap;
     devbuf ok_b, os_b, oc_b, cur_b;
     HIP_CHK(ctx, ok_b.alloc((size_t) cap * 8));
     HIP_CHK(ctx, os_b.alloc((size_t) cap * 8));
@@ -3929,6 +4111,7 @@ extern "C" gx_status gx_groupby(gx_ctx *ctx, const gx_table *t, int key_col,
                        ok_b.as<unsigned long long>(), os_b.as<double>(),
                        oc_b.as<unsigned long long>(),
                        cur_b.as<unsigned long long>());
+    if (ev_done) HIP_CHK(ctx, hipEventRecord(ev_done, s));
     int herr = 0;
     double nsum = 0;
     unsigned long long ncnt = 0, ng = 0;
@@ -3979,6 +4162,266 @@ extern "C" gx_status gx_groupby(gx_ctx *ctx, const gx_table *t, int key_col,
     if (!*out) return GX_ERR_OOM;
     memcpy(*out, groups.data(), groups.size() * sizeof(gx_kv_group));
     return GX_OK;
+}
+
+extern "C" gx_status gx_groupby(gx_ctx *ctx, const gx_table *t, int key_col,
+                                int val_col, gx_kv_group **out,
+                                int64_t *ngroups)
+{
+    if (!out || !ngroups) return GX_ERR_INVALID;
+    gb_table T;
+    gx_status st = gb_build(ctx, t, key_col, val_col, T);
+    if (st != GX_OK) return st;
+    return gb_extract_sorted(ctx, T, nullptr, out, ngroups);
+}
+
+/* ---- two-stage GROUP BY: partial agg → hash Motion → combine agg ----
+ * (cdbgroupingpaths.c:251 plan shape; nodeAgg.c:2305,2321 combine step) */
+
+/* destination of the NULL-key group: cdbhash of one NULL int8 attribute is
+ * the rotation of the init value only (cdbhash.c:189-247) */
+static int gb_null_dest(int nsegs)
+{
+    int64_t v = 0;
+    uint8_t isnull = 1;
+    return gx_jump_consistent_hash(
+        (uint64_t) gx_cdbhash_multi(&v, &isnull, nullptr, 1), nsegs);
+}
+
+static void gb_part_hist(gx_ctx *ctx, gb_table &T, int nsegs,
+                         unsigned long long *dhist)
+{
+    hipLaunchKernelGGL(k_gb_part_hist, dim3(GRID), dim3(TPB),
+                       (size_t) nsegs * 8, ctx->stream,
+                       T.tk.as<unsigned long long>(), T.tslots,
+                       T.nacc.as<unsigned long long>() + 1,
+                       gb_null_dest(nsegs), nsegs, dhist);
+}
+
+static void gb_part_emit(gx_ctx *ctx, gb_table &T, int nsegs,
+                         unsigned long long *dcur, gx_kv_group *dsend)
+{
+    hipLaunchKernelGGL(k_gb_part_emit, dim3(GRID), dim3(TPB),
+                       (size_t) nsegs * 16, ctx->stream,
+                       T.tk.as<unsigned long long>(), T.ts.as<double>(),
+                       T.tc.as<unsigned long long>(), T.tslots,
+                       T.nacc.as<double>(),
+                       T.nacc.as<unsigned long long>() + 1,
+                       gb_null_dest(nsegs), nsegs, dcur, dsend);
+}
+
+/* combine stage over n device-resident partial rows */
+static gx_status gb_combine(gx_ctx *ctx, const gx_kv_group *drows, int64_t n,
+                            hipEvent_t ev_done, gx_kv_group **out,
+                            int64_t *ngroups)
+{
+    gb_table T;
+    gx_status st = gb_table_alloc(ctx, T, n, "groupby combine table");
+    if (st != GX_OK) return st;
+    hipLaunchKernelGGL(k_gb_combine, dim3(GRID), dim3(TPB), 0, ctx->stream,
+                       drows, n, T.tk.as<unsigned long long>(),
+                       T.ts.as<double>(), T.tc.as<unsigned long long>(),
+                       T.tslots - 1, T.nacc.as<double>(),
+                       T.nacc.as<unsigned long long>() + 1, T.errb.as<int>());
+    return gb_extract_sorted(ctx, T, ev_done, out, ngroups);
+}
+
+extern "C" gx_status gx_groupby_dist(gx_ctx *ctx, const gx_table *t,
+                                     int key_col, int val_col,
+                                     gx_kv_group **out, int64_t *ngroups,
+                                     gx_gb_stats *stats)
+{
+    if (!ctx || !t || !out || !ngroups) return GX_ERR_INVALID;
+    /* one-stage plan: the group key needs no redistribution on a single
+     * segment.  GX_FORCE_MOTION=1 routes a single-segment run through the
+     * full exchange branch, as in gx_q3_run. */
+    bool one_stage = ctx->nsegs == 1 && env_int("GX_FORCE_MOTION", 0) == 0;
+    if (!one_stage && !ctx->comm)
+    { set_err(ctx, "nsegs>1 but gx_comm_init not called%s", ""); return GX_ERR_STATE; }
+    gx_gb_stats S{};
+    S.rows_in = t->nrows;
+    hipStream_t s = ctx->stream;
+    evholder ev[7];
+    for (auto &e : ev) HIP_CHK(ctx, e.create());
+    auto ms_between = [](hipEvent_t a, hipEvent_t b) {
+        float ms = 0;
+        (void) hipEventElapsedTime(&ms, a, b);
+        return (double) ms;
+    };
+
+    if (one_stage)
+    {
+        gb_table T;
+        HIP_CHK(ctx, hipEventRecord(ev[0], s));
+        gx_status st = gb_build(ctx, t, key_col, val_col, T);
+        if (st != GX_OK) return st;
+        st = gb_extract_sorted(ctx, T, ev[1], out, ngroups);
+        if (st != GX_OK) return st;
+        S.ms_partial = ms_between(ev[0], ev[1]);
+        S.partial_groups = S.final_groups = *ngroups;
+        if (stats) *stats = S;
+        return GX_OK;
+    }
+
+    int n = ctx->nsegs;
+    if (n > GB_MAX_SEGS)
+    { set_err(ctx, "groupby_dist: more segments than the partition kernels' LDS histogram holds%s", ""); return GX_ERR_INVALID; }
+
+    /* stage 1: partial agg — the groups stay on the device */
+    gb_table T;
+    HIP_CHK(ctx, hipEventRecord(ev[0], s));
+    gx_status st = gb_build(ctx, t, key_col, val_col, T);
+    if (st != GX_OK) return st;
+    HIP_CHK(ctx, hipEventRecord(ev[1], s));
+
+    /* stage 2: partition.  The per-destination histogram goes straight
+     * into the all-gather, so ONE host sync yields both this rank's send
+     * layout (its own row) and every peer's counts. */
+    devbuf hist_b, cur_b, all_b;
+    HIP_CHK(ctx, hist_b.alloc(n * 8));
+    HIP_CHK(ctx, cur_b.alloc(n * 8));
+    HIP_CHK(ctx, all_b.alloc((size_t) n * n * 8));
+    unsigned long long *dhist = hist_b.as<unsigned long long>();
+    HIP_CHK(ctx, hipMemsetAsync(dhist, 0, n * 8, s));
+    gb_part_hist(ctx, T, n, dhist);
+    HIP_CHK(ctx, hipEventRecord(ev[2], s));
+    RCCL_CHK(ctx, ncclAllGather(dhist, all_b.p, n, ncclUint64, ctx->comm, s));
+    std::vector<unsigned long long> cnts_all((size_t) n * n);
+    int herr = 0;
+    HIP_CHK(ctx, hipMemcpyAsync(cnts_all.data(), all_b.p, (size_t) n * n * 8,
+                                hipMemcpyDeviceToHost, s));
+    HIP_CHK(ctx, hipMemcpyAsync(&herr, T.errb.p, 4, hipMemcpyDeviceToHost, s));
+    HIP_CHK(ctx, hipStreamSynchronize(s));
+    HIP_CHK(ctx, hipGetLastError());
+    std::vector<unsigned long long> h(n), off(n + 1, 0), rcv(n), roff(n + 1, 0);
+    for (int i = 0; i < n; i++) h[i] = cnts_all[(size_t) ctx->seg * n + i];
+    for (int i = 0; i < n; i++) off[i + 1] = off[i] + h[i];
+    for (int r = 0; r < n; r++) rcv[r] = cnts_all[(size_t) r * n + ctx->seg];
+    for (int r = 0; r < n; r++) roff[r + 1] = roff[r] + rcv[r];
+    unsigned long long send_n = off[n], recv_n = roff[n];
+    if ((int64_t) send_n > T.cap + 1)
+    { set_err(ctx, "groupby_dist: partition overflow%s", ""); return GX_ERR_INVALID; }
+    st = hbm_budget_check(ctx, (send_n + recv_n) * sizeof(gx_kv_group) + 64,
+                          "groupby exchange buffers");
+    if (st != GX_OK) return st;
+    devbuf send_b, recv_b;
+    HIP_CHK(ctx, send_b.alloc(send_n * sizeof(gx_kv_group)));
+    HIP_CHK(ctx, recv_b.alloc(recv_n * sizeof(gx_kv_group)));
+    gx_kv_group *send = send_b.as<gx_kv_group>(), *recv = recv_b.as<gx_kv_group>();
+    HIP_CHK(ctx, hipMemcpyAsync(cur_b.p, off.data(), n * 8, hipMemcpyHostToDevice, s));
+    HIP_CHK(ctx, hipEventRecord(ev[3], s));
+    gb_part_emit(ctx, T, n, cur_b.as<unsigned long long>(), send);
+    HIP_CHK(ctx, hipEventRecord(ev[4], s));
+
+    /* stage 3: exchange.  The self-share bypasses RCCL (device copy); peer
+     * transfers go through the <=512 MiB chunk helpers, one grouped call. */
+    if (h[ctx->seg])
+        HIP_CHK(ctx, hipMemcpyAsync(recv + roff[ctx->seg], send + off[ctx->seg],
+                                    h[ctx->seg] * sizeof(gx_kv_group),
+                                    hipMemcpyDeviceToDevice, s));
+    RCCL_CHK(ctx, ncclGroupStart());
+    for (int r = 0; r < n; r++)
+    {
+        if (r == ctx->seg) continue;
+        if (h[r])
+            RCCL_CHK(ctx, gx_nccl_send_chunked(send + off[r],
+                                               h[r] * sizeof(gx_kv_group),
+                                               r, ctx->comm, s));
+        if (rcv[r])
+            RCCL_CHK(ctx, gx_nccl_recv_chunked(recv + roff[r],
+                                               rcv[r] * sizeof(gx_kv_group),
+                                               r, ctx->comm, s));
+    }
+    RCCL_CHK(ctx, ncclGroupEnd());
+    HIP_CHK(ctx, hipEventRecord(ev[5], s));
+    /* a rejected key is reported only now, after this rank's sends and
+     * receives are enqueued, so the peers' matching calls still complete */
+    if (herr & 4)
+    {
+        HIP_CHK(ctx, hipStreamSynchronize(s));
+        set_err(ctx, "groupby: key INT64_MIN unsupported (biased sentinel)%s", "");
+        return GX_ERR_INVALID;
+    }
+
+    /* stage 4: combine agg over the received partial states */
+    st = gb_combine(ctx, recv, (int64_t) recv_n, ev[6], out, ngroups);
+    if (st != GX_OK) return st;
+
+    S.ms_partial = ms_between(ev[0], ev[1]);
+    S.ms_partition = ms_between(ev[1], ev[2]) + ms_between(ev[3], ev[4]);
+    S.ms_exchange = ms_between(ev[2], ev[3]) + ms_between(ev[4], ev[5]);
+    S.ms_combine = ms_between(ev[5], ev[6]);
+    S.partial_groups = S.sent_rows = (int64_t) send_n;
+    S.recv_rows = (int64_t) recv_n;
+    S.final_groups = *ngroups;
+    if (stats) *stats = S;
+    return GX_OK;
+}
+
+/* Test ABI: partial agg + partition kernels on one GPU for a given nsegs,
+ * returning the packed wire rows and per-destination counts to the host. */
+extern "C" gx_status gx_test_gb_partial(gx_ctx *ctx, const gx_table *t,
+                                        int key_col, int val_col, int nsegs,
+                                        int64_t *out_counts /* nsegs */,
+                                        gx_kv_group *out_rows /* cap */,
+                                        int64_t cap, int64_t *out_total)
+{
+    if (!ctx || !t || nsegs < 1 || nsegs > GB_MAX_SEGS || !out_counts ||
+        !out_total || cap < 0 ||
+        (cap > 0 && !out_rows))
+        return GX_ERR_INVALID;
+    hipStream_t s = ctx->stream;
+    gb_table T;
+    gx_status st = gb_build(ctx, t, key_col, val_col, T);
+    if (st != GX_OK) return st;
+    devbuf hist_b, cur_b, send_b;
+    HIP_CHK(ctx, hist_b.alloc(nsegs * 8));
+    HIP_CHK(ctx, cur_b.alloc(nsegs * 8));
+    HIP_CHK(ctx, hipMemsetAsync(hist_b.p, 0, nsegs * 8, s));
+    gb_part_hist(ctx, T, nsegs, hist_b.as<unsigned long long>());
+    std::vector<unsigned long long> h(nsegs), off(nsegs + 1, 0);
+    int herr = 0;
+    HIP_CHK(ctx, hipMemcpyAsync(h.data(), hist_b.p, nsegs * 8, hipMemcpyDeviceToHost, s));
+    HIP_CHK(ctx, hipMemcpyAsync(&herr, T.errb.p, 4, hipMemcpyDeviceToHost, s));
+    HIP_CHK(ctx, hipStreamSynchronize(s));
+    HIP_CHK(ctx, hipGetLastError());
+    if (herr & 4)
+    { set_err(ctx, "groupby: key INT64_MIN unsupported (biased sentinel)%s", ""); return GX_ERR_INVALID; }
+    for (int i = 0; i < nsegs; i++) off[i + 1] = off[i] + h[i];
+    int64_t total = (int64_t) off[nsegs];
+    if (total > cap)
+    { set_err(ctx, "gb_partial: output capacity too small%s", ""); return GX_ERR_INVALID; }
+    st = hbm_budget_check(ctx, (uint64_t) total * sizeof(gx_kv_group) + 64,
+                          "groupby exchange buffers");
+    if (st != GX_OK) return st;
+    HIP_CHK(ctx, send_b.alloc((size_t) total * sizeof(gx_kv_group)));
+    HIP_CHK(ctx, hipMemcpyAsync(cur_b.p, off.data(), nsegs * 8, hipMemcpyHostToDevice, s));
+    gb_part_emit(ctx, T, nsegs, cur_b.as<unsigned long long>(),
+                 send_b.as<gx_kv_group>());
+    if (total)
+        HIP_CHK(ctx, hipMemcpyAsync(out_rows, send_b.p,
+                                    (size_t) total * sizeof(gx_kv_group),
+                                    hipMemcpyDeviceToHost, s));
+    HIP_CHK(ctx, hipStreamSynchronize(s));
+    HIP_CHK(ctx, hipGetLastError());
+    for (int i = 0; i < nsegs; i++) out_counts[i] = (int64_t) h[i];
+    *out_total = total;
+    return GX_OK;
+}
+
+/* Test ABI: the combine stage over host-supplied partial rows */
+extern "C" gx_status gx_test_gb_combine(gx_ctx *ctx, const gx_kv_group *rows,
+                                        int64_t n, gx_kv_group **out,
+                                        int64_t *ngroups)
+{
+    if (!ctx || n < 0 || (n > 0 && !rows) || !out || !ngroups)
+        return GX_ERR_INVALID;
+    devbuf rows_b;
+    HIP_CHK(ctx, rows_b.alloc((size_t) n * sizeof(gx_kv_group)));
+    if (n)
+        HIP_CHK(ctx, hipMemcpyAsync(rows_b.p, rows, (size_t) n * sizeof(gx_kv_group),
+                                    hipMemcpyHostToDevice, ctx->stream));
+    return gb_combine(ctx, rows_b.as<gx_kv_group>(), n, nullptr, out, ngroups);
 }
 
 extern "C" gx_status gx_partition(gx_ctx *ctx, const int64_t *host_keys, int64_t n,
@@ -5559,7 +6002,7 @@ extern "C" void gx_free(void *p) { free(p); }
 /* ABI self-description: struct sizes for cross-checking foreign-language
  * mirrors (ctypes tests; the PG extension's abi-check compiles against the
  * real header instead).  kind: 0 stats, 1 group, 2 kv_group, 3 desc,
- * 4 coldesc, 5 filter. */
+ * 4 coldesc, 5 filter, 6 gb_stats. */
 extern "C" int64_t gx_abi_sizeof(int kind)
 {
     switch (kind)
@@ -5570,6 +6013,7 @@ extern "C" int64_t gx_abi_sizeof(int kind)
         case 3: return (int64_t) sizeof(gx_q3_desc);
         case 4: return (int64_t) sizeof(gx_coldesc);
         case 5: return (int64_t) sizeof(gx_filter);
+        case 6: return (int64_t) sizeof(gx_gb_stats);
         default: return -1;
     }
 }

@@ -298,7 +298,8 @@ gx_status gx_q3_free(gx_q3 *q);
 void gx_free(void *p);
 
 /* ABI self-description for foreign mirrors (0 stats, 1 q3_group,
- * 2 kv_group, 3 q3_desc, 4 coldesc, 5 filter); -1 for unknown kinds */
+ * 2 kv_group, 3 q3_desc, 4 coldesc, 5 filter, 6 gb_stats); -1 for unknown
+ * kinds */
 int64_t gx_abi_sizeof(int kind);
 
 /* ---- standalone hash GROUP BY (nodeAgg.c:2288 hash strategy over one key;
@@ -318,6 +319,28 @@ typedef struct gx_kv_group {
 gx_status gx_groupby(gx_ctx *ctx, const gx_table *t, int key_col, int val_col,
                      gx_kv_group **out, int64_t *ngroups);
 
+/* ---- two-stage GROUP BY through Motion: the plan the reference builds when
+ * the group key is not the distribution key (cdbgroupingpaths.c:251) —
+ * partial agg per segment, hash-redistribute Motion of the transition
+ * states by group key, combine agg on the owning segment (nodeAgg.c:2305,
+ * 2321: float8pl / int8pl as combine functions).  Routing is the bit-exact
+ * Motion chain; a NULL key routes as cdbhash routes a NULL attribute.
+ * Same grouping semantics, column formats and INT64_MIN restriction as the
+ * one-stage call above. ---- */
+typedef struct gx_gb_stats {
+    double  ms_partial, ms_partition, ms_exchange, ms_combine; /* HIP events */
+    int64_t rows_in, partial_groups, sent_rows, recv_rows, final_groups;
+} gx_gb_stats;
+
+/* GROUP BY key_col, COUNT(*), SUM(val_col) across all segments of ctx.
+ * Returns the groups THIS segment owns (route(key) == seg), key asc,
+ * NULL group last (on its owning segment only).  stats may be NULL.
+ * nsegs == 1 without GX_FORCE_MOTION runs the one-stage plan (motion stats
+ * zero); otherwise gx_comm_init must have been called (GX_ERR_STATE). */
+gx_status gx_groupby_dist(gx_ctx *ctx, const gx_table *t, int key_col,
+                          int val_col, gx_kv_group **out, int64_t *ngroups,
+                          gx_gb_stats *stats);
+
 /* ---- test-only entry points (parity harness; not part of the drop-in) ---- */
 typedef struct gx_ord_row { int64_t okey, ocust; int32_t odate, oprio; } gx_ord_row;
 /* Motion-1 partition kernels on one GPU: filter orders by cutoff, route by
@@ -334,6 +357,16 @@ gx_status gx_test_qual(gx_ctx *ctx, gx_table *customer, const gx_ord_row *rows,
 gx_status gx_test_q3_from_qual(gx_ctx *ctx, const gx_qual_row_abi *rows,
                                int64_t n, gx_table *lineitem, int32_t cutoff,
                                gx_q3_group **out, int64_t *ngroups);
+/* two-stage GROUP BY stages on one GPU.  Partial agg + partition for a given
+ * nsegs: packed partial groups, grouped contiguously by destination in
+ * destination order (order within a destination unspecified);
+ * GX_ERR_INVALID if the total exceeds cap. */
+gx_status gx_test_gb_partial(gx_ctx *ctx, const gx_table *t, int key_col, int val_col,
+                             int nsegs, int64_t *out_counts /* nsegs */,
+                             gx_kv_group *out_rows, int64_t cap, int64_t *out_total);
+/* combine agg over received partial rows: key asc, NULL group last */
+gx_status gx_test_gb_combine(gx_ctx *ctx, const gx_kv_group *rows, int64_t n,
+                             gx_kv_group **out, int64_t *ngroups);
 int gx_selftest_addressing(void);
 
 #ifdef __cplusplus
