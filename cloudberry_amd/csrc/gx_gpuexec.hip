@@ -1220,6 +1220,33 @@ __global__ void k_orders_count(const uint8_t *ok_s, gx_colmeta ok_m,
     }
 }
 
+/* Join/agg table payload, beside the SoA key array tkey[]: one 16-byte
+ * aggregation slot and one 8-byte attr pair per table slot.
+ *
+ * NEITHER ARRAY IS CLEARED PER RUN.  Only tkey[] is memset; the build thread
+ * whose CAS claims a slot stores the attr pair and one 16-byte zero to the
+ * agg slot.  Slots whose key is 0 therefore hold garbage (a previous run's
+ * sums, or whatever hipMalloc returned) BY DESIGN: every reader must gate on
+ * tkey[slot] != 0 before touching tagg[slot] / tattr[slot].
+ *
+ * f64 mode: {double sum; double cnt} — the count is an f64 everywhere
+ * (exact below 2^53; extract converts it to int64).  numeric mode: the same
+ * 16 bytes viewed as {u64 numerator; u64 cnt} (gx_aggslot_num). */
+struct alignas(16) gx_aggslot { double sum; double cnt; };
+struct alignas(16) gx_aggslot_num { unsigned long long sum; unsigned long long cnt; };
+struct alignas(8) gx_attrpair { int32_t attr1; int32_t attr2; };
+static_assert(sizeof(gx_aggslot) == 16 && sizeof(gx_aggslot_num) == 16 &&
+              sizeof(gx_attrpair) == 8, "table payload layout");
+
+/* claim-time init of a freshly CAS-won slot: one 8-B and one 16-B store
+ * (all-zero bits are 0.0 and 0ULL alike, so both modes share it) */
+__device__ __forceinline__ void d_slot_claim(gx_attrpair *tattr, gx_aggslot *tagg,
+                                             uint64_t slot, int32_t a1, int32_t a2)
+{
+    *reinterpret_cast<int2 *>(&tattr[slot]) = make_int2(a1, a2);
+    *reinterpret_cast<ulonglong2 *>(&tagg[slot]) = make_ulonglong2(0ULL, 0ULL);
+}
+
 /* orders local path: build the join/agg table keyed by o_orderkey.
  * (ExecHashTableInsert nodeHash.c:1886; o_orderkey unique → 1 entry/key;
  *  payload doubles as the agg group state, nodeAgg.c group = join row) */
@@ -1237,7 +1264,8 @@ __global__ void k_orders_build(const uint8_t *ok_s, gx_colmeta ok_m,
                                const KS *cset, uint64_t cmask,
                                const unsigned long long *bloom, uint64_t bwmask,
                                KT *tkey,
-                               int32_t *tdate, int32_t *tprio, gx_slotmap smap)
+                               gx_attrpair *tattr, gx_aggslot *tagg,
+                               gx_slotmap smap)
 {
     int64_t i, stride, iend;
     if constexpr (CHUNKED)
@@ -1271,8 +1299,8 @@ __global__ void k_orders_build(const uint8_t *ok_s, gx_colmeta ok_m,
             KT prev = atomicCAS(&tkey[slot], (KT) 0, (KT) k);
             if (prev == (KT) 0)
             {
-                tdate[slot] = od;
-                tprio[slot] = gx_col_get<int32_t>(op_s, op_m, i);
+                d_slot_claim(tattr, tagg, slot, od,
+                             gx_col_get<int32_t>(op_s, op_m, i));
                 break;
             }
             if (prev == (KT) k) break;   /* unique keys: no-op */
@@ -1298,7 +1326,7 @@ __global__ void k_li_probe_agg_t(const uint8_t *lk_s, gx_colmeta lk_m,
                                  const uint8_t *sh_s, gx_colmeta sh_m,
                                  const uint8_t *vmap, int fop, int32_t flit,
                                  const KT *tkey,
-                                 double *trev, unsigned long long *tcnt,
+                                 gx_aggslot *tagg,
                                  gx_slotmap smap,
                                  unsigned long long *hits,
                                  /* LEFT OUTER (HJ_FILL_OUTER): unmatched
@@ -1349,8 +1377,8 @@ __global__ void k_li_probe_agg_t(const uint8_t *lk_s, gx_colmeta lk_m,
     auto hit = [&](uint64_t slot, int64_t i) {
         double price = gx_col_get<double>(pr_s, pr_m, i);
         double disc = gx_col_get<double>(di_s, di_m, i);
-        atomicAdd(&trev[slot], price * (1.0 - disc));
-        atomicAdd(&tcnt[slot], 1ULL);
+        atomicAdd(&tagg[slot].sum, price * (1.0 - disc));
+        atomicAdd(&tagg[slot].cnt, 1.0);
         local_hits++;
     };
     if constexpr (B == 1)
@@ -1359,7 +1387,17 @@ __global__ void k_li_probe_agg_t(const uint8_t *lk_s, gx_colmeta lk_m,
         int64_t stride = gridDim.x * (int64_t) blockDim.x;
         /* visimap via a compile-time template split (VM): the default
          * instantiation carries no per-row check at all — a runtime guard
-         * here cost 57% (measured, profiles/bw_probe_r01.txt) */
+         * here cost 57% (measured, profiles/bw_probe_r01.txt).  The two
+         * adds stay two plain atomics: pairing them into one wave
+         * instruction through an LDS queue measured 6.17 ms against 4.41
+         * (profiles/aggslot_probe_ab.txt).
+         * On the packed 16-B slot this kernel is 0.05-0.10 ms SLOWER than
+         * on separate sum/count arrays (4.37-4.42 against 4.30-4.32 ms at
+         * SF100: 4 slots per 64-B line instead of 8, so a wave's adds
+         * cover more lines).  The layout is kept because the orders build
+         * gives the same amount back (one 16-B claim store instead of two
+         * 8-B ones: 2.28 against 2.35-2.37 ms) and the whole step is equal
+         * within spread — three-way A/B in profiles/aggslot_abc.json. */
         for (; i < lk_m.nrows; i += stride)
         {
             if constexpr (VM)
@@ -1640,8 +1678,8 @@ __global__ void k_li_probe_agg_t(const uint8_t *lk_s, gx_colmeta lk_m,
             if (r == ~0ULL) continue;
             double price = gx_col_get_nt<double>(pr_s, pr_m, i);
             double disc = gx_col_get_nt<double>(di_s, di_m, i);
-            atomicAdd(&trev[slot], price * (1.0 - disc));
-            atomicAdd(&tcnt[slot], 1ULL);
+            atomicAdd(&tagg[slot].sum, price * (1.0 - disc));
+            atomicAdd(&tagg[slot].cnt, 1.0);
             local_hits++;
         }
     }
@@ -1784,7 +1822,7 @@ __global__ void k_li_probe_agg_rle(const uint8_t *lk_s, const gx_blockref *dir,
                                    const uint8_t *sh_s, gx_colmeta sh_m,
                                    const uint8_t *vmap, int fop, int32_t flit,
                                    const KT *tkey,
-                                   double *trev, unsigned long long *tcnt,
+                                   gx_aggslot *tagg,
                                    gx_slotmap smap,
                                    unsigned long long *hits, int *err)
 {
@@ -1963,8 +2001,8 @@ __global__ void k_li_probe_agg_rle(const uint8_t *lk_s, const gx_blockref *dir,
                 if (!gx_cmp(fop, gx_col_get<int32_t>(sh_s, sh_m, g), flit)) continue;
                 double price = gx_col_get<double>(pr_s, pr_m, g);
                 double disc = gx_col_get<double>(di_s, di_m, g);
-                atomicAdd(&trev[slot], price * (1.0 - disc));
-                atomicAdd(&tcnt[slot], 1ULL);
+                atomicAdd(&tagg[slot].sum, price * (1.0 - disc));
+                atomicAdd(&tagg[slot].cnt, 1.0);
                 local_hits++;
             }
         }
@@ -1976,8 +2014,8 @@ __global__ void k_li_probe_agg_rle(const uint8_t *lk_s, const gx_blockref *dir,
 /* numeric(15,2) probe+agg: measures are scaled int64 (price
  * in cents, discount in hundredths); revenue numerator = Σ price_c·(100−d)
  * accumulated with integer atomics — BIT-EXACT, order-independent, equal to
- * the PG numeric SUM for these ranges.  The numerator lives in the trev
- * buffer (reinterpreted u64).  Overflow guard: numerators past 2^62 set the
+ * the PG numeric SUM for these ranges.  The numerator lives in the agg
+ * slot's sum word (gx_aggslot_num view).  Overflow guard: numerators past 2^62 set the
  * error flag (impossible for sane groups; detects corrupt input). */
 template <typename KT, bool VM = false, bool OUTER = false>
 __global__ void k_li_probe_agg_num(const uint8_t *lk_s, gx_colmeta lk_m,
@@ -1986,8 +2024,7 @@ __global__ void k_li_probe_agg_num(const uint8_t *lk_s, gx_colmeta lk_m,
                                    const uint8_t *sh_s, gx_colmeta sh_m,
                                    const uint8_t *vmap, int fop, int32_t flit,
                                    const KT *tkey,
-                                   unsigned long long *tnum,
-                                   unsigned long long *tcnt,
+                                   gx_aggslot_num *tagg,
                                    gx_slotmap smap,
                                    unsigned long long *hits, int *err,
                                    unsigned long long *ukey = nullptr,
@@ -2039,19 +2076,20 @@ __global__ void k_li_probe_agg_num(const uint8_t *lk_s, gx_colmeta lk_m,
         int64_t price_c = gx_col_get<int64_t>(pr_s, pr_m, i);
         int64_t disc_c = gx_col_get<int64_t>(di_s, di_m, i);
         unsigned long long add = (unsigned long long) (price_c * (100 - disc_c));
-        unsigned long long old = atomicAdd(&tnum[slot], add);
+        unsigned long long old = atomicAdd(&tagg[slot].sum, add);
         if (old + add > (1ULL << 62)) atomicOr(err, 4);
-        atomicAdd(&tcnt[slot], 1ULL);
+        atomicAdd(&tagg[slot].cnt, 1ULL);
         local_hits++;
     }
     gx_wave_count_add(hits, local_hits);
 }
 
 /* extract groups with ≥1 matched lineitem into SoA result arrays.
- * Two-pass per-workgroup compaction: each workgroup owns a contiguous slot
- * range, counts its keeps, claims an output region with ONE atomic, then
- * writes (cdna_hip_programming.md G12 — a single shared cursor serializes;
- * the first version lost 6 ms to ~500k same-address atomics). */
+ * Per-workgroup compaction (k_extract below): each workgroup owns a
+ * contiguous slot tile, counts its keeps, claims an output region with ONE
+ * atomic, then writes (cdna_hip_programming.md G12 — a single shared cursor
+ * serializes; the first version lost 6 ms to ~500k same-address atomics).
+ * d_wave_claim is the per-wave form used by the small side tables. */
 __device__ __forceinline__ unsigned long long
 d_wave_claim(unsigned long long *ctr, bool mine, int lane,
              unsigned long long *out_off)
@@ -2099,49 +2137,92 @@ __global__ void k_extract_u(const unsigned long long *ukey, const double *urev,
     }
 }
 
+/* Single-read, block-ordered extract.  A block owns one fixed tile of
+ * GX_EXTRACT_ROWS rows x 256 slots; thread t handles slot t of every row, so
+ * key loads are fully coalesced and each table byte is read once: the key
+ * always, the 16-B agg slot and 8-B attr pair only where the key is non-zero
+ * (unclaimed payload is garbage — see gx_aggslot).  Everything a thread will
+ * emit stays in registers.  Keeps (key != 0 and count != 0) are ranked with
+ * one ballot per (row, wave); the 32 ballot counts are scanned by wave 0,
+ * which claims the block's output region with ONE cursor atomic (G12), and a
+ * wave's stores for a row then land on consecutive output positions.
+ * Output order is slot order within a block.  blockDim.x must be TPB. */
+static constexpr int GX_EXTRACT_ROWS = 8;
+static constexpr int GX_EXTRACT_TILE = GX_EXTRACT_ROWS * TPB;
+
 template <typename KT>
-__global__ void k_extract(const KT *tkey, const int32_t *tdate,
-                          const int32_t *tprio, const double *trev,
-                          const unsigned long long *tcnt, uint64_t tslots,
-                          int64_t *okey, int32_t *odate, int32_t *oprio,
-                          double *rev, int64_t *cnt, unsigned long long *cursor)
+__global__ void __launch_bounds__(TPB)
+k_extract(const KT *tkey, const gx_attrpair *tattr, const gx_aggslot *tagg,
+          uint64_t tslots, int numeric,
+          int64_t *okey, int32_t *odate, int32_t *oprio,
+          double *rev, int64_t *cnt, unsigned long long *cursor)
 {
-    __shared__ unsigned int scan[256];
-    __shared__ unsigned long long sbase;
-    int64_t range = ((int64_t) tslots + gridDim.x - 1) / gridDim.x;
-    int64_t lo = blockIdx.x * range;
-    int64_t hi = min(lo + range, (int64_t) tslots);
-    if (lo >= hi) return;
+    constexpr int R = GX_EXTRACT_ROWS, NW = TPB / 64;
+    /* wave 0 scans the R*NW ballot counts with one lane each */
+    static_assert(TPB % 64 == 0 && R * NW <= 64, "k_extract tile geometry");
+    __shared__ unsigned long long s_off[R * NW];   /* [row][wave] */
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t base = (uint64_t) blockIdx.x * GX_EXTRACT_TILE + threadIdx.x;
 
-    /* pass 1: count my keeps (thread-strided over the block's range) */
-    unsigned int mine = 0;
-    for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x)
-        if (tkey[i] != (KT) 0 && tcnt[i] != 0ULL) mine++;
-    scan[threadIdx.x] = mine;
-    __syncthreads();
-    /* exclusive scan of 256 per-thread counts (Hillis-Steele in LDS) */
-    for (int o = 1; o < 256; o <<= 1)
+    KT key[R];
+    ulonglong2 agg[R];        /* raw bits: .x = sum, .y = count */
+    int2 attr[R];
+#pragma unroll
+    for (int r = 0; r < R; r++)
     {
-        unsigned int v = (threadIdx.x >= (unsigned) o) ? scan[threadIdx.x - o] : 0;
-        __syncthreads();
-        scan[threadIdx.x] += v;
-        __syncthreads();
+        uint64_t i = base + (uint64_t) r * TPB;
+        key[r] = (i < tslots) ? tkey[i] : (KT) 0;    /* tslots < tile: tail */
     }
-    if (threadIdx.x == blockDim.x - 1)
-        sbase = atomicAdd(cursor, (unsigned long long) scan[255]);
-    __syncthreads();
-    unsigned long long w = sbase + scan[threadIdx.x] - mine;
-
-    /* pass 2: write at my claimed positions */
-    for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x)
+#pragma unroll
+    for (int r = 0; r < R; r++)
     {
-        if (tkey[i] == (KT) 0 || tcnt[i] == 0ULL) continue;
-        okey[w] = (int64_t) tkey[i];
-        odate[w] = tdate[i];
-        oprio[w] = tprio[i];
-        rev[w] = trev[i];
-        cnt[w] = (int64_t) tcnt[i];
-        w++;
+        uint64_t i = base + (uint64_t) r * TPB;
+        agg[r] = make_ulonglong2(0ULL, 0ULL);
+        attr[r] = make_int2(0, 0);
+        if (key[r] != (KT) 0)
+        {
+            agg[r] = *reinterpret_cast<const ulonglong2 *>(&tagg[i]);
+            attr[r] = *reinterpret_cast<const int2 *>(&tattr[i]);
+        }
+    }
+    /* count bits != 0 is "count != 0" for the f64 and the u64 view alike */
+    unsigned long long m[R];
+#pragma unroll
+    for (int r = 0; r < R; r++)
+    {
+        m[r] = __ballot(key[r] != (KT) 0 && agg[r].y != 0ULL);
+        if (lane == 0) s_off[r * NW + wave] = (unsigned long long) __popcll(m[r]);
+    }
+    __syncthreads();
+    if (wave == 0)
+    {
+        /* exclusive scan of the R*NW (= 32) counts in (row, wave) order */
+        unsigned long long v = (lane < R * NW) ? s_off[lane] : 0ULL, incl = v;
+#pragma unroll
+        for (int o = 1; o < R * NW; o <<= 1)
+        {
+            unsigned long long u = __shfl_up(incl, o, 64);
+            if (lane >= o) incl += u;
+        }
+        unsigned long long total = __shfl(incl, R * NW - 1, 64);
+        unsigned long long b = 0;
+        if (lane == 0 && total) b = atomicAdd(cursor, total);
+        b = __shfl(b, 0, 64);
+        if (lane < R * NW) s_off[lane] = b + incl - v;
+    }
+    __syncthreads();
+    const unsigned long long below = (lane == 0) ? 0ULL : (~0ULL >> (64 - lane));
+#pragma unroll
+    for (int r = 0; r < R; r++)
+    {
+        if (!((m[r] >> lane) & 1ULL)) continue;
+        unsigned long long w = s_off[r * NW + wave] + __popcll(m[r] & below);
+        okey[w] = (int64_t) key[r];
+        odate[w] = attr[r].x;
+        oprio[w] = attr[r].y;
+        rev[w] = __longlong_as_double((long long) agg[r].x);   /* raw bits */
+        cnt[w] = numeric ? (int64_t) agg[r].y
+                         : (int64_t) __longlong_as_double((long long) agg[r].y);
     }
 }
 
@@ -2603,7 +2684,8 @@ template <typename KT>
 __global__ void k_build_from_rows(const gx_qual_row *rows, int64_t n,
                                   const unsigned long long *dn,
                                   KT *tkey,
-                                  int32_t *tdate, int32_t *tprio, gx_slotmap smap)
+                                  gx_attrpair *tattr, gx_aggslot *tagg,
+                                  gx_slotmap smap)
 {
     if (dn) n = min(n, (int64_t) *dn);
     int64_t i = blockIdx.x * (int64_t) blockDim.x + threadIdx.x;
@@ -2618,8 +2700,7 @@ __global__ void k_build_from_rows(const gx_qual_row *rows, int64_t n,
             KT prev = atomicCAS(&tkey[slot], (KT) 0, (KT) k);
             if (prev == (KT) 0)
             {
-                tdate[slot] = rows[i].odate;
-                tprio[slot] = rows[i].oprio;
+                d_slot_claim(tattr, tagg, slot, rows[i].odate, rows[i].oprio);
                 break;
             }
             if (prev == (KT) k) break;
@@ -2814,9 +2895,8 @@ struct gx_q3 {
     void *tkey = nullptr;            /* u32 or u64 slots, see key_width */
     int key_width = 8;
     gx_slotmap smap{};               /* slot mapping (interpolation or hash) */
-    int32_t *tdate = nullptr, *tprio = nullptr;
-    double *trev = nullptr;
-    unsigned long long *tcnt = nullptr;
+    gx_attrpair *tattr = nullptr;    /* claimed slots only — see gx_aggslot */
+    gx_aggslot *tagg = nullptr;      /* claimed slots only, never memset */
     uint64_t tmask = 0;
     unsigned long long *dcount = nullptr, *dhits = nullptr, *dmin = nullptr;
     /* motion-path exchange state (nsegs>1), cached across steps */
@@ -4858,7 +4938,7 @@ extern "C" gx_status gx_q3_prepare(gx_ctx *ctx, gx_table *customer, gx_table *or
 static void q3_free_runstate(gx_q3 *q)
 {
     auto fr = [](auto *&p) { if (p) { (void) hipFree(p); p = nullptr; } };
-    fr(q->cset); fr(q->bloom); fr(q->tkey); fr(q->tdate); fr(q->tprio); fr(q->trev); fr(q->tcnt);
+    fr(q->cset); fr(q->bloom); fr(q->tkey); fr(q->tattr); fr(q->tagg);
     fr(q->r_okey); fr(q->r_odate); fr(q->r_oprio); fr(q->r_rev); fr(q->r_cnt);
     fr(q->r_flags);
     fr(q->ukey); fr(q->ucnt_u); fr(q->urev);
@@ -5126,10 +5206,11 @@ static gx_status q3_size_and_alloc(gx_q3 *q)
         /* fill factor: slots = qual * tf/100, pow2-rounded.  r2 sweep
          * (profiles/rocprof_r2_kernels.txt): tf=300 (2^26 slots at SF100,
          * load factor 0.19) takes the probe 4.86 -> 4.43 ms and the whole
-         * step 8.21 -> 8.07 ms; tf>=600 gains the probe further but the
-         * two-pass extract's table scan eats it (a single-pass wave-claim
-         * extract re-measured the r1 cursor-serialization pathology and
-         * was reverted — clustered occupied slots make every wave claim). */
+         * step 8.21 -> 8.07 ms.  Re-swept with the single-read extract
+         * (profiles/aggslot_kernels.txt): tf>=600 still gains 0.38 ms of
+         * probe and the extract gives 0.38-0.45 ms of it back (twice the
+         * key array to stream), stage sum 7.66-7.70 against 7.59-7.60 at
+         * tf=300 — 300 stays. */
         int tf = env_int("GX_TABLE_FACTOR_PCT", 300);
         uint64_t tslots = (uint64_t) pow2_at_least(qual * tf / 100 + 1);
         {
@@ -5154,10 +5235,8 @@ static gx_status q3_size_and_alloc(gx_q3 *q)
                 q->smap.scale = (double) tslots / range;
         }
         HIP_CHK(ctx, hipMalloc(&q->tkey, tslots * q->key_width));
-        HIP_CHK(ctx, hipMalloc(&q->tdate, tslots * 4));
-        HIP_CHK(ctx, hipMalloc(&q->tprio, tslots * 4));
-        HIP_CHK(ctx, hipMalloc(&q->trev, tslots * 8));
-        HIP_CHK(ctx, hipMalloc(&q->tcnt, tslots * 8));
+        HIP_CHK(ctx, hipMalloc(&q->tattr, tslots * sizeof(gx_attrpair)));
+        HIP_CHK(ctx, hipMalloc(&q->tagg, tslots * sizeof(gx_aggslot)));
         q->rescap = std::max<int64_t>(qual + q->u_cap, 1);
         HIP_CHK(ctx, hipMalloc(&q->r_okey, q->rescap * 8));
         HIP_CHK(ctx, hipMalloc(&q->r_odate, q->rescap * 4));
@@ -5257,9 +5336,8 @@ extern "C" gx_status gx_q3_run(gx_q3 *q)
     if (ctx->nsegs == 1 && env_int("GX_FORCE_MOTION", 0) == 0)
     {
         uint64_t tslots = q->tmask + 1;
+        /* keys only: agg/attr slots are initialised at claim (gx_aggslot) */
         HIP_CHK(ctx, hipMemsetAsync(q->tkey, 0, tslots * q->key_width, s));
-        HIP_CHK(ctx, hipMemsetAsync(q->trev, 0, tslots * 8, s));
-        HIP_CHK(ctx, hipMemsetAsync(q->tcnt, 0, tslots * 8, s));
         if (D.fact_join == 1)
         {
             HIP_CHK(ctx, hipMemsetAsync(q->ukey, 0, (q->umask + 1) * 8, s));
@@ -5282,7 +5360,7 @@ extern "C" gx_status gx_q3_run(gx_q3 *q)
                                    op.dstream, op.m, ovm, D.mid_filter.op,
                                    (int32_t) D.mid_filter.literal, cs, q->cmask,
                                    q->bloom, q->bwmask,
-                                   tk, q->tdate, q->tprio, q->smap);
+                                   tk, q->tattr, q->tagg, q->smap);
             };
             auto go = [&](auto ch, auto vm) {
                 if (anti_join) go2(ch, vm, std::true_type{});
@@ -5336,13 +5414,13 @@ extern "C" gx_status gx_q3_run(gx_q3 *q)
                                    dim3(GRID), dim3(TPB), 0, s,
                                    q->m_send2, q->rescap, q->dcount,
                                    (unsigned int *) q->tkey,
-                                   q->tdate, q->tprio, q->smap);
+                                   q->tattr, q->tagg, q->smap);
             else
                 hipLaunchKernelGGL(k_build_from_rows<unsigned long long>,
                                    dim3(GRID), dim3(TPB), 0, s,
                                    q->m_send2, q->rescap, q->dcount,
                                    (unsigned long long *) q->tkey,
-                                   q->tdate, q->tprio, q->smap);
+                                   q->tattr, q->tagg, q->smap);
         }
         else if (q->key_width == 4 && q->cset_width == 4)
             launch_build((unsigned int *) q->tkey, (const unsigned int *) q->cset);
@@ -5571,7 +5649,7 @@ extern "C" gx_status gx_q3_run(gx_q3 *q)
             return GX_ERR_INVALID;
         }
         int want_kw = (kmax < (1ULL << 32)) ? 4 : 8;
-        /* same tuned fill factor as the local path (r2 sweep: tf=300) */
+        /* same tuned fill factor as the local path (tf=300) */
         int mtf = env_int("GX_TABLE_FACTOR_PCT", 300);
         uint64_t tslots = (uint64_t) pow2_at_least(qual * mtf / 100 + 1);
         /* motion path sizes from the exchanged counts each run; qual can
@@ -5580,15 +5658,13 @@ extern "C" gx_status gx_q3_run(gx_q3 *q)
             qual + q->u_cap > q->rescap)
         {
             auto fr = [](auto *&p) { if (p) { (void) hipFree(p); p = nullptr; } };
-            fr(q->tkey); fr(q->tdate); fr(q->tprio); fr(q->trev); fr(q->tcnt);
+            fr(q->tkey); fr(q->tattr); fr(q->tagg);
             fr(q->r_okey); fr(q->r_odate); fr(q->r_oprio); fr(q->r_rev); fr(q->r_cnt);
             fr(q->r_flags);
             q->key_width = want_kw;
             HIP_CHK(ctx, hipMalloc(&q->tkey, tslots * q->key_width));
-            HIP_CHK(ctx, hipMalloc(&q->tdate, tslots * 4));
-            HIP_CHK(ctx, hipMalloc(&q->tprio, tslots * 4));
-            HIP_CHK(ctx, hipMalloc(&q->trev, tslots * 8));
-            HIP_CHK(ctx, hipMalloc(&q->tcnt, tslots * 8));
+            HIP_CHK(ctx, hipMalloc(&q->tattr, tslots * sizeof(gx_attrpair)));
+            HIP_CHK(ctx, hipMalloc(&q->tagg, tslots * sizeof(gx_aggslot)));
             q->rescap = std::max<int64_t>(qual + q->u_cap, 1);
             HIP_CHK(ctx, hipMalloc(&q->r_okey, q->rescap * 8));
             HIP_CHK(ctx, hipMalloc(&q->r_odate, q->rescap * 4));
@@ -5598,9 +5674,8 @@ extern "C" gx_status gx_q3_run(gx_q3 *q)
             HIP_CHK(ctx, hipMalloc(&q->r_flags, q->rescap));
             q->tmask = tslots - 1;
         }
+        /* keys only: agg/attr slots are initialised at claim (gx_aggslot) */
         HIP_CHK(ctx, hipMemsetAsync(q->tkey, 0, (q->tmask + 1) * q->key_width, s));
-        HIP_CHK(ctx, hipMemsetAsync(q->trev, 0, (q->tmask + 1) * 8, s));
-        HIP_CHK(ctx, hipMemsetAsync(q->tcnt, 0, (q->tmask + 1) * 8, s));
         if (D.fact_join == 1)
         {
             HIP_CHK(ctx, hipMemsetAsync(q->ukey, 0, (q->umask + 1) * 8, s));
@@ -5620,12 +5695,12 @@ extern "C" gx_status gx_q3_run(gx_q3 *q)
             hipLaunchKernelGGL(k_build_from_rows<unsigned int>, dim3(GRID), dim3(TPB), 0, s,
                                recv2, qual, (const unsigned long long *) nullptr,
                                (unsigned int *) q->tkey,
-                               q->tdate, q->tprio, q->smap);
+                               q->tattr, q->tagg, q->smap);
         else
             hipLaunchKernelGGL(k_build_from_rows<unsigned long long>, dim3(GRID), dim3(TPB), 0, s,
                                recv2, qual, (const unsigned long long *) nullptr,
                                (unsigned long long *) q->tkey,
-                               q->tdate, q->tprio, q->smap);
+                               q->tattr, q->tagg, q->smap);
         HIP_CHK(ctx, hipEventRecord(mev1, s));
         HIP_CHK(ctx, hipStreamSynchronize(s));
         float mms = 0, p01 = 0, p23 = 0;
@@ -5656,7 +5731,7 @@ extern "C" gx_status gx_q3_run(gx_q3 *q)
                                lk.dstream, lk.ddir, nb, lp.dstream, lp.m,
                                ld.dstream, ld.m, ls.dstream, ls.m, lvm,
                                D.fact_filter.op, (int32_t) D.fact_filter.literal,
-                               keys, q->trev, q->tcnt, q->smap, dhits,
+                               keys, q->tagg, q->smap, dhits,
                                (int *) q->dmin);
         };
         if (q->key_width == 4)
@@ -5686,7 +5761,7 @@ extern "C" gx_status gx_q3_run(gx_q3 *q)
                                lk.dstream, lk.m, lp.dstream, lp.m, ld.dstream, ld.m,
                                ls.dstream, ls.m, lvm, D.fact_filter.op,
                                (int32_t) D.fact_filter.literal, keys,
-                               (unsigned long long *) q->trev, q->tcnt, q->smap,
+                               (gx_aggslot_num *) q->tagg, q->smap,
                                dhits, (int *) q->dmin,
                                q->ukey, (unsigned long long *) q->urev,
                                q->ucnt_u, q->umask);
@@ -5727,7 +5802,7 @@ extern "C" gx_status gx_q3_run(gx_q3 *q)
                                lk.dstream, lk.m, lp.dstream, lp.m, ld.dstream, ld.m,
                                ls.dstream, ls.m, lvm, D.fact_filter.op,
                                (int32_t) D.fact_filter.literal, keys,
-                               q->trev, q->tcnt, q->smap, dhits,
+                               q->tagg, q->smap, dhits,
                                q->ukey, q->urev, q->ucnt_u, q->umask);
         };
         if (q->key_width == 4)
@@ -5801,16 +5876,23 @@ extern "C" gx_status gx_q3_run(gx_q3 *q)
     HIP_CHK(ctx, hipMemsetAsync(dcount, 0, 8, s));
     if (q->r_flags)
         HIP_CHK(ctx, hipMemsetAsync(q->r_flags, 0, q->rescap, s));
-    int egrid = env_int("GX_EXTRACT_GRID", 32768);  /* measured optimum */
+    /* one block per fixed tile of the table; k_extract_u keeps its own grid */
+    const int egrid = 32768;
+    uint64_t etiles = (q->tmask + 1 + GX_EXTRACT_TILE - 1) / GX_EXTRACT_TILE;
+    if (etiles > 0x7FFFFFFFULL)
+    {
+        set_err(ctx, "join/agg table too large for the extract grid%s", "");
+        return GX_ERR_INVALID;
+    }
     if (q->key_width == 4)
-        hipLaunchKernelGGL(k_extract<unsigned int>, dim3(egrid), dim3(TPB), 0, s,
-                           (const unsigned int *) q->tkey, q->tdate, q->tprio,
-                           q->trev, q->tcnt, q->tmask + 1,
+        hipLaunchKernelGGL(k_extract<unsigned int>, dim3((unsigned) etiles), dim3(TPB), 0, s,
+                           (const unsigned int *) q->tkey, q->tattr, q->tagg,
+                           q->tmask + 1, q->numeric,
                            q->r_okey, q->r_odate, q->r_oprio, q->r_rev, q->r_cnt, dcount);
     else
-        hipLaunchKernelGGL(k_extract<unsigned long long>, dim3(egrid), dim3(TPB), 0, s,
-                           (const unsigned long long *) q->tkey, q->tdate, q->tprio,
-                           q->trev, q->tcnt, q->tmask + 1,
+        hipLaunchKernelGGL(k_extract<unsigned long long>, dim3((unsigned) etiles), dim3(TPB), 0, s,
+                           (const unsigned long long *) q->tkey, q->tattr, q->tagg,
+                           q->tmask + 1, q->numeric,
                            q->r_okey, q->r_odate, q->r_oprio, q->r_rev, q->r_cnt, dcount);
     if (q->desc.fact_join == 1)
         hipLaunchKernelGGL(k_extract_u, dim3(egrid), dim3(TPB), 0, s,
@@ -5899,7 +5981,7 @@ extern "C" gx_status gx_q3_result(gx_q3 *q, gx_q3_group **out, int64_t *ngroups)
         if (q->numeric)
         {
             int64_t num;
-            memcpy(&num, &rev[idx[i]], 8);   /* trev held integer numerators */
+            memcpy(&num, &rev[idx[i]], 8);   /* agg slot held integer numerators */
             g[i].revenue_num = num;
             g[i].revenue = (double) num / 1e4;
         }
@@ -6153,7 +6235,7 @@ extern "C" gx_status gx_test_q3_from_qual(gx_ctx *ctx,
 {
     if (!ctx || !lineitem || lineitem->cols.size() != 4) return GX_ERR_INVALID;
     hipStream_t s = ctx->stream;
-    devbuf rows_b, stat_b, key_b, date_b, prio_b, rev_b, cnt_b2, cur_b, hit_b;
+    devbuf rows_b, stat_b, key_b, attr_b, agg_b, cur_b, hit_b;
     HIP_CHK(ctx, rows_b.alloc(std::max<int64_t>(n, 1) * sizeof(gx_qual_row)));
     HIP_CHK(ctx, hipMemcpyAsync(rows_b.p, host_rows, n * sizeof(gx_qual_row),
                                 hipMemcpyHostToDevice, s));
@@ -6179,18 +6261,14 @@ extern "C" gx_status gx_test_q3_from_qual(gx_ctx *ctx,
             smap.scale = (double) tslots / range;
     }
     HIP_CHK(ctx, key_b.alloc(tslots * 8));
-    HIP_CHK(ctx, date_b.alloc(tslots * 4));
-    HIP_CHK(ctx, prio_b.alloc(tslots * 4));
-    HIP_CHK(ctx, rev_b.alloc(tslots * 8));
-    HIP_CHK(ctx, cnt_b2.alloc(tslots * 8));
+    HIP_CHK(ctx, attr_b.alloc(tslots * sizeof(gx_attrpair)));
+    HIP_CHK(ctx, agg_b.alloc(tslots * sizeof(gx_aggslot)));
     HIP_CHK(ctx, hipMemsetAsync(key_b.p, 0, tslots * 8, s));
-    HIP_CHK(ctx, hipMemsetAsync(rev_b.p, 0, tslots * 8, s));
-    HIP_CHK(ctx, hipMemsetAsync(cnt_b2.p, 0, tslots * 8, s));
     hipLaunchKernelGGL(k_build_from_rows<unsigned long long>, dim3(GRID), dim3(TPB), 0, s,
                        rows_b.as<gx_qual_row>(), n,
                        (const unsigned long long *) nullptr,
-                       key_b.as<unsigned long long>(), date_b.as<int32_t>(),
-                       prio_b.as<int32_t>(), smap);
+                       key_b.as<unsigned long long>(), attr_b.as<gx_attrpair>(),
+                       agg_b.as<gx_aggslot>(), smap);
     const gx_col &lk = lineitem->cols[0], &lp = lineitem->cols[1],
                  &ld = lineitem->cols[2], &ls = lineitem->cols[3];
     HIP_CHK(ctx, hit_b.alloc(8));
@@ -6199,7 +6277,7 @@ extern "C" gx_status gx_test_q3_from_qual(gx_ctx *ctx,
                        lk.dstream, lk.m, lp.dstream, lp.m, ld.dstream, ld.m,
                        ls.dstream, ls.m, (const uint8_t *) nullptr, 1, cutoff,
                        key_b.as<unsigned long long>(),
-                       rev_b.as<double>(), cnt_b2.as<unsigned long long>(),
+                       agg_b.as<gx_aggslot>(),
                        smap, hit_b.as<unsigned long long>());
     devbuf r_okey, r_odate, r_oprio, r_rev, r_cnt;
     int64_t cap = std::max<int64_t>(n, 1);
@@ -6210,10 +6288,11 @@ extern "C" gx_status gx_test_q3_from_qual(gx_ctx *ctx,
     HIP_CHK(ctx, r_cnt.alloc(cap * 8));
     HIP_CHK(ctx, cur_b.alloc(8));
     HIP_CHK(ctx, hipMemsetAsync(cur_b.p, 0, 8, s));
-    hipLaunchKernelGGL(k_extract<unsigned long long>, dim3(32768), dim3(TPB), 0, s,
-                       key_b.as<unsigned long long>(), date_b.as<int32_t>(),
-                       prio_b.as<int32_t>(), rev_b.as<double>(),
-                       cnt_b2.as<unsigned long long>(), tslots,
+    hipLaunchKernelGGL(k_extract<unsigned long long>,
+                       dim3((unsigned) ((tslots + GX_EXTRACT_TILE - 1) / GX_EXTRACT_TILE)),
+                       dim3(TPB), 0, s,
+                       key_b.as<unsigned long long>(), attr_b.as<gx_attrpair>(),
+                       agg_b.as<gx_aggslot>(), tslots, 0,
                        r_okey.as<int64_t>(), r_odate.as<int32_t>(),
                        r_oprio.as<int32_t>(), r_rev.as<double>(),
                        r_cnt.as<int64_t>(), cur_b.as<unsigned long long>());

@@ -29,7 +29,12 @@ def main():
         for _ in range(REPS):
             q.run()
             st = q.stats()
-            if best is None or st["ms_probe_agg"] < best["ms_probe_agg"]:
+            st["ms_stage_sum"] = (st["ms_cust_build"] + st["ms_orders_build"] +
+                                  st["ms_probe_agg"] + st["ms_extract"])
+            # "best" is the run with the smallest stage sum: the table size
+            # moves the orders build, the probe and the extract in opposite
+            # directions, so no single stage may pick the winner
+            if best is None or st["ms_stage_sum"] < best["ms_stage_sum"]:
                 best = st
         if base is None:
             base = best
@@ -37,9 +42,15 @@ def main():
               best["groups"] == base["groups"])
         print(f"tf={tf}: probe {best['ms_probe_agg']:.3f} ms "
               f"orders {best['ms_orders_build']:.3f} ms "
+              f"extract {best['ms_extract']:.3f} ms "
+              f"sum {best['ms_stage_sum']:.3f} ms "
               f"{'OK' if ok else 'PARITY MISMATCH!'}", flush=True)
-        results[tf] = (best["ms_probe_agg"], best["ms_orders_build"])
+        results[tf] = {k: round(best[k], 3) for k in
+                       ("ms_probe_agg", "ms_orders_build", "ms_extract",
+                        "ms_stage_sum")}
         q.free()
+    win = min(results, key=lambda t: results[t]["ms_stage_sum"])
+    print(f"best by stage sum: tf={win}")
     print(json.dumps(results))
 
 
