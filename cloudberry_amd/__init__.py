@@ -252,8 +252,10 @@ class Context:
         return Table(self, t)
 
     def bind(self, streams):
-        """streams: list of (bytes, width, nrows[, format]) AOCS column
-        streams; format 0 = Orig fixed, 1 = Dense/RLE."""
+        """streams: list of (bytes, width, nrows[, format[, codec[,
+        blocksize]]]) AOCS column streams; format 0 = Orig fixed, 1 =
+        Dense/RLE; blocksize = the AO blocksize the stream was written
+        with (default 32768)."""
         descs = (_ColDesc * len(streams))()
         keep = []
         for i, spec in enumerate(streams):
@@ -264,7 +266,7 @@ class Context:
             descs[i].nbytes = len(arr)
             descs[i].width = width
             descs[i].nrows = nrows
-            descs[i].blocksize = 32768
+            descs[i].blocksize = spec[5] if len(spec) > 5 else 32768
             descs[i].format = spec[3] if len(spec) > 3 else 0
             descs[i].codec = spec[4] if len(spec) > 4 else 0
         t = ctypes.c_void_p()
@@ -427,6 +429,9 @@ class Context:
         """Plan-descriptor Q3 slice: column roles + filter
         {col, op, literal} triples chosen by the caller."""
         ops = {"<": 0, ">": 1, "==": 2, "!=": 3, "<=": 4, ">=": 5}
+
+        def opcode(op):         # symbol, or a raw gx_filter op code
+            return op if isinstance(op, int) else ops[op]
         d = _Q3Desc()
         for role in ("dim", "mid", "fact"):
             setattr(d, role, desc_dict[role]._t)
@@ -446,9 +451,9 @@ class Context:
                 blit = lit.encode() if isinstance(lit, str) else lit
                 d.dim_text = blit
                 d.dim_text_len = len(blit)
-                setattr(d, role, _Filter(col, ops[op], 0))
+                setattr(d, role, _Filter(col, opcode(op), 0))
             else:
-                setattr(d, role, _Filter(col, ops[op], int(lit)))
+                setattr(d, role, _Filter(col, opcode(op), int(lit)))
         # AND-ed extra qual lists (execScan.c:241 semantics)
         for role, arr, cnt in (("dim_extra", d.dim_extra, "n_dim_extra"),
                                ("mid_extra", d.mid_extra, "n_mid_extra"),
@@ -456,7 +461,7 @@ class Context:
             quals = desc_dict.get(role, [])
             assert len(quals) <= 4
             for i, (col, op, lit) in enumerate(quals):
-                arr[i] = _Filter(col, ops[op], int(lit))
+                arr[i] = _Filter(col, opcode(op), int(lit))
             setattr(d, cnt, len(quals))
         d.dim_join = {"semi": 0, "anti": 1, "anti_notin": 2}[
             desc_dict.get("dim_join", "semi")]
@@ -500,8 +505,10 @@ class Table:
         return b.value
 
     def scan_filter(self, col, op, literal):
-        """SeqScan+qual count; op in {'<','>','==','!='}; returns (count, ms)."""
-        opc = {"<": 0, ">": 1, "==": 2, "!=": 3}[op]
+        """SeqScan+qual count; op in {'<','>','==','!=','<=','>='} or a raw
+        gx_filter op code; returns (count, ms)."""
+        opc = op if isinstance(op, int) else \
+            {"<": 0, ">": 1, "==": 2, "!=": 3, "<=": 4, ">=": 5}[op]
         n = ctypes.c_int64()
         ms = ctypes.c_double()
         self.ctx._chk(self.ctx._lib.gx_scan_filter(self.ctx._h, self._t, col, opc,

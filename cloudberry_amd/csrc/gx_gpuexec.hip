@@ -800,7 +800,7 @@ __device__ __forceinline__ void gx_wave_count_add(unsigned long long *dst,
 
 /* Standalone columnar scan + filter (BASELINE config 2; the SeqScan+qual
  * slice without a join): count rows of one column passing <op, literal>.
- * op: 0 '<', 1 '>', 2 '=', 3 '!='; three-valued logic degenerates to
+ * op: the six gx_filter ops (gx_cmp); three-valued logic degenerates to
  * two-valued on NOT NULL columns (execScan.c:241). */
 template <typename T>
 __global__ void k_scan_filter(const uint8_t *col_s, gx_colmeta m,
@@ -814,9 +814,7 @@ __global__ void k_scan_filter(const uint8_t *col_s, gx_colmeta m,
     {
         if (gx_vm_hidden(vmap, i)) continue;
         T v = gx_col_get<T>(col_s, m, i);
-        bool pass = (op == 0) ? (v < lit) : (op == 1) ? (v > lit)
-                  : (op == 2) ? (v == lit) : (v != lit);
-        if (pass) local++;
+        if (gx_cmp<T>(op, v, lit)) local++;
     }
     gx_wave_count_add(count, local);
 }
@@ -3297,10 +3295,54 @@ static gx_status parse_block_dir(const uint8_t *s, int64_t nbytes,
     return GX_OK;
 }
 
+/* A format-0 column is addressed in O(1) (gx_col_get): block b starts at
+ * b*full_block_len and every block but the last holds exactly rpb rows.
+ * Nothing on the device re-checks that, so walk the envelope headers on the
+ * HOST at bind and refuse any stream the arithmetic would mis-address: a
+ * truncated stream, a wrong width or blocksize, a partial block in the
+ * middle (two segment files concatenated — bind those as format 1). */
+static const char *check_orig_geometry(const uint8_t *s, int64_t nbytes,
+                                       const gx_colmeta &m)
+{
+    if (m.width != 1 && m.width != 4 && m.width != 8)
+        return "format-0 width must be 1, 4 or 8";
+    if (m.nrows < 0 || m.rpb <= 0) return "bad nrows/blocksize";
+    int64_t off = 0, row = 0;
+    while (off < nbytes)
+    {
+        if (off + 24 > nbytes) return "truncated block header";
+        uint32_t b03, b47;
+        memcpy(&b03, s + off, 4);
+        memcpy(&b47, s + off + 4, 4);
+        if (((b03 >> 28) & 7) != 1 || (b47 & 0x1FFFFFu) != 0)
+            return "not a small-content block";
+        int64_t rows = (b03 & 0x00FFFC00u) >> 10;
+        int64_t datalen = ((b03 & 0x3FFu) << 11) | ((b47 & 0xFFE00000u) >> 21);
+        int64_t blocklen = (24 + datalen + 7) & ~7LL;
+        if (off + blocklen > nbytes) return "truncated block";
+        int64_t want = std::min<int64_t>(m.rpb, m.nrows - row);
+        if (want <= 0) return "more rows than nrows";
+        if (rows != want)
+            return "a block before the last is not full (wrong width or "
+                   "blocksize, or concatenated streams: bind as format 1)";
+        if (datalen != 16 + rows * m.width) return "block length does not match width";
+        row += rows;
+        off += blocklen;
+    }
+    if (row != m.nrows) return "fewer rows than nrows";
+    return nullptr;
+}
+
 extern "C" gx_status gx_table_bind(gx_ctx *ctx, const gx_coldesc *cols, int ncols,
                                    gx_table **out)
 {
     if (!ctx || !cols || ncols <= 0) return GX_ERR_INVALID;
+    for (int c = 1; c < ncols; c++)
+        if (cols[c].nrows != cols[0].nrows)
+        {
+            set_err(ctx, "bind: every column of a table needs the same nrows%s", "");
+            return GX_ERR_INVALID;
+        }
     gx_table *t = new gx_table();
     t->ctx = ctx;
     t->nrows = cols[0].nrows;
@@ -3329,7 +3371,24 @@ extern "C" gx_status gx_table_bind(gx_ctx *ctx, const gx_coldesc *cols, int ncol
         col.m.nrows = cols[c].nrows;
         col.m.full_block_len = gx_aocs_block_len(cols[c].width, col.m.rpb);
         col.m.nbytes = stream_len;
+        if (col.m.rpb <= 0)
+        {
+            set_err(ctx, "bind: blocksize too small for one row%s", "");
+            gx_table_free(t);
+            return GX_ERR_INVALID;
+        }
         gx_colmeta_finish(&col.m);
+        if (col.format == 0)
+        {
+            const char *why = check_orig_geometry((const uint8_t *) stream_src,
+                                                  stream_len, col.m);
+            if (why)
+            {
+                set_err(ctx, "bad Orig stream: %s", why);
+                gx_table_free(t);
+                return GX_ERR_INVALID;
+            }
+        }
         if (col.format == 1)
         {
             std::vector<gx_blockref> dir;
@@ -3967,6 +4026,35 @@ extern "C" gx_status gx_decode_column_varlena(gx_ctx *ctx, const gx_table *t,
     return GX_OK;
 }
 
+/* Primary filters compare in the COLUMN type (the kernels take a T literal),
+ * but the plan's literal is an int64 and the reference evaluates the
+ * cross-type operator (int48lt etc.) with the mathematically correct result.
+ * Before the literal is narrowed, fold <op, literal> over a width-byte signed
+ * column into an equivalent pair whose literal fits the type: an
+ * out-of-range literal makes the qual constant, always-true becomes
+ * v >= TYPE_MIN and always-false v < TYPE_MIN.  Returns false for an op
+ * outside 0..5 (gx_cmp would silently read it as '>='). */
+static bool gx_fold_filter(int width, int32_t *op, int64_t *literal)
+{
+    if (*op < 0 || *op > 5) return false;
+    if (width != 1 && width != 4) return true;     /* i64: nothing to narrow */
+    const int64_t lo = (width == 1) ? INT8_MIN : INT32_MIN;
+    const int64_t hi = (width == 1) ? INT8_MAX : INT32_MAX;
+    if (*literal >= lo && *literal <= hi) return true;
+    const bool above = *literal > hi;               /* every v < literal */
+    bool pass;
+    switch (*op)
+    {
+        case 0: case 4: pass = above; break;        /* v <  lit, v <= lit */
+        case 1: case 5: pass = !above; break;       /* v >  lit, v >= lit */
+        case 2: pass = false; break;                /* v == lit */
+        default: pass = true; break;                /* v != lit */
+    }
+    *op = pass ? 5 : 0;
+    *literal = lo;
+    return true;
+}
+
 /* TPC-H Q1 core aggregation over a GX_TPCH_LINEITEM_Q1 table: 6 fixed
  * groups (returnflag×linestatus); out arrays of 6: counts, sum_price,
  * sum_revenue.  AVG = sum/count on the caller side (float8_avg = Sx/N). */
@@ -3975,6 +4063,14 @@ extern "C" gx_status gx_q1(gx_ctx *ctx, const gx_table *t, int32_t cutoff,
                            double *sum_rev6, double *ms_out)
 {
     if (!ctx || !t || t->cols.size() != 5) return GX_ERR_INVALID;
+    static const int32_t q1_width[5] = {1, 1, 8, 8, 4};
+    for (int c = 0; c < 5; c++)
+        if (t->cols[c].format != 0 || t->cols[c].m.width != q1_width[c])
+        {
+            set_err(ctx, "gx_q1 needs Orig columns [flag i8, status i8, "
+                         "price f64, discount f64, shipdate i32]%s", "");
+            return GX_ERR_INVALID;
+        }
     hipStream_t s = ctx->stream;
     devbuf cnt, spr, srv;
     HIP_CHK(ctx, cnt.alloc(6 * 8));
@@ -4011,10 +4107,17 @@ extern "C" gx_status gx_scan_filter(gx_ctx *ctx, const gx_table *t, int col,
                                     int op, int64_t literal,
                                     int64_t *count_out, double *ms_out)
 {
-    if (!ctx || !t || col < 0 || col >= (int) t->cols.size() || op < 0 || op > 3)
+    if (!ctx || !t || col < 0 || col >= (int) t->cols.size())
         return GX_ERR_INVALID;
     const gx_col &c = t->cols[col];
     if (c.format != 0) { set_err(ctx, "scan_filter requires fixed-format column%s", ""); return GX_ERR_INVALID; }
+    int32_t fop = op;
+    if (!gx_fold_filter(c.m.width, &fop, &literal))
+    {
+        set_err(ctx, "scan_filter: op must be in 0..5%s", "");
+        return GX_ERR_INVALID;
+    }
+    op = fop;
     hipStream_t s = ctx->stream;
     devbuf cnt;
     HIP_CHK(ctx, cnt.alloc(8));
@@ -4822,6 +4925,17 @@ extern "C" gx_status gx_q3_prepare_desc(gx_ctx *ctx, const gx_q3_desc *desc,
     q->ord = orders;
     q->li = lineitem;
     q->desc = *desc;
+    /* every primary-filter launch reads q->desc: fold the literals into the
+     * column types here, once (the TEXT dim filter carries no literal) */
+    if ((!dim_text && !gx_fold_filter(1, &q->desc.dim_filter.op,
+                                      &q->desc.dim_filter.literal)) ||
+        !gx_fold_filter(4, &q->desc.mid_filter.op, &q->desc.mid_filter.literal) ||
+        !gx_fold_filter(4, &q->desc.fact_filter.op, &q->desc.fact_filter.literal))
+    {
+        set_err(ctx, "gx_q3_desc: primary filter op must be in 0..5%s", "");
+        delete q;
+        return GX_ERR_INVALID;
+    }
     if (dim_text)
     {
         hipError_t e = hipMalloc(&q->dtext,

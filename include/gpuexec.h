@@ -92,6 +92,13 @@ typedef struct gx_coldesc {
                                   compresstype analog) */
 } gx_coldesc;
 
+/* Every column must carry the same nrows.  A format-0 stream is addressed in
+ * O(1) afterwards, so bind walks its block headers on the host and returns
+ * GX_ERR_INVALID unless they are small-content blocks of exactly
+ * rows_per_block(width, blocksize) rows each (the last may be shorter), the
+ * rows add up to nrows and the blocks to nbytes, and nrows == 0 exactly for
+ * an empty stream.  Streams concatenated from several segment files have a
+ * partial block in the middle: bind those as format 1. */
 gx_status gx_table_bind(gx_ctx *ctx, const gx_coldesc *cols, int ncols,
                         gx_table **out);
 gx_status gx_table_free(gx_table *t);
@@ -143,14 +150,17 @@ gx_status gx_decode_column_varlena(gx_ctx *ctx, const gx_table *t, int col,
                                    int verify_checksums);
 
 /* TPC-H Q1 core (BASELINE config 4): GROUP BY returnflag,linestatus with
- * COUNT/SUM over a GX_TPCH_LINEITEM_Q1 table; AVG = sum/count (float8_avg) */
+ * COUNT/SUM over a GX_TPCH_LINEITEM_Q1 table; AVG = sum/count (float8_avg).
+ * The table must be five format-0 columns of widths [1, 1, 8, 8, 4]
+ * (GX_ERR_INVALID otherwise). */
 gx_status gx_q1(gx_ctx *ctx, const gx_table *t, int32_t cutoff,
                 int64_t *counts6, double *sum_price6, double *sum_rev6,
                 double *ms_out);
 
 /* standalone columnar scan + filter count (the SeqScan+qual slice;
- * BASELINE config 2): op 0 '<', 1 '>', 2 '=', 3 '!=' vs an integer/date
- * literal; ms_out = kernel time from HIP events */
+ * BASELINE config 2): op is a gx_filter op (0..5, below) vs an integer/date
+ * literal of any int64 value, compared as the cross-type operator would
+ * (see gx_filter); ms_out = kernel time from HIP events */
 gx_status gx_scan_filter(gx_ctx *ctx, const gx_table *t, int col, int op,
                          int64_t literal, int64_t *count_out, double *ms_out);
 
@@ -213,6 +223,13 @@ gx_status gx_q3_prepare(gx_ctx *ctx, gx_table *customer, gx_table *orders,
 /* ---- plan-descriptor form (what PlanCustomPath lowering
  * fills; tagged structs, no expression trees yet).  Filter ops:
  * 0 '<', 1 '>', 2 '=', 3 '!=', 4 '<=', 5 '>='. ---- */
+/* The literal is an int64 whatever the column's width, and the comparison
+ * is the mathematically correct cross-type one (int48lt etc.): on an int8
+ * column `v < 300` is always true and `v = 300` always false.  The kernels
+ * compare in the column type, so the host folds <op, literal> first: an
+ * out-of-range literal becomes v >= TYPE_MIN (always true) or v < TYPE_MIN
+ * (always false); in-range pairs pass through.  An op outside 0..5 in a
+ * primary filter or gx_scan_filter is GX_ERR_INVALID. */
 typedef struct gx_filter {
     int32_t col;               /* column index in the role's table */
     int32_t op;

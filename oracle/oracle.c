@@ -362,6 +362,39 @@ int orc_gen_lineitem(double sf, uint64_t seed, int seg, int nsegs, orc_lineitem 
     return 0;
 }
 
+/* Q1 columns of lineitem, row for row the table orc_gen_lineitem builds
+ * (same order loop, same per-row formulas orc_q1 uses inline). */
+int orc_gen_lineitem_q1(double sf, uint64_t seed, int seg, int nsegs,
+                        orc_lineitem_q1 *out)
+{
+    int64_t nord = orc_norders(sf), n = 0, kept = 0;
+    for (int64_t o = 1; o <= nord; o++)
+        if (nsegs <= 1 || orc_route_i64(o, nsegs) == seg)
+            n += gen_nlines(seed, o);
+    int64_t cap = n > 0 ? n : 1;
+    out->l_returnflag = malloc(cap);
+    out->l_linestatus = malloc(cap);
+    out->l_extendedprice = malloc(sizeof(double) * cap);
+    out->l_discount = malloc(sizeof(double) * cap);
+    out->l_shipdate = malloc(sizeof(int32_t) * cap);
+    for (int64_t o = 1; o <= nord; o++)
+    {
+        if (nsegs > 1 && orc_route_i64(o, nsegs) != seg) continue;
+        int32_t nl = gen_nlines(seed, o);
+        for (int32_t j = 0; j < nl; j++)
+        {
+            out->l_returnflag[kept] = (int8_t) gen_returnflag(seed, o, j);
+            out->l_linestatus[kept] = (int8_t) gen_linestatus(seed, o, j);
+            out->l_extendedprice[kept] = gen_price(seed, o, j);
+            out->l_discount[kept] = gen_discount(seed, o, j);
+            out->l_shipdate[kept] = gen_shipdate(seed, o, j);
+            kept++;
+        }
+    }
+    out->n = kept;
+    return 0;
+}
+
 void orc_free_customer(orc_customer *c)
 { free(c->c_custkey); free(c->c_mktsegment); c->c_custkey = NULL; c->c_mktsegment = NULL; }
 void orc_free_orders(orc_orders *o)

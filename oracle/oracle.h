@@ -81,7 +81,7 @@ int64_t orc_ncustomer(double sf);
 int64_t orc_norders(double sf);
 
 /* ---- AOCS column-store codec (byte-exact vs reference writer) ---- */
-/* returns bytes written, or -1 on error.  width in {4,8}. */
+/* returns bytes written, or -1 on error.  width in {1,4,8}. */
 int64_t orc_aocs_encode(const void *vals, int width, int64_t nrows,
                         int64_t first_rownum, int32_t blocksize,
                         uint8_t *out, int64_t outcap);
@@ -198,6 +198,18 @@ typedef struct {
     double  sum_revenue;
 } orc_q1_group;
 int orc_q1(double sf, uint64_t seed, int32_t cutoff, orc_q1_group *out6);
+/* the rows orc_q1 aggregates, materialized (same row order as
+ * orc_gen_lineitem); arrays are malloc'd, free each with orc_free() */
+typedef struct {
+    int8_t  *l_returnflag;
+    int8_t  *l_linestatus;
+    double  *l_extendedprice;
+    double  *l_discount;
+    int32_t *l_shipdate;
+    int64_t  n;
+} orc_lineitem_q1;
+int orc_gen_lineitem_q1(double sf, uint64_t seed, int seg, int nsegs,
+                        orc_lineitem_q1 *out);
 
 #ifdef __cplusplus
 }

@@ -181,6 +181,33 @@ def q1(sf, cutoff, seed=42):
             "sum_revenue": np.array([g.sum_revenue for g in out])}
 
 
+class _LineitemQ1(ctypes.Structure):
+    _fields_ = [("l_returnflag", ctypes.POINTER(ctypes.c_int8)),
+                ("l_linestatus", ctypes.POINTER(ctypes.c_int8)),
+                ("l_extendedprice", ctypes.POINTER(ctypes.c_double)),
+                ("l_discount", ctypes.POINTER(ctypes.c_double)),
+                ("l_shipdate", ctypes.POINTER(ctypes.c_int32)),
+                ("n", ctypes.c_int64)]
+
+
+def gen_lineitem_q1(sf, seed=42, seg=0, nsegs=1):
+    """The Q1 columns of lineitem, row for row gen_lineitem's table."""
+    lib.orc_gen_lineitem_q1.restype = ctypes.c_int
+    lib.orc_gen_lineitem_q1.argtypes = [ctypes.c_double, ctypes.c_uint64,
+                                        ctypes.c_int, ctypes.c_int,
+                                        ctypes.POINTER(_LineitemQ1)]
+    t = _LineitemQ1()
+    assert lib.orc_gen_lineitem_q1(sf, seed, seg, nsegs, ctypes.byref(t)) == 0
+    fields = (("l_returnflag", np.int8), ("l_linestatus", np.int8),
+              ("l_extendedprice", np.float64), ("l_discount", np.float64),
+              ("l_shipdate", np.int32))
+    out = {f: (_np(getattr(t, f), t.n, dt) if t.n else np.zeros(0, dt))
+           for f, dt in fields}
+    for f, _ in fields:
+        lib.orc_free(getattr(t, f))
+    return out
+
+
 _refw = None
 
 
@@ -380,14 +407,15 @@ def cdbhash_multi(vals, types, isnull=None):
                                  types.ctypes.data, len(vals))
 
 
-def aocs_encode(vals):
+def aocs_encode(vals, blocksize=32768):
     """Encode a fixed-width NOT NULL numpy column into an AOCS stream (bytes)."""
     vals = np.ascontiguousarray(vals)
     width = vals.itemsize
     n = len(vals)
-    cap = lib.orc_aocs_encoded_size(width, n, 32768)
+    cap = lib.orc_aocs_encoded_size(width, n, blocksize)
     buf = np.zeros(cap, np.uint8)
-    got = lib.orc_aocs_encode(vals.ctypes.data, width, n, 1, 32768, buf.ctypes.data, cap)
+    got = lib.orc_aocs_encode(vals.ctypes.data, width, n, 1, blocksize,
+                              buf.ctypes.data, cap)
     assert got == cap, (got, cap)
     return buf.tobytes()
 

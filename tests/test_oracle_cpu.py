@@ -467,6 +467,45 @@ def test_q1_oracle_vs_numpy():
                                    li["l_extendedprice"][m].sum(), rtol=1e-9)
 
 
+def test_gen_lineitem_q1_matches_q1_and_lineitem():
+    """gen_lineitem_q1 materializes the rows orc_q1 aggregates inline: its
+    shared columns equal gen_lineitem's, numpy-aggregating it reproduces
+    orc_q1's counts exactly, and a shard is the matching slice of rows."""
+    sf, seed = 0.02, 42
+    q = orc.gen_lineitem_q1(sf, seed)
+    li = orc.gen_lineitem(sf, seed)
+    for f in ("l_extendedprice", "l_discount", "l_shipdate"):
+        np.testing.assert_array_equal(q[f], li[f])
+    assert q["l_returnflag"].dtype == np.int8 and q["l_linestatus"].dtype == np.int8
+    assert set(np.unique(q["l_returnflag"])) == {0, 1, 2}
+    assert set(np.unique(q["l_linestatus"])) == {0, 1}
+    g = q["l_returnflag"].astype(np.int64) * 2 + q["l_linestatus"]
+    lo, hi = int(q["l_shipdate"].min()), int(q["l_shipdate"].max())
+    for cut in (lo - 1, orc.lib.orc_date_adt(1995, 3, 15),
+                orc.lib.orc_date_adt(1998, 9, 2), hi):
+        want = orc.q1(sf, cut, seed)
+        ok = q["l_shipdate"] <= cut
+        got = np.bincount(g[ok], minlength=6)
+        np.testing.assert_array_equal(got, want["count"])
+        for gi in range(6):
+            m = ok & (g == gi)
+            np.testing.assert_allclose(q["l_extendedprice"][m].sum(),
+                                       want["sum_price"][gi], rtol=1e-9)
+            np.testing.assert_allclose(
+                (q["l_extendedprice"][m] * (1.0 - q["l_discount"][m])).sum(),
+                want["sum_revenue"][gi], rtol=1e-9)
+    # sharded: same rows as gen_lineitem's shard, and shards partition the table
+    tot = 0
+    for seg in range(3):
+        qs = orc.gen_lineitem_q1(sf, seed, seg, 3)
+        ls = orc.gen_lineitem(sf, seed, seg, 3)
+        np.testing.assert_array_equal(qs["l_shipdate"], ls["l_shipdate"])
+        np.testing.assert_array_equal(qs["l_extendedprice"], ls["l_extendedprice"])
+        tot += len(qs["l_returnflag"])
+    assert tot == len(q["l_returnflag"])
+    assert len(orc.gen_lineitem_q1(0.0)["l_returnflag"]) == 0
+
+
 # ---------------- REFERENCE-writer parity (the strongest format pin) ----------------
 
 def _ref_fixture_values():
