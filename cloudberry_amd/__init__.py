@@ -193,6 +193,7 @@ def _load():
     lib.gx_q3_set_numeric.argtypes = [ctypes.c_void_p, ctypes.c_int]
     lib.gx_q3_run.argtypes = [ctypes.c_void_p]
     lib.gx_q3_stats_get.argtypes = [ctypes.c_void_p, ctypes.POINTER(_Stats)]
+    lib.gx_q3_dim_mode.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
     lib.gx_q3_result.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.POINTER(_Group)),
                                  ctypes.POINTER(ctypes.c_int64)]
     lib.gx_q3_topn.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
@@ -612,6 +613,13 @@ class Q3:
         s = _Stats()
         self.ctx._chk(self.ctx._lib.gx_q3_stats_get(self._q, ctypes.byref(s)))
         return {f: getattr(s, f) for f, _ in s._fields_}
+
+    def dim_mode(self):
+        """Dim membership form the last run read: 0 = bloom + hash set,
+        1 = exact bitmap (dense keys, local path)."""
+        m = ctypes.c_int()
+        self.ctx._chk(self.ctx._lib.gx_q3_dim_mode(self._q, ctypes.byref(m)))
+        return m.value
 
     def result(self):
         gp = ctypes.POINTER(_Group)()

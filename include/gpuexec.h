@@ -304,6 +304,12 @@ gx_status gx_q3_prepare_desc(gx_ctx *ctx, const gx_q3_desc *desc, gx_q3 **out);
 gx_status gx_q3_set_numeric(gx_q3 *q, int on);
 gx_status gx_q3_run(gx_q3 *q);   /* one full pass; re-runnable (bench steps) */
 gx_status gx_q3_stats_get(const gx_q3 *q, gx_q3_stats *out);
+/* Form of the dim membership structure the LAST run's mid-table filter read:
+ * 0 = bloom + hash set, 1 = exact bitmap.  Sizing picks the bitmap when the
+ * qualifying dim keys are dense (max - min + 1 <= 64 * their count) and
+ * GX_DIM_BITMAP is not 0; only the local (single-segment, no forced Motion)
+ * path reads it.  GX_ERR_STATE before the first run. */
+gx_status gx_q3_dim_mode(gx_q3 *q, int *mode);
 /* groups of THIS segment, sorted by l_orderkey asc; caller frees with gx_free */
 gx_status gx_q3_result(gx_q3 *q, gx_q3_group **out, int64_t *ngroups);
 /* top-N of this segment's groups (Q3's ORDER BY revenue DESC, o_orderdate
