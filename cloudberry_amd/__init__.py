@@ -40,6 +40,14 @@ class _Group(ctypes.Structure):
                 ("_pad", ctypes.c_uint8 * 6)]
 
 
+# numpy mirror of gx_q3_group (48 B)
+Q3_GROUP_DTYPE = np.dtype([("l_orderkey", np.int64), ("o_orderdate", np.int32),
+                           ("o_shippriority", np.int32),
+                           ("revenue", np.float64), ("revenue_num", np.int64),
+                           ("nitems", np.int64), ("key_is_null", np.uint8),
+                           ("attrs_null", np.uint8), ("_pad", np.uint8, (6,))])
+
+
 class _Stats(ctypes.Structure):
     _fields_ = [("ms_cust_build", ctypes.c_double),
                 ("ms_orders_build", ctypes.c_double),
@@ -84,6 +92,27 @@ class _GbStats(ctypes.Structure):
 class _Filter(ctypes.Structure):
     _fields_ = [("col", ctypes.c_int32), ("op", ctypes.c_int32),
                 ("literal", ctypes.c_int64)]
+
+
+class _TblLayout(ctypes.Structure):
+    _fields_ = [("key_width", ctypes.c_int32), ("interpolated", ctypes.c_int32),
+                ("slots", ctypes.c_uint64), ("kmin", ctypes.c_int64),
+                ("scale", ctypes.c_double), ("slot_kmin", ctypes.c_uint64),
+                ("slot_kmax", ctypes.c_uint64)]
+
+
+_OPS = {"<": 0, ">": 1, "==": 2, "!=": 3, "<=": 4, ">=": 5}
+_DIM_JOINS = {"semi": 0, "anti": 1, "anti_notin": 2}
+
+# numpy mirrors of the Motion wire rows (gx_ord_row, gx_qual_row_abi)
+ORD_ROW_DTYPE = np.dtype([("okey", np.int64), ("ocust", np.int64),
+                          ("odate", np.int32), ("oprio", np.int32)])
+QUAL_ROW_DTYPE = np.dtype([("okey", np.int64), ("odate", np.int32),
+                           ("oprio", np.int32)])
+
+
+def _opcode(op):                # symbol, or a raw gx_filter op code
+    return op if isinstance(op, int) else _OPS[op]
 
 
 class _Q3Desc(ctypes.Structure):
@@ -212,6 +241,33 @@ def _load():
                                          ctypes.c_int32,
                                          ctypes.POINTER(ctypes.POINTER(_Group)),
                                          ctypes.POINTER(ctypes.c_int64)]
+    lib.gx_test_m1.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
+                               ctypes.POINTER(_Filter), ctypes.c_int,
+                               ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
+                               ctypes.c_void_p, ctypes.c_void_p,
+                               ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
+    lib.gx_test_dim.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
+                                ctypes.c_int32, ctypes.c_int64,
+                                ctypes.c_uint64, ctypes.c_void_p,
+                                ctypes.POINTER(ctypes.c_int64),
+                                ctypes.POINTER(ctypes.c_int32)]
+    lib.gx_test_m2.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
+                               ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64,
+                               ctypes.c_void_p, ctypes.c_int64, ctypes.c_int,
+                               ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                               ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
+                               ctypes.POINTER(ctypes.c_int32)]
+    lib.gx_test_m3.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                               ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,
+                               ctypes.POINTER(ctypes.POINTER(_Group)),
+                               ctypes.POINTER(ctypes.c_int64),
+                               ctypes.POINTER(_TblLayout)]
+    lib.gx_selftest_motion_layout.restype = ctypes.c_int
+    lib.gx_selftest_motion_layout.argtypes = [
+        ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+        ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
+        ctypes.POINTER(_TblLayout)]
     return lib
 
 
@@ -223,6 +279,40 @@ def lib():
     if _lib is None:
         _lib = _load()
     return _lib
+
+
+def _layout_dict(lay):
+    return {f: getattr(lay, f) for f, _ in lay._fields_}
+
+
+def motion_exchange_layout(cnts_all, seg):
+    """The Motion path's send/receive bookkeeping (host only, no GPU):
+    cnts_all is the all-gathered n×n count matrix, row r = rank r's
+    per-destination counts.  Returns (scnt, soff, rcnt, roff) of rank seg as
+    uint64 arrays; the offsets have n + 1 entries, the last the total."""
+    c = np.ascontiguousarray(cnts_all, np.uint64)
+    n = c.shape[0]
+    assert c.shape == (n, n)
+    scnt, rcnt = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+    soff, roff = np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.uint64)
+    rc = lib().gx_selftest_motion_layout(
+        c.ctypes.data, n, seg, scnt.ctypes.data, soff.ctypes.data,
+        rcnt.ctypes.data, roff.ctypes.data, 0, 0, 0, 1, 300, None)
+    if rc != 0:
+        raise ValueError(f"gx_selftest_motion_layout: bad arguments ({rc})")
+    return scnt, soff, rcnt, roff
+
+
+def motion_table_layout(qual, kmin, kmax, nsegs, tf_pct=300):
+    """The Motion path's join-table layout for qual received keys spanning
+    [kmin, kmax] (host only, no GPU): gx_test_tbl_layout as a dict."""
+    lay = _TblLayout()
+    rc = lib().gx_selftest_motion_layout(None, 0, 0, None, None, None, None,
+                                         qual, kmin, kmax, nsegs, tf_pct,
+                                         ctypes.byref(lay))
+    if rc != 0:
+        raise ValueError(f"gx_selftest_motion_layout: bad arguments ({rc})")
+    return _layout_dict(lay)
 
 
 class Context:
@@ -411,6 +501,93 @@ class Context:
                                       np.bool_)}
         self._lib.gx_free(gp)
         return res
+
+    # ---- Motion stages of the nsegs>1 Q3 path, one rank at a time ----
+
+    def test_m1(self, orders, mid_filter, nsegs, dim_join="semi",
+                bloom_all=None):
+        """Motion 1 of one rank: mid_filter = (col, op, literal) on orders
+        (visimap honoured); bloom_all = (nsegs, bwords) uint64 array of every
+        rank's dim bloom, or None.  Returns (counts, ORD_ROW_DTYPE rows packed
+        by destination)."""
+        col, op, lit = mid_filter
+        f = _Filter(col, _opcode(op), int(lit))
+        cap = orders.nrows
+        counts = np.zeros(nsegs, np.int64)
+        rows = np.zeros(cap, ORD_ROW_DTYPE)
+        total = ctypes.c_int64()
+        bptr, bwords = None, 0
+        if bloom_all is not None:
+            bloom_all = np.ascontiguousarray(bloom_all, np.uint64)
+            assert bloom_all.ndim == 2 and bloom_all.shape[0] == nsegs
+            bptr, bwords = bloom_all.ctypes.data, bloom_all.shape[1]
+        self._chk(self._lib.gx_test_m1(
+            self._h, orders._t, ctypes.byref(f), nsegs, _DIM_JOINS[dim_join],
+            bptr, bwords, counts.ctypes.data, rows.ctypes.data, cap,
+            ctypes.byref(total)))
+        return counts, rows[:total.value]
+
+    def test_dim(self, customer, dim_filter, bwords):
+        """Dim side of one rank: dim_filter = (op, literal) on the int8
+        column.  Returns (bloom words uint64[bwords], selected rows, set
+        width production picks)."""
+        op, lit = dim_filter
+        bloom = np.zeros(bwords, np.uint64)
+        nsel = ctypes.c_int64()
+        width = ctypes.c_int32()
+        self._chk(self._lib.gx_test_dim(
+            self._h, customer._t, _opcode(op), int(lit), bwords,
+            bloom.ctypes.data, ctypes.byref(nsel), ctypes.byref(width)))
+        return bloom, nsel.value, width.value
+
+    def test_m2(self, customer, dim_filter, rows, nsegs, dim_join="semi",
+                bwords=0):
+        """Motion 2 of one rank: received ORD_ROW_DTYPE rows against this
+        rank's dim set.  Returns (counts, QUAL_ROW_DTYPE rows packed by
+        destination, set width)."""
+        op, lit = dim_filter
+        rows = np.ascontiguousarray(rows, ORD_ROW_DTYPE)
+        n = len(rows)
+        counts = np.zeros(nsegs, np.int64)
+        out = np.zeros(n, QUAL_ROW_DTYPE)
+        total = ctypes.c_int64()
+        width = ctypes.c_int32()
+        self._chk(self._lib.gx_test_m2(
+            self._h, customer._t, _opcode(op), int(lit), bwords,
+            rows.ctypes.data if n else None, n, _DIM_JOINS[dim_join], nsegs,
+            counts.ctypes.data, out.ctypes.data if n else None, n,
+            ctypes.byref(total), ctypes.byref(width)))
+        return counts, out[:total.value], width.value
+
+    def test_m3(self, qual_rows, lineitem, fact_filter):
+        """Motion 3 of one rank (nsegs of this context): table from received
+        QUAL_ROW_DTYPE rows, probe + aggregate lineitem under fact_filter =
+        (op, literal) on shipdate, visimap honoured.  Returns (groups dict
+        sorted by key, table layout dict)."""
+        op, lit = fact_filter
+        qual_rows = np.ascontiguousarray(qual_rows, QUAL_ROW_DTYPE)
+        n = len(qual_rows)
+        gp = ctypes.POINTER(_Group)()
+        ng = ctypes.c_int64()
+        lay = _TblLayout()
+        self._chk(self._lib.gx_test_m3(
+            self._h, qual_rows.ctypes.data if n else None, n, lineitem._t,
+            _opcode(op), int(lit), ctypes.byref(gp), ctypes.byref(ng),
+            ctypes.byref(lay)))
+        m = ng.value
+        raw = ctypes.string_at(gp, m * ctypes.sizeof(_Group)) if m else b""
+        self._lib.gx_free(gp)
+        g = np.frombuffer(raw, Q3_GROUP_DTYPE)
+        res = {"l_orderkey": g["l_orderkey"].copy(),
+               "o_orderdate": g["o_orderdate"].copy(),
+               "o_shippriority": g["o_shippriority"].copy(),
+               "revenue": g["revenue"].copy(),
+               "revenue_num": g["revenue_num"].copy(),
+               "nitems": g["nitems"].copy(),
+               "key_is_null": g["key_is_null"].copy(),
+               "attrs_null": g["attrs_null"].copy(),
+               "_pad": g["_pad"].copy()}
+        return res, _layout_dict(lay)
 
     def q1(self, lineitem_q1, cutoff):
         """TPC-H Q1 core: returns dict of 6-group arrays + kernel ms."""

@@ -752,7 +752,7 @@ struct gx_slotmap {
     uint64_t mask;
     int64_t kmin;
     double scale;          /* tslots / (range+1); <0 ⇒ use hmix */
-    __device__ __forceinline__ uint64_t slot0(uint64_t k) const
+    __host__ __device__ __forceinline__ uint64_t slot0(uint64_t k) const
     {
         if (scale < 0.0)
             return gx_hmix64(k) & mask;
@@ -5551,6 +5551,307 @@ static gx_status q3_size_and_alloc(gx_q3 *q)
     return GX_OK;
 }
 
+/* ================= Motion stage seams =================
+ * Everything of the nsegs>1 branch of gx_q3_run that is not an RCCL call
+ * lives in the helpers below.  They take all inputs as arguments and never
+ * reach into gx_q3, so the test-only entry points at the end of this file
+ * drive the very same launches, dispatch and layout rules with any nsegs on
+ * one GPU ("Test seams of the Motion path"). */
+
+/* the destination-bloom prefilter of Motion 1 applies to the semi join only:
+ * for the anti joins non-membership is the keep condition */
+static inline bool m1_prefilter_on(int dim_join) { return dim_join == 0; }
+
+/* Motion 1, pass 1: per-destination histogram of the filtered mid rows.
+ * bloom_all (nsegs * (bwmask + 1) words, rank-major) is ignored unless the
+ * prefilter applies to dim_join. */
+static void m1_launch_hist(hipStream_t s, const gx_col &od, const gx_col &oc,
+                           const uint8_t *vmap, int32_t fop, int32_t flit,
+                           int nsegs, int dim_join,
+                           const unsigned long long *bloom_all, uint64_t bwmask,
+                           unsigned long long *dhist)
+{
+    if (!m1_prefilter_on(dim_join)) bloom_all = nullptr;
+    hipLaunchKernelGGL(k_ord_m1_hist, dim3(GRID), dim3(TPB), 0, s,
+                       od.dstream, od.m, oc.dstream, oc.m, vmap,
+                       fop, flit, nsegs, bloom_all, bwmask, dhist);
+}
+
+/* Motion 1, pass 2: emit the packed rows; dcur holds the region starts */
+static void m1_launch_emit(hipStream_t s, const gx_col &ok, const gx_col &oc,
+                           const gx_col &od, const gx_col &op,
+                           const uint8_t *vmap, int32_t fop, int32_t flit,
+                           int nsegs, int dim_join,
+                           const unsigned long long *bloom_all, uint64_t bwmask,
+                           unsigned long long *dcur, gx_ord_row *send)
+{
+    if (!m1_prefilter_on(dim_join)) bloom_all = nullptr;
+    hipLaunchKernelGGL(k_ord_m1_emit, dim3(GRID), dim3(TPB), 0, s,
+                       ok.dstream, ok.m, oc.dstream, oc.m, od.dstream, od.m,
+                       op.dstream, op.m, vmap, fop, flit, nsegs,
+                       bloom_all, bwmask, dcur, send);
+}
+
+/* Motion 2: probe the local dim set with the received rows, histogram /
+ * emit by route(mid key).  Dispatch on the dim-set width (4 or 8 bytes) and
+ * on semi (dim_join == 0) against anti. */
+static void m2_launch_hist(hipStream_t s, const gx_ord_row *recv, int64_t n,
+                           const void *cset, int cset_width, uint64_t cmask,
+                           const unsigned long long *bloom, uint64_t bwmask,
+                           int dim_join, int nsegs, unsigned long long *dhist)
+{
+    auto go = [&](auto *cs, auto anti) {
+        hipLaunchKernelGGL((k_qual_hist<std::decay_t<decltype(*cs)>,
+                                        decltype(anti)::value>),
+                           dim3(GRID), dim3(TPB), 0, s,
+                           recv, n, cs, cmask, bloom, bwmask, nsegs, dhist);
+    };
+    bool anti_join = dim_join != 0;
+    if (cset_width == 4 && anti_join)
+        go((const unsigned int *) cset, std::true_type{});
+    else if (cset_width == 4)
+        go((const unsigned int *) cset, std::false_type{});
+    else if (anti_join)
+        go((const unsigned long long *) cset, std::true_type{});
+    else
+        go((const unsigned long long *) cset, std::false_type{});
+}
+
+static void m2_launch_emit(hipStream_t s, const gx_ord_row *recv, int64_t n,
+                           const void *cset, int cset_width, uint64_t cmask,
+                           const unsigned long long *bloom, uint64_t bwmask,
+                           int dim_join, int nsegs, unsigned long long *dcur,
+                           gx_qual_row *send)
+{
+    auto go = [&](auto *cs, auto anti) {
+        hipLaunchKernelGGL((k_qual_emit<std::decay_t<decltype(*cs)>,
+                                        decltype(anti)::value>),
+                           dim3(GRID), dim3(TPB), 0, s,
+                           recv, n, cs, cmask, bloom, bwmask, nsegs, dcur, send);
+    };
+    bool anti_join = dim_join != 0;
+    if (cset_width == 4 && anti_join)
+        go((const unsigned int *) cset, std::true_type{});
+    else if (cset_width == 4)
+        go((const unsigned int *) cset, std::false_type{});
+    else if (anti_join)
+        go((const unsigned long long *) cset, std::true_type{});
+    else
+        go((const unsigned long long *) cset, std::false_type{});
+}
+
+/* Send/receive layout of one Motion (pure host).  cnts_all is the
+ * all-gathered n×n count matrix, row r = rank r's per-destination histogram.
+ * Rank seg sends its own row (cnts_all[seg*n + i] rows to rank i) and
+ * receives its column (cnts_all[r*n + seg] rows from rank r); the offsets
+ * are the exclusive prefix sums, entry n the totals. */
+struct gx_mlayout {
+    std::vector<unsigned long long> scnt, soff, rcnt, roff;
+    unsigned long long send_n = 0, recv_n = 0;
+};
+
+static gx_mlayout m_exchange_layout(const unsigned long long *cnts_all, int n,
+                                    int seg)
+{
+    gx_mlayout L;
+    L.scnt.assign(n, 0); L.rcnt.assign(n, 0);
+    L.soff.assign(n + 1, 0); L.roff.assign(n + 1, 0);
+    for (int i = 0; i < n; i++) L.scnt[i] = cnts_all[(int64_t) seg * n + i];
+    for (int i = 0; i < n; i++) L.soff[i + 1] = L.soff[i] + L.scnt[i];
+    for (int r = 0; r < n; r++) L.rcnt[r] = cnts_all[(int64_t) r * n + seg];
+    for (int r = 0; r < n; r++) L.roff[r + 1] = L.roff[r] + L.rcnt[r];
+    L.send_n = L.soff[n];
+    L.recv_n = L.roff[n];
+    return L;
+}
+
+/* Slot map of a join/agg table of `slots` slots over the received keys:
+ * order-preserving interpolation when their density over [kmin,kmax] is
+ * high enough that runs stay short (the local rule, relaxed by nsegs since
+ * each rank holds ~1/nsegs of a globally dense key range), otherwise
+ * multiplicative hashing (scale < 0). */
+static gx_slotmap m3_slotmap(int64_t qual, unsigned long long kmin,
+                             unsigned long long kmax, int nsegs, uint64_t slots)
+{
+    gx_slotmap sm;
+    sm.mask = slots - 1;
+    sm.kmin = (int64_t) kmin;
+    sm.scale = -1.0;
+    if (qual > 0 && kmax >= kmin)
+    {
+        double range = (double) (kmax - kmin) + 1.0;
+        if ((double) qual >= range / ((double) nsegs * 64.0))
+            sm.scale = (double) slots / range;
+    }
+    return sm;
+}
+
+/* Table layout from the received rows (pure host): 4-byte keys when every
+ * key fits, slots = qual * tf_pct/100 pow2-rounded and always > qual (an
+ * open-addressing table with no free slot would never terminate an insert),
+ * slot map for exactly that many slots.  Whether a larger cached table is
+ * reused instead is the caller's decision; it then re-derives the slot map
+ * with m3_slotmap for the slots it really has. */
+struct gx_tbl_layout {
+    int key_width;
+    uint64_t slots;
+    gx_slotmap smap;
+};
+
+static gx_tbl_layout m3_table_layout(int64_t qual, unsigned long long kmin,
+                                     unsigned long long kmax, int nsegs,
+                                     int tf_pct)
+{
+    gx_tbl_layout L;
+    L.key_width = (kmax < (1ULL << 32)) ? 4 : 8;
+    L.slots = (uint64_t) pow2_at_least(
+        std::max<int64_t>(qual * tf_pct / 100, qual) + 1);
+    L.smap = m3_slotmap(qual, kmin, kmax, nsegs, L.slots);
+    return L;
+}
+
+/* Build the join/agg table from packed qualifying rows; dn (optional,
+ * device) caps n (see k_build_from_rows). */
+static void m3_launch_build(hipStream_t s, const gx_qual_row *rows, int64_t n,
+                            const unsigned long long *dn, int key_width,
+                            void *tkey, gx_attrpair *tattr, gx_aggslot *tagg,
+                            gx_slotmap smap)
+{
+    if (key_width == 4)
+        hipLaunchKernelGGL(k_build_from_rows<unsigned int>,
+                           dim3(GRID), dim3(TPB), 0, s, rows, n, dn,
+                           (unsigned int *) tkey, tattr, tagg, smap);
+    else
+        hipLaunchKernelGGL(k_build_from_rows<unsigned long long>,
+                           dim3(GRID), dim3(TPB), 0, s, rows, n, dn,
+                           (unsigned long long *) tkey, tattr, tagg, smap);
+}
+
+/* Stage 3, f64 measures over a plain fact key: probe + aggregate with the
+ * variant GX_PROBE_VARIANT selects (0 = the tuned default; the others are
+ * A/B experiments without visimap/outer support). */
+static gx_status q3_launch_probe(gx_ctx *ctx, hipStream_t s,
+                                 const gx_col &lk, const gx_col &lp,
+                                 const gx_col &ld, const gx_col &ls,
+                                 const uint8_t *lvm, int32_t fop, int32_t flit,
+                                 int key_width, const void *tkey,
+                                 gx_aggslot *tagg, gx_slotmap smap,
+                                 unsigned long long *dhits, bool outer,
+                                 unsigned long long *ukey, double *urev,
+                                 unsigned long long *ucnt_u, uint64_t umask)
+{
+    const char *pv = getenv("GX_PROBE_VARIANT");
+    int variant = pv ? atoi(pv) : 0;
+    if (variant != 0 && (lvm || outer))
+    {
+        set_err(ctx, "visimap/extra quals/outer require the default probe variant%s", "");
+        return GX_ERR_INVALID;
+    }
+    const char *pg = getenv("GX_PROBE_GRID");
+    int pgrid = pg ? atoi(pg) : GRID;
+    const char *pt = getenv("GX_PROBE_TPB");
+    int ptpb = pt ? atoi(pt) : TPB;
+    auto launch = [&](auto kern, auto *keys) {
+        hipLaunchKernelGGL(kern, dim3(pgrid), dim3(ptpb), 0, s,
+                           lk.dstream, lk.m, lp.dstream, lp.m, ld.dstream, ld.m,
+                           ls.dstream, ls.m, lvm, fop, flit, keys,
+                           tagg, smap, dhits, ukey, urev, ucnt_u, umask);
+    };
+    if (key_width == 4)
+    {
+        auto *keys = (const unsigned int *) tkey;
+        switch (variant)
+        {
+            default:
+            case 0:
+                if (outer && lvm)
+                    launch((k_li_probe_agg_t<1, unsigned int, true, true>), keys);
+                else if (outer)
+                    launch((k_li_probe_agg_t<1, unsigned int, false, true>), keys);
+                else if (lvm)
+                    launch((k_li_probe_agg_t<1, unsigned int, true>), keys);
+                else
+                    launch(k_li_probe_agg_t<1, unsigned int>, keys);
+                break;
+            case 2: launch(k_li_probe_agg_t<4, unsigned int>, keys); break;
+            case 4: launch(k_li_probe_agg_t<2, unsigned int>, keys); break;
+            case 5: launch(k_li_probe_agg_t<8, unsigned int>, keys); break;
+            case 6: launch(k_li_probe_agg_t<-1, unsigned int>, keys); break;
+            case 7: launch(k_li_probe_agg_t<-4, unsigned int>, keys); break;
+            case 8: launch(k_li_probe_agg_t<-2, unsigned int>, keys); break;
+            case 9: launch(k_li_probe_agg_t<-5, unsigned int>, keys); break;
+            case 10: launch(k_li_probe_agg_t<-6, unsigned int>, keys); break;
+            case 11: launch(k_li_probe_agg_t<-9, unsigned int>, keys); break;
+            case 12: launch(k_li_probe_agg_t<-10, unsigned int>, keys); break;
+            case 13: launch(k_li_probe_agg_t<-11, unsigned int>, keys); break;
+            case 14: launch(k_li_probe_agg_t<-12, unsigned int>, keys); break;
+            case 15: launch(k_li_probe_agg_t<-13, unsigned int>, keys); break;
+            case 16: launch(k_li_probe_agg_t<-14, unsigned int>, keys); break;
+        }
+    }
+    else
+    {
+        auto *keys = (const unsigned long long *) tkey;
+        switch (variant)
+        {
+            default:
+            case 0:
+                if (outer && lvm)
+                    launch((k_li_probe_agg_t<1, unsigned long long, true, true>), keys);
+                else if (outer)
+                    launch((k_li_probe_agg_t<1, unsigned long long, false, true>), keys);
+                else if (lvm)
+                    launch((k_li_probe_agg_t<1, unsigned long long, true>), keys);
+                else
+                    launch(k_li_probe_agg_t<1, unsigned long long>, keys);
+                break;
+            case 2: launch(k_li_probe_agg_t<4, unsigned long long>, keys); break;
+            case 4: launch(k_li_probe_agg_t<2, unsigned long long>, keys); break;
+            case 5: launch(k_li_probe_agg_t<8, unsigned long long>, keys); break;
+            case 6: launch(k_li_probe_agg_t<-1, unsigned long long>, keys); break;
+            case 7: launch(k_li_probe_agg_t<-4, unsigned long long>, keys); break;
+            case 8: launch(k_li_probe_agg_t<-2, unsigned long long>, keys); break;
+            case 9: launch(k_li_probe_agg_t<-5, unsigned long long>, keys); break;
+            case 10: launch(k_li_probe_agg_t<-6, unsigned long long>, keys); break;
+            case 11: launch(k_li_probe_agg_t<-9, unsigned long long>, keys); break;
+            case 12: launch(k_li_probe_agg_t<-10, unsigned long long>, keys); break;
+            case 13: launch(k_li_probe_agg_t<-11, unsigned long long>, keys); break;
+            case 14: launch(k_li_probe_agg_t<-12, unsigned long long>, keys); break;
+            case 15: launch(k_li_probe_agg_t<-13, unsigned long long>, keys); break;
+            case 16: launch(k_li_probe_agg_t<-14, unsigned long long>, keys); break;
+        }
+    }
+    return GX_OK;
+}
+
+/* Stage 4: one block per fixed tile of the table, block-ordered extract */
+static gx_status q3_launch_extract(gx_ctx *ctx, hipStream_t s, int key_width,
+                                   const void *tkey, const gx_attrpair *tattr,
+                                   const gx_aggslot *tagg, uint64_t tslots,
+                                   int numeric, int64_t *r_okey,
+                                   int32_t *r_odate, int32_t *r_oprio,
+                                   double *r_rev, int64_t *r_cnt,
+                                   unsigned long long *dcount)
+{
+    uint64_t etiles = (tslots + GX_EXTRACT_TILE - 1) / GX_EXTRACT_TILE;
+    if (etiles > 0x7FFFFFFFULL)
+    {
+        set_err(ctx, "join/agg table too large for the extract grid%s", "");
+        return GX_ERR_INVALID;
+    }
+    if (key_width == 4)
+        hipLaunchKernelGGL(k_extract<unsigned int>, dim3((unsigned) etiles), dim3(TPB), 0, s,
+                           (const unsigned int *) tkey, tattr, tagg,
+                           tslots, numeric,
+                           r_okey, r_odate, r_oprio, r_rev, r_cnt, dcount);
+    else
+        hipLaunchKernelGGL(k_extract<unsigned long long>, dim3((unsigned) etiles), dim3(TPB), 0, s,
+                           (const unsigned long long *) tkey, tattr, tagg,
+                           tslots, numeric,
+                           r_okey, r_odate, r_oprio, r_rev, r_cnt, dcount);
+    return GX_OK;
+}
+
 extern "C" gx_status gx_q3_set_numeric(gx_q3 *q, int on)
 {
     if (!q) return GX_ERR_INVALID;
@@ -5705,18 +6006,8 @@ extern "C" gx_status gx_q3_run(gx_q3 *q)
                 launch_emit((const unsigned int *) q->cset);
             else
                 launch_emit((const unsigned long long *) q->cset);
-            if (q->key_width == 4)
-                hipLaunchKernelGGL(k_build_from_rows<unsigned int>,
-                                   dim3(GRID), dim3(TPB), 0, s,
-                                   q->m_send2, q->rescap, q->dcount,
-                                   (unsigned int *) q->tkey,
-                                   q->tattr, q->tagg, q->smap);
-            else
-                hipLaunchKernelGGL(k_build_from_rows<unsigned long long>,
-                                   dim3(GRID), dim3(TPB), 0, s,
-                                   q->m_send2, q->rescap, q->dcount,
-                                   (unsigned long long *) q->tkey,
-                                   q->tattr, q->tagg, q->smap);
+            m3_launch_build(s, q->m_send2, q->rescap, q->dcount, q->key_width,
+                            q->tkey, q->tattr, q->tagg, q->smap);
         }
         else if (use_bitmap && q->key_width == 4)
             launch_build((unsigned int *) q->tkey, (const unsigned int *) nullptr,
@@ -5782,7 +6073,7 @@ extern "C" gx_status gx_q3_run(gx_q3 *q)
          * the DESTINATION's bloom — the runtime filter pushed across the
          * interconnect.  Requires the local dim build (primary stream). */
         const unsigned long long *bloom_all = nullptr;
-        if (D.dim_join == 0)
+        if (m1_prefilter_on(D.dim_join))
         {
             uint64_t bwords = q->bwmask + 1;
             if (!q->m_bloom_all)
@@ -5794,10 +6085,9 @@ extern "C" gx_status gx_q3_run(gx_q3 *q)
             bloom_all = q->m_bloom_all;
         }
         HIP_CHK(ctx, hipMemsetAsync(dhist, 0, n * 8, s));
-        hipLaunchKernelGGL(k_ord_m1_hist, dim3(GRID), dim3(TPB), 0, s,
-                           od.dstream, od.m, oc.dstream, oc.m, ovm_eff,
-                           D.mid_filter.op, (int32_t) D.mid_filter.literal, n,
-                           bloom_all, q->bwmask, dhist);
+        m1_launch_hist(s, od, oc, ovm_eff, D.mid_filter.op,
+                       (int32_t) D.mid_filter.literal, n, D.dim_join,
+                       bloom_all, q->bwmask, dhist);
         unsigned long long *dcnts_all = q->m_cnts_all;
         double t_counts = 0;
         auto now_ms = []() {
@@ -5812,24 +6102,16 @@ extern "C" gx_status gx_q3_run(gx_q3 *q)
                                     hipMemcpyDeviceToHost, s));
         HIP_CHK(ctx, hipStreamSynchronize(s));
         t_counts += now_ms() - tc0;
-        std::vector<unsigned long long> h1(n);
-        for (int i = 0; i < n; i++) h1[i] = cnts_all[(int64_t) ctx->seg * n + i];
-        std::vector<unsigned long long> off1(n + 1, 0);
-        for (int i = 0; i < n; i++) off1[i + 1] = off1[i] + h1[i];
-        unsigned long long send1_n = off1[n];
-        if (grow(q->m_send1, q->m_send1_cap, send1_n) != GX_OK) return GX_ERR_OOM;
+        const gx_mlayout L1 = m_exchange_layout(cnts_all.data(), n, ctx->seg);
+        const auto &h1 = L1.scnt, &off1 = L1.soff, &rcv1 = L1.rcnt, &roff1 = L1.roff;
+        if (grow(q->m_send1, q->m_send1_cap, L1.send_n) != GX_OK) return GX_ERR_OOM;
         gx_ord_row *send1 = q->m_send1;
         unsigned long long *dcur = q->m_cur;
         HIP_CHK(ctx, hipMemcpyAsync(dcur, off1.data(), n * 8, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_ord_m1_emit, dim3(GRID), dim3(TPB), 0, s,
-                           ok.dstream, ok.m, oc.dstream, oc.m, od.dstream, od.m,
-                           op.dstream, op.m, ovm_eff, D.mid_filter.op,
-                           (int32_t) D.mid_filter.literal, n,
-                           bloom_all, q->bwmask, dcur, send1);
-        std::vector<unsigned long long> rcv1(n), roff1(n + 1, 0);
-        for (int r = 0; r < n; r++) rcv1[r] = cnts_all[(int64_t) r * n + ctx->seg];
-        for (int r = 0; r < n; r++) roff1[r + 1] = roff1[r] + rcv1[r];
-        unsigned long long recv1_n = roff1[n];
+        m1_launch_emit(s, ok, oc, od, op, ovm_eff, D.mid_filter.op,
+                       (int32_t) D.mid_filter.literal, n, D.dim_join,
+                       bloom_all, q->bwmask, dcur, send1);
+        unsigned long long recv1_n = L1.recv_n;
         if (grow(q->m_recv1, q->m_recv1_cap, recv1_n) != GX_OK) return GX_ERR_OOM;
         gx_ord_row *recv1 = q->m_recv1;
         /* self-share bypasses RCCL entirely: a device copy is both faster
@@ -5864,22 +6146,8 @@ extern "C" gx_status gx_q3_run(gx_q3 *q)
          * stream to finish */
         HIP_CHK(ctx, hipStreamWaitEvent(s, ev[1], 0));
         HIP_CHK(ctx, hipMemsetAsync(dhist, 0, n * 8, s));
-        bool anti_join = D.dim_join != 0;
-        auto launch_qhist = [&](auto *cs, auto anti) {
-            hipLaunchKernelGGL((k_qual_hist<std::decay_t<decltype(*cs)>,
-                                            decltype(anti)::value>),
-                               dim3(GRID), dim3(TPB), 0, s,
-                               recv1, (int64_t) recv1_n, cs,
-                               q->cmask, q->bloom, q->bwmask, n, dhist);
-        };
-        if (q->cset_width == 4 && anti_join)
-            launch_qhist((const unsigned int *) q->cset, std::true_type{});
-        else if (q->cset_width == 4)
-            launch_qhist((const unsigned int *) q->cset, std::false_type{});
-        else if (anti_join)
-            launch_qhist((const unsigned long long *) q->cset, std::true_type{});
-        else
-            launch_qhist((const unsigned long long *) q->cset, std::false_type{});
+        m2_launch_hist(s, recv1, (int64_t) recv1_n, q->cset, q->cset_width,
+                       q->cmask, q->bloom, q->bwmask, D.dim_join, n, dhist);
         /* Motion-2 count exchange: same single-sync shape */
         tc0 = now_ms();
         RCCL_CHK(ctx, ncclAllGather(dhist, dcnts_all, n, ncclUint64, ctx->comm, s));
@@ -5887,32 +6155,14 @@ extern "C" gx_status gx_q3_run(gx_q3 *q)
                                     hipMemcpyDeviceToHost, s));
         HIP_CHK(ctx, hipStreamSynchronize(s));
         t_counts += now_ms() - tc0;
-        std::vector<unsigned long long> h2(n);
-        for (int i = 0; i < n; i++) h2[i] = cnts_all[(int64_t) ctx->seg * n + i];
-        std::vector<unsigned long long> off2(n + 1, 0);
-        for (int i = 0; i < n; i++) off2[i + 1] = off2[i] + h2[i];
-        if (grow(q->m_send2, q->m_send2_cap, off2[n]) != GX_OK) return GX_ERR_OOM;
+        const gx_mlayout L2 = m_exchange_layout(cnts_all.data(), n, ctx->seg);
+        const auto &h2 = L2.scnt, &off2 = L2.soff, &rcv2 = L2.rcnt, &roff2 = L2.roff;
+        if (grow(q->m_send2, q->m_send2_cap, L2.send_n) != GX_OK) return GX_ERR_OOM;
         gx_qual_row *send2 = q->m_send2;
         HIP_CHK(ctx, hipMemcpyAsync(dcur, off2.data(), n * 8, hipMemcpyHostToDevice, s));
-        auto launch_qemit = [&](auto *cs, auto anti) {
-            hipLaunchKernelGGL((k_qual_emit<std::decay_t<decltype(*cs)>,
-                                            decltype(anti)::value>),
-                               dim3(GRID), dim3(TPB), 0, s,
-                               recv1, (int64_t) recv1_n, cs,
-                               q->cmask, q->bloom, q->bwmask, n, dcur, send2);
-        };
-        if (q->cset_width == 4 && anti_join)
-            launch_qemit((const unsigned int *) q->cset, std::true_type{});
-        else if (q->cset_width == 4)
-            launch_qemit((const unsigned int *) q->cset, std::false_type{});
-        else if (anti_join)
-            launch_qemit((const unsigned long long *) q->cset, std::true_type{});
-        else
-            launch_qemit((const unsigned long long *) q->cset, std::false_type{});
-        std::vector<unsigned long long> rcv2(n), roff2(n + 1, 0);
-        for (int r = 0; r < n; r++) rcv2[r] = cnts_all[(int64_t) r * n + ctx->seg];
-        for (int r = 0; r < n; r++) roff2[r + 1] = roff2[r] + rcv2[r];
-        unsigned long long recv2_n = roff2[n];
+        m2_launch_emit(s, recv1, (int64_t) recv1_n, q->cset, q->cset_width,
+                       q->cmask, q->bloom, q->bwmask, D.dim_join, n, dcur, send2);
+        unsigned long long recv2_n = L2.recv_n;
         if (grow(q->m_recv2, q->m_recv2_cap, recv2_n) != GX_OK) return GX_ERR_OOM;
         gx_qual_row *recv2 = q->m_recv2;
         HIP_CHK(ctx, hipEventRecord(pev2, s));
@@ -5954,10 +6204,11 @@ extern "C" gx_status gx_q3_run(gx_q3 *q)
                          "sentinel (gpuexec.h gx_q3_prepare_desc)%s", "");
             return GX_ERR_INVALID;
         }
-        int want_kw = (kmax < (1ULL << 32)) ? 4 : 8;
         /* same tuned fill factor as the local path (tf=300) */
-        int mtf = env_int("GX_TABLE_FACTOR_PCT", 300);
-        uint64_t tslots = (uint64_t) pow2_at_least(qual * mtf / 100 + 1);
+        const gx_tbl_layout TL = m3_table_layout(
+            qual, kmin, kmax, ctx->nsegs, env_int("GX_TABLE_FACTOR_PCT", 300));
+        int want_kw = TL.key_width;
+        uint64_t tslots = TL.slots;
         /* motion path sizes from the exchanged counts each run; qual can
          * grow within the same pow2 table size, so rescap is checked too */
         if (q->tkey == nullptr || tslots > q->tmask + 1 || want_kw != q->key_width ||
@@ -5988,25 +6239,12 @@ extern "C" gx_status gx_q3_run(gx_q3 *q)
             HIP_CHK(ctx, hipMemsetAsync(q->urev, 0, (q->umask + 1) * 8, s));
             HIP_CHK(ctx, hipMemsetAsync(q->ucnt_u, 0, (q->umask + 1) * 8, s));
         }
-        q->smap.mask = q->tmask;
-        q->smap.kmin = (int64_t) kmin;
-        q->smap.scale = -1.0;
-        if (qual > 0 && kmax >= kmin)
-        {
-            double range = (double) (kmax - kmin) + 1.0;
-            if ((double) qual >= range / ((double) ctx->nsegs * 64.0))
-                q->smap.scale = (double) (q->tmask + 1) / range;
-        }
-        if (q->key_width == 4)
-            hipLaunchKernelGGL(k_build_from_rows<unsigned int>, dim3(GRID), dim3(TPB), 0, s,
-                               recv2, qual, (const unsigned long long *) nullptr,
-                               (unsigned int *) q->tkey,
-                               q->tattr, q->tagg, q->smap);
-        else
-            hipLaunchKernelGGL(k_build_from_rows<unsigned long long>, dim3(GRID), dim3(TPB), 0, s,
-                               recv2, qual, (const unsigned long long *) nullptr,
-                               (unsigned long long *) q->tkey,
-                               q->tattr, q->tagg, q->smap);
+        /* a reused cached table may be larger than this run's layout */
+        q->smap = (q->tmask + 1 == TL.slots)
+                      ? TL.smap
+                      : m3_slotmap(qual, kmin, kmax, ctx->nsegs, q->tmask + 1);
+        m3_launch_build(s, recv2, qual, nullptr, q->key_width, q->tkey,
+                        q->tattr, q->tagg, q->smap);
         HIP_CHK(ctx, hipEventRecord(mev1, s));
         HIP_CHK(ctx, hipStreamSynchronize(s));
         float mms = 0, p01 = 0, p23 = 0;
@@ -6090,91 +6328,12 @@ extern "C" gx_status gx_q3_run(gx_q3 *q)
     }
     else
     {
-        const char *pv = getenv("GX_PROBE_VARIANT");
-        int variant = pv ? atoi(pv) : 0;
-        bool outer = D.fact_join == 1;
-        if (variant != 0 && (lvm_eff || outer))
-        {
-            set_err(ctx, "visimap/extra quals/outer require the default probe variant%s", "");
-            return GX_ERR_INVALID;
-        }
-        const char *pg = getenv("GX_PROBE_GRID");
-        int pgrid = pg ? atoi(pg) : GRID;
-        const char *pt = getenv("GX_PROBE_TPB");
-        int ptpb = pt ? atoi(pt) : TPB;
-        const uint8_t *lvm = lvm_eff;
-        auto launch = [&](auto kern, auto *keys) {
-            hipLaunchKernelGGL(kern, dim3(pgrid), dim3(ptpb), 0, s,
-                               lk.dstream, lk.m, lp.dstream, lp.m, ld.dstream, ld.m,
-                               ls.dstream, ls.m, lvm, D.fact_filter.op,
-                               (int32_t) D.fact_filter.literal, keys,
-                               q->tagg, q->smap, dhits,
-                               q->ukey, q->urev, q->ucnt_u, q->umask);
-        };
-        if (q->key_width == 4)
-        {
-            auto *keys = (const unsigned int *) q->tkey;
-            switch (variant)
-            {
-                default:
-                case 0:
-                    if (outer && lvm)
-                        launch((k_li_probe_agg_t<1, unsigned int, true, true>), keys);
-                    else if (outer)
-                        launch((k_li_probe_agg_t<1, unsigned int, false, true>), keys);
-                    else if (lvm)
-                        launch((k_li_probe_agg_t<1, unsigned int, true>), keys);
-                    else
-                        launch(k_li_probe_agg_t<1, unsigned int>, keys);
-                    break;
-                case 2: launch(k_li_probe_agg_t<4, unsigned int>, keys); break;
-                case 4: launch(k_li_probe_agg_t<2, unsigned int>, keys); break;
-                case 5: launch(k_li_probe_agg_t<8, unsigned int>, keys); break;
-                case 6: launch(k_li_probe_agg_t<-1, unsigned int>, keys); break;
-                case 7: launch(k_li_probe_agg_t<-4, unsigned int>, keys); break;
-                case 8: launch(k_li_probe_agg_t<-2, unsigned int>, keys); break;
-                case 9: launch(k_li_probe_agg_t<-5, unsigned int>, keys); break;
-                case 10: launch(k_li_probe_agg_t<-6, unsigned int>, keys); break;
-                case 11: launch(k_li_probe_agg_t<-9, unsigned int>, keys); break;
-                case 12: launch(k_li_probe_agg_t<-10, unsigned int>, keys); break;
-                case 13: launch(k_li_probe_agg_t<-11, unsigned int>, keys); break;
-                case 14: launch(k_li_probe_agg_t<-12, unsigned int>, keys); break;
-                case 15: launch(k_li_probe_agg_t<-13, unsigned int>, keys); break;
-                case 16: launch(k_li_probe_agg_t<-14, unsigned int>, keys); break;
-            }
-        }
-        else
-        {
-            auto *keys = (const unsigned long long *) q->tkey;
-            switch (variant)
-            {
-                default:
-                case 0:
-                    if (outer && lvm)
-                        launch((k_li_probe_agg_t<1, unsigned long long, true, true>), keys);
-                    else if (outer)
-                        launch((k_li_probe_agg_t<1, unsigned long long, false, true>), keys);
-                    else if (lvm)
-                        launch((k_li_probe_agg_t<1, unsigned long long, true>), keys);
-                    else
-                        launch(k_li_probe_agg_t<1, unsigned long long>, keys);
-                    break;
-                case 2: launch(k_li_probe_agg_t<4, unsigned long long>, keys); break;
-                case 4: launch(k_li_probe_agg_t<2, unsigned long long>, keys); break;
-                case 5: launch(k_li_probe_agg_t<8, unsigned long long>, keys); break;
-                case 6: launch(k_li_probe_agg_t<-1, unsigned long long>, keys); break;
-                case 7: launch(k_li_probe_agg_t<-4, unsigned long long>, keys); break;
-                case 8: launch(k_li_probe_agg_t<-2, unsigned long long>, keys); break;
-                case 9: launch(k_li_probe_agg_t<-5, unsigned long long>, keys); break;
-                case 10: launch(k_li_probe_agg_t<-6, unsigned long long>, keys); break;
-                case 11: launch(k_li_probe_agg_t<-9, unsigned long long>, keys); break;
-                case 12: launch(k_li_probe_agg_t<-10, unsigned long long>, keys); break;
-                case 13: launch(k_li_probe_agg_t<-11, unsigned long long>, keys); break;
-                case 14: launch(k_li_probe_agg_t<-12, unsigned long long>, keys); break;
-                case 15: launch(k_li_probe_agg_t<-13, unsigned long long>, keys); break;
-                case 16: launch(k_li_probe_agg_t<-14, unsigned long long>, keys); break;
-            }
-        }
+        gx_status pst = q3_launch_probe(
+            ctx, s, lk, lp, ld, ls, lvm_eff, D.fact_filter.op,
+            (int32_t) D.fact_filter.literal, q->key_width, q->tkey, q->tagg,
+            q->smap, dhits, D.fact_join == 1, q->ukey, q->urev, q->ucnt_u,
+            q->umask);
+        if (pst != GX_OK) return pst;
     }
     HIP_CHK(ctx, hipEventRecord(ev[3], s));
 
@@ -6184,22 +6343,13 @@ extern "C" gx_status gx_q3_run(gx_q3 *q)
         HIP_CHK(ctx, hipMemsetAsync(q->r_flags, 0, q->rescap, s));
     /* one block per fixed tile of the table; k_extract_u keeps its own grid */
     const int egrid = 32768;
-    uint64_t etiles = (q->tmask + 1 + GX_EXTRACT_TILE - 1) / GX_EXTRACT_TILE;
-    if (etiles > 0x7FFFFFFFULL)
     {
-        set_err(ctx, "join/agg table too large for the extract grid%s", "");
-        return GX_ERR_INVALID;
+        gx_status est = q3_launch_extract(ctx, s, q->key_width, q->tkey, q->tattr,
+                                          q->tagg, q->tmask + 1, q->numeric,
+                                          q->r_okey, q->r_odate, q->r_oprio,
+                                          q->r_rev, q->r_cnt, dcount);
+        if (est != GX_OK) return est;
     }
-    if (q->key_width == 4)
-        hipLaunchKernelGGL(k_extract<unsigned int>, dim3((unsigned) etiles), dim3(TPB), 0, s,
-                           (const unsigned int *) q->tkey, q->tattr, q->tagg,
-                           q->tmask + 1, q->numeric,
-                           q->r_okey, q->r_odate, q->r_oprio, q->r_rev, q->r_cnt, dcount);
-    else
-        hipLaunchKernelGGL(k_extract<unsigned long long>, dim3((unsigned) etiles), dim3(TPB), 0, s,
-                           (const unsigned long long *) q->tkey, q->tattr, q->tagg,
-                           q->tmask + 1, q->numeric,
-                           q->r_okey, q->r_odate, q->r_oprio, q->r_rev, q->r_cnt, dcount);
     if (q->desc.fact_join == 1)
         hipLaunchKernelGGL(k_extract_u, dim3(egrid), dim3(TPB), 0, s,
                            q->ukey, q->urev, q->ucnt_u, q->umask + 1,
@@ -6390,7 +6540,7 @@ extern "C" void gx_free(void *p) { free(p); }
 /* ABI self-description: struct sizes for cross-checking foreign-language
  * mirrors (ctypes tests; the PG extension's abi-check compiles against the
  * real header instead).  kind: 0 stats, 1 group, 2 kv_group, 3 desc,
- * 4 coldesc, 5 filter, 6 gb_stats. */
+ * 4 coldesc, 5 filter, 6 gb_stats, 7 test_tbl_layout. */
 extern "C" int64_t gx_abi_sizeof(int kind)
 {
     switch (kind)
@@ -6402,52 +6552,101 @@ extern "C" int64_t gx_abi_sizeof(int kind)
         case 4: return (int64_t) sizeof(gx_coldesc);
         case 5: return (int64_t) sizeof(gx_filter);
         case 6: return (int64_t) sizeof(gx_gb_stats);
+        case 7: return (int64_t) sizeof(gx_test_tbl_layout);
         default: return -1;
     }
 }
 
-/* Test ABI: run the Motion-1 partition kernels (filter + route + emit) on a
- * bound/generated orders table for a given nsegs, returning the packed rows
- * and per-destination counts to the host.  Lets the Motion path's kernels be
- * parity-tested on ONE GPU (the RCCL exchange itself is a thin, separately
- * covered layer).  Mirrors doSendTuple routing (nodeMotion.c:1181). */
-extern "C" gx_status gx_test_motion1(gx_ctx *ctx, gx_table *orders,
-                                     int32_t cutoff, int nsegs,
-                                     int64_t *out_counts /* nsegs */,
-                                     gx_ord_row *out_rows /* cap */,
-                                     int64_t cap, int64_t *out_total)
+/* ---- test-only entry points of the Motion stages ----
+ * Each one drives a stage of the nsegs>1 branch of gx_q3_run through the
+ * shared seams above (same launches, dispatch and layout rules) for ANY
+ * nsegs on one GPU; the exchange between stages is done by the caller on
+ * the host with the counts returned here.  The RCCL calls themselves, the
+ * cross-rank agreement on the bloom size and on dim_state, and multi-GPU
+ * timing stay outside their reach. */
+
+static bool test_is_pow2(uint64_t v) { return v && !(v & (v - 1)); }
+
+static bool test_cols_are(const gx_table *t, std::initializer_list<int> widths)
 {
-    if (!ctx || !orders || orders->cols.size() != 4) return GX_ERR_INVALID;
+    if (!t || t->cols.size() != widths.size()) return false;
+    size_t i = 0;
+    for (int w : widths)
+    {
+        if (t->cols[i].format != 0 || t->cols[i].m.width != w) return false;
+        i++;
+    }
+    return true;
+}
+
+/* Motion 1 for one rank: orders cols [okey i64, ocust i64, odate i32,
+ * oprio i32]; host_bloom_all (optional) holds nsegs * bwords words. */
+static gx_status test_m1_impl(gx_ctx *ctx, gx_table *orders, gx_filter f,
+                              int nsegs, int dim_join,
+                              const uint64_t *host_bloom_all, uint64_t bwords,
+                              int64_t *out_counts, gx_ord_row *out_rows,
+                              int64_t cap, int64_t *out_total)
+{
+    if (!ctx || !out_counts || !out_total || nsegs < 1 || cap < 0 ||
+        (cap > 0 && !out_rows) || !test_cols_are(orders, {8, 8, 4, 4}))
+        return GX_ERR_INVALID;
+    if (f.col < 2 || f.col > 3)
+    {
+        set_err(ctx, "test_m1: the mid filter reads an i32 column (2 or 3)%s", "");
+        return GX_ERR_INVALID;
+    }
+    if (!gx_fold_filter(4, &f.op, &f.literal))
+    {
+        set_err(ctx, "test_m1: filter op must be in 0..5%s", "");
+        return GX_ERR_INVALID;
+    }
+    if (host_bloom_all && (!test_is_pow2(bwords) || bwords < 4096))
+    {
+        set_err(ctx, "test_m1: bwords must be a power of two >= 4096%s", "");
+        return GX_ERR_INVALID;
+    }
     hipStream_t s = ctx->stream;
+    /* as in gx_q3_run, the filter column is also the carried first attribute */
     const gx_col &ok = orders->cols[0], &oc = orders->cols[1],
-                 &od = orders->cols[2], &op = orders->cols[3];
-    devbuf dhist_b, dcur_b, dsend_b;
+                 &od = orders->cols[f.col], &op = orders->cols[3];
+    devbuf dhist_b, dcur_b, dsend_b, dbloom_b;
+    const unsigned long long *bloom_all = nullptr;
+    uint64_t bwmask = 0;
+    if (host_bloom_all)
+    {
+        HIP_CHK(ctx, dbloom_b.alloc((uint64_t) nsegs * bwords * 8));
+        HIP_CHK(ctx, hipMemcpyAsync(dbloom_b.p, host_bloom_all,
+                                    (uint64_t) nsegs * bwords * 8,
+                                    hipMemcpyHostToDevice, s));
+        bloom_all = dbloom_b.as<unsigned long long>();
+        bwmask = bwords - 1;
+    }
     HIP_CHK(ctx, dhist_b.alloc(nsegs * 8));
     HIP_CHK(ctx, dcur_b.alloc(nsegs * 8));
     unsigned long long *dhist = dhist_b.as<unsigned long long>();
     unsigned long long *dcur = dcur_b.as<unsigned long long>();
     HIP_CHK(ctx, hipMemsetAsync(dhist, 0, nsegs * 8, s));
-    hipLaunchKernelGGL(k_ord_m1_hist, dim3(GRID), dim3(TPB), 0, s,
-                       od.dstream, od.m, oc.dstream, oc.m,
-                       (const uint8_t *) nullptr, 0, cutoff, nsegs,
-                       (const unsigned long long *) nullptr, 0, dhist);
+    m1_launch_hist(s, od, oc, orders->dvmap, f.op, (int32_t) f.literal, nsegs,
+                   dim_join, bloom_all, bwmask, dhist);
     std::vector<unsigned long long> h(nsegs);
     HIP_CHK(ctx, hipMemcpyAsync(h.data(), dhist, nsegs * 8, hipMemcpyDeviceToHost, s));
     HIP_CHK(ctx, hipStreamSynchronize(s));
     std::vector<unsigned long long> off(nsegs + 1, 0);
     for (int i = 0; i < nsegs; i++) off[i + 1] = off[i] + h[i];
     int64_t total = (int64_t) off[nsegs];
-    if (total > cap) return GX_ERR_INVALID;
+    if (total > cap)
+    {
+        set_err(ctx, "test_m1: output capacity too small%s", "");
+        return GX_ERR_INVALID;
+    }
     HIP_CHK(ctx, dsend_b.alloc(std::max<int64_t>(total, 1) * sizeof(gx_ord_row)));
     gx_ord_row *dsend = dsend_b.as<gx_ord_row>();
     HIP_CHK(ctx, hipMemcpyAsync(dcur, off.data(), nsegs * 8, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_ord_m1_emit, dim3(GRID), dim3(TPB), 0, s,
-                       ok.dstream, ok.m, oc.dstream, oc.m, od.dstream, od.m,
-                       op.dstream, op.m, (const uint8_t *) nullptr,
-                       0, cutoff, nsegs,
-                       (const unsigned long long *) nullptr, 0, dcur, dsend);
-    HIP_CHK(ctx, hipMemcpyAsync(out_rows, dsend, total * sizeof(gx_ord_row),
-                                hipMemcpyDeviceToHost, s));
+    m1_launch_emit(s, ok, oc, od, op, orders->dvmap, f.op, (int32_t) f.literal,
+                   nsegs, dim_join, bloom_all, bwmask, dcur, dsend);
+    if (total)
+        HIP_CHK(ctx, hipMemcpyAsync(out_rows, dsend, total * sizeof(gx_ord_row),
+                                    hipMemcpyDeviceToHost, s));
     HIP_CHK(ctx, hipStreamSynchronize(s));
     HIP_CHK(ctx, hipGetLastError());
     for (int i = 0; i < nsegs; i++) out_counts[i] = (int64_t) h[i];
@@ -6455,97 +6654,187 @@ extern "C" gx_status gx_test_motion1(gx_ctx *ctx, gx_table *orders,
     return GX_OK;
 }
 
-/* Motion stage-2 kernels on one GPU: build THIS segment's customer
- * set+bloom from `customer`, probe the received Motion-1 rows, and emit
- * qualifying rows grouped by route(o_orderkey).  With gx_test_motion1 and
- * gx_test_q3_from_qual this covers every kernel of the nsegs>1 path
- * without an exchange (the RCCL layer itself is thin and symmetric). */
-static_assert(sizeof(gx_qual_row_abi) == sizeof(gx_qual_row), "qual row abi");
-extern "C" gx_status gx_test_qual(gx_ctx *ctx, gx_table *customer,
-                                  const gx_ord_row *host_rows, int64_t n,
-                                  int nsegs, int64_t *out_counts,
-                                  gx_qual_row_abi *out_rows, int64_t cap,
-                                  int64_t *out_total)
+/* one rank's dim membership as the Motion path holds it: hash set + bloom,
+ * sized as q3_size_and_alloc sizes them.  bwords == 0 takes this rank's own
+ * bloom size; a caller-chosen one stands in for the max-over-ranks
+ * agreement. */
+struct test_dimset {
+    devbuf set, bloom;
+    uint64_t cmask = 0, bwmask = 0;
+    int width = 8;
+    int64_t nsel = 0;
+};
+
+static gx_status test_build_dim(gx_ctx *ctx, gx_table *customer, int32_t op,
+                                int64_t literal, uint64_t bwords,
+                                test_dimset &ds)
 {
-    if (!ctx || !customer || customer->cols.size() != 2) return GX_ERR_INVALID;
+    if (!ctx || !test_cols_are(customer, {8, 1})) return GX_ERR_INVALID;
+    if (!gx_fold_filter(1, &op, &literal))
+    {
+        set_err(ctx, "test_dim: filter op must be in 0..5%s", "");
+        return GX_ERR_INVALID;
+    }
+    if (bwords && (!test_is_pow2(bwords) || bwords < 4096))
+    {
+        set_err(ctx, "test_dim: bwords must be a power of two >= 4096%s", "");
+        return GX_ERR_INVALID;
+    }
     hipStream_t s = ctx->stream;
     const gx_col &ck = customer->cols[0], &cm = customer->cols[1];
-    devbuf cnt_b, set_b, bloom_b, rows_b, hist_b, cur_b, send_b;
+    const uint8_t *cvm = customer->dvmap;
+    devbuf cnt_b;
     HIP_CHK(ctx, cnt_b.alloc(24));
-    HIP_CHK(ctx, hipMemsetAsync(cnt_b.p, 0, 16, s));
-    HIP_CHK(ctx, hipMemsetAsync((char *) cnt_b.p + 16, 0xFF, 8, s));
+    unsigned long long *dc = cnt_b.as<unsigned long long>();
+    HIP_CHK(ctx, hipMemsetAsync(dc, 0, 16, s));
+    HIP_CHK(ctx, hipMemsetAsync(dc + 2, 0xFF, 8, s));
     hipLaunchKernelGGL(k_cust_count, dim3(GRID), dim3(TPB), 0, s,
-                       ck.dstream, ck.m, cm.dstream, cm.m,
-                       (const uint8_t *) nullptr, 2, (int8_t) 0,
-                       cnt_b.as<unsigned long long>(),
-                       cnt_b.as<unsigned long long>() + 1,
-                       cnt_b.as<unsigned long long>() + 2);
-    unsigned long long nb[2];
-    HIP_CHK(ctx, hipMemcpyAsync(nb, cnt_b.p, 16, hipMemcpyDeviceToHost, s));
+                       ck.dstream, ck.m, cm.dstream, cm.m, cvm, op,
+                       (int8_t) literal, dc, dc + 1, dc + 2);
+    unsigned long long st[3];
+    HIP_CHK(ctx, hipMemcpyAsync(st, dc, 24, hipMemcpyDeviceToHost, s));
     HIP_CHK(ctx, hipStreamSynchronize(s));
-    uint64_t cslots = (uint64_t) pow2_at_least((int64_t) nb[0] * 2);
-    uint64_t bwords = (uint64_t) pow2_at_least(
-        std::max<int64_t>((int64_t) nb[0] * 8 / 64, 4096));
-    HIP_CHK(ctx, set_b.alloc(cslots * 8));
-    HIP_CHK(ctx, bloom_b.alloc(bwords * 8));
-    HIP_CHK(ctx, hipMemsetAsync(set_b.p, 0, cslots * 8, s));
-    HIP_CHK(ctx, hipMemsetAsync(bloom_b.p, 0, bwords * 8, s));
-    hipLaunchKernelGGL(k_cust_build<unsigned long long>, dim3(GRID), dim3(TPB), 0, s,
-                       ck.dstream, ck.m, cm.dstream, cm.m,
-                       (const uint8_t *) nullptr, 2, (int8_t) 0,
-                       set_b.as<unsigned long long>(), cslots - 1,
-                       bloom_b.as<unsigned long long>(), bwords - 1,
-                       (unsigned long long *) nullptr, (uint64_t) 0, (uint64_t) 0);
+    unsigned long long n_building = st[0], cmax = st[1], cmin = st[2];
+    if (n_building > 0 && cmin == 0)
+    {
+        set_err(ctx, "dim join key 0 found: 0 is reserved as the empty-slot "
+                     "sentinel (gpuexec.h gx_q3_prepare_desc)%s", "");
+        return GX_ERR_INVALID;
+    }
+    ds.nsel = (int64_t) n_building;
+    ds.width = (cmax < (1ULL << 32)) ? 4 : 8;
+    uint64_t cslots = (uint64_t) pow2_at_least((int64_t) n_building * 2);
+    if (!bwords)
+        bwords = (uint64_t) pow2_at_least(
+            std::max<int64_t>((int64_t) n_building * 8 / 64, 4096));
+    ds.cmask = cslots - 1;
+    ds.bwmask = bwords - 1;
+    HIP_CHK(ctx, ds.set.alloc(cslots * ds.width));
+    HIP_CHK(ctx, ds.bloom.alloc(bwords * 8));
+    HIP_CHK(ctx, hipMemsetAsync(ds.set.p, 0, cslots * ds.width, s));
+    HIP_CHK(ctx, hipMemsetAsync(ds.bloom.p, 0, bwords * 8, s));
+    auto go = [&](auto *cs) {
+        hipLaunchKernelGGL((k_cust_build<std::decay_t<decltype(*cs)>, false>),
+                           dim3(GRID), dim3(TPB), 0, s,
+                           ck.dstream, ck.m, cm.dstream, cm.m, cvm, op,
+                           (int8_t) literal, cs, ds.cmask,
+                           ds.bloom.as<unsigned long long>(), ds.bwmask,
+                           (unsigned long long *) nullptr, (uint64_t) 0,
+                           (uint64_t) 0);
+    };
+    if (ds.width == 4) go(ds.set.as<unsigned int>());
+    else go(ds.set.as<unsigned long long>());
+    return GX_OK;
+}
+
+extern "C" gx_status gx_test_dim(gx_ctx *ctx, gx_table *customer, int32_t op,
+                                 int64_t literal, uint64_t bwords,
+                                 uint64_t *out_bloom, int64_t *out_nsel,
+                                 int32_t *out_set_width)
+{
+    if (!ctx || !out_bloom || !bwords) return GX_ERR_INVALID;
+    test_dimset ds;
+    gx_status st = test_build_dim(ctx, customer, op, literal, bwords, ds);
+    if (st != GX_OK) return st;
+    HIP_CHK(ctx, hipMemcpyAsync(out_bloom, ds.bloom.p, bwords * 8,
+                                hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_CHK(ctx, hipGetLastError());
+    if (out_nsel) *out_nsel = ds.nsel;
+    if (out_set_width) *out_set_width = ds.width;
+    return GX_OK;
+}
+
+/* Motion 2 for one rank: its dim set against the rows it received */
+static_assert(sizeof(gx_qual_row_abi) == sizeof(gx_qual_row), "qual row abi");
+static gx_status test_m2_impl(gx_ctx *ctx, gx_table *customer, int32_t op,
+                              int64_t literal, uint64_t bwords,
+                              const gx_ord_row *host_rows, int64_t n,
+                              int dim_join, int nsegs, int64_t *out_counts,
+                              gx_qual_row_abi *out_rows, int64_t cap,
+                              int64_t *out_total, int32_t *out_set_width)
+{
+    if (!ctx || !out_counts || !out_total || nsegs < 1 || n < 0 || cap < 0 ||
+        (n > 0 && !host_rows) || (cap > 0 && !out_rows))
+        return GX_ERR_INVALID;
+    hipStream_t s = ctx->stream;
+    test_dimset ds;
+    gx_status st = test_build_dim(ctx, customer, op, literal, bwords, ds);
+    if (st != GX_OK) return st;
+    devbuf rows_b, hist_b, cur_b, send_b;
     HIP_CHK(ctx, rows_b.alloc(std::max<int64_t>(n, 1) * sizeof(gx_ord_row)));
-    HIP_CHK(ctx, hipMemcpyAsync(rows_b.p, host_rows, n * sizeof(gx_ord_row),
-                                hipMemcpyHostToDevice, s));
+    if (n)
+        HIP_CHK(ctx, hipMemcpyAsync(rows_b.p, host_rows, n * sizeof(gx_ord_row),
+                                    hipMemcpyHostToDevice, s));
     HIP_CHK(ctx, hist_b.alloc(nsegs * 8));
     HIP_CHK(ctx, cur_b.alloc(nsegs * 8));
     HIP_CHK(ctx, hipMemsetAsync(hist_b.p, 0, nsegs * 8, s));
-    hipLaunchKernelGGL(k_qual_hist<unsigned long long>, dim3(GRID), dim3(TPB), 0, s,
-                       rows_b.as<gx_ord_row>(), n,
-                       set_b.as<unsigned long long>(), cslots - 1,
-                       bloom_b.as<unsigned long long>(), bwords - 1, nsegs,
-                       hist_b.as<unsigned long long>());
+    m2_launch_hist(s, rows_b.as<gx_ord_row>(), n, ds.set.p, ds.width, ds.cmask,
+                   ds.bloom.as<unsigned long long>(), ds.bwmask, dim_join,
+                   nsegs, hist_b.as<unsigned long long>());
     std::vector<unsigned long long> h(nsegs);
     HIP_CHK(ctx, hipMemcpyAsync(h.data(), hist_b.p, nsegs * 8, hipMemcpyDeviceToHost, s));
     HIP_CHK(ctx, hipStreamSynchronize(s));
     std::vector<unsigned long long> off(nsegs + 1, 0);
     for (int i = 0; i < nsegs; i++) off[i + 1] = off[i] + h[i];
     int64_t total = (int64_t) off[nsegs];
-    if (total > cap) return GX_ERR_INVALID;
+    if (total > cap)
+    {
+        set_err(ctx, "test_m2: output capacity too small%s", "");
+        return GX_ERR_INVALID;
+    }
     HIP_CHK(ctx, send_b.alloc(std::max<int64_t>(total, 1) * sizeof(gx_qual_row)));
     HIP_CHK(ctx, hipMemcpyAsync(cur_b.p, off.data(), nsegs * 8, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_qual_emit<unsigned long long>, dim3(GRID), dim3(TPB), 0, s,
-                       rows_b.as<gx_ord_row>(), n,
-                       set_b.as<unsigned long long>(), cslots - 1,
-                       bloom_b.as<unsigned long long>(), bwords - 1, nsegs,
-                       cur_b.as<unsigned long long>(), send_b.as<gx_qual_row>());
-    HIP_CHK(ctx, hipMemcpyAsync(out_rows, send_b.p, total * sizeof(gx_qual_row),
-                                hipMemcpyDeviceToHost, s));
+    m2_launch_emit(s, rows_b.as<gx_ord_row>(), n, ds.set.p, ds.width, ds.cmask,
+                   ds.bloom.as<unsigned long long>(), ds.bwmask, dim_join,
+                   nsegs, cur_b.as<unsigned long long>(),
+                   send_b.as<gx_qual_row>());
+    if (total)
+        HIP_CHK(ctx, hipMemcpyAsync(out_rows, send_b.p, total * sizeof(gx_qual_row),
+                                    hipMemcpyDeviceToHost, s));
     HIP_CHK(ctx, hipStreamSynchronize(s));
     HIP_CHK(ctx, hipGetLastError());
     for (int i = 0; i < nsegs; i++) out_counts[i] = (int64_t) h[i];
     *out_total = total;
+    if (out_set_width) *out_set_width = ds.width;
     return GX_OK;
 }
 
-/* Motion stage-3 on one GPU: build the join/agg table from received
- * qualifying rows (k_rows_minmax + k_build_from_rows — the nsegs>1 build)
- * and run probe+agg+extract over `lineitem`, returning this segment's
- * groups sorted by key.  Caller frees *out with gx_free. */
-extern "C" gx_status gx_test_q3_from_qual(gx_ctx *ctx,
-                                          const gx_qual_row_abi *host_rows,
-                                          int64_t n, gx_table *lineitem,
-                                          int32_t cutoff, gx_q3_group **out,
-                                          int64_t *ngroups)
+static void test_fill_layout(gx_test_tbl_layout *o, const gx_tbl_layout &L,
+                             unsigned long long kmin, unsigned long long kmax)
 {
-    if (!ctx || !lineitem || lineitem->cols.size() != 4) return GX_ERR_INVALID;
+    o->key_width = L.key_width;
+    o->interpolated = L.smap.scale < 0.0 ? 0 : 1;
+    o->slots = L.slots;
+    o->kmin = L.smap.kmin;
+    o->scale = L.smap.scale;
+    o->slot_kmin = L.smap.slot0(kmin);
+    o->slot_kmax = L.smap.slot0(kmax);
+}
+
+/* Motion 3 for one rank: table from the received qualifying rows (layout,
+ * key width and build launch as gx_q3_run picks them, nsegs from ctx), then
+ * probe + aggregate its lineitem shard [lkey i64, price f64, disc f64,
+ * shipdate i32] through the production probe dispatch, visimap honoured. */
+static gx_status test_m3_impl(gx_ctx *ctx, const gx_qual_row_abi *host_rows,
+                              int64_t n, gx_table *lineitem, int32_t fop,
+                              int64_t flit, gx_q3_group **out,
+                              int64_t *ngroups, gx_test_tbl_layout *lay)
+{
+    if (!ctx || !out || !ngroups || n < 0 || (n > 0 && !host_rows) ||
+        !test_cols_are(lineitem, {8, 8, 8, 4}))
+        return GX_ERR_INVALID;
+    if (!gx_fold_filter(4, &fop, &flit))
+    {
+        set_err(ctx, "test_m3: filter op must be in 0..5%s", "");
+        return GX_ERR_INVALID;
+    }
     hipStream_t s = ctx->stream;
     devbuf rows_b, stat_b, key_b, attr_b, agg_b, cur_b, hit_b;
     HIP_CHK(ctx, rows_b.alloc(std::max<int64_t>(n, 1) * sizeof(gx_qual_row)));
-    HIP_CHK(ctx, hipMemcpyAsync(rows_b.p, host_rows, n * sizeof(gx_qual_row),
-                                hipMemcpyHostToDevice, s));
+    if (n)
+        HIP_CHK(ctx, hipMemcpyAsync(rows_b.p, host_rows, n * sizeof(gx_qual_row),
+                                    hipMemcpyHostToDevice, s));
     HIP_CHK(ctx, stat_b.alloc(16));
     HIP_CHK(ctx, hipMemsetAsync(stat_b.p, 0, 8, s));
     HIP_CHK(ctx, hipMemsetAsync((uint8_t *) stat_b.p + 8, 0xFF, 8, s));
@@ -6556,36 +6845,35 @@ extern "C" gx_status gx_test_q3_from_qual(gx_ctx *ctx,
     unsigned long long st2[2];
     HIP_CHK(ctx, hipMemcpyAsync(st2, stat_b.p, 16, hipMemcpyDeviceToHost, s));
     HIP_CHK(ctx, hipStreamSynchronize(s));
-    uint64_t tslots = (uint64_t) pow2_at_least(n * 2);
-    gx_slotmap smap;
-    smap.mask = tslots - 1;
-    smap.kmin = (int64_t) st2[1];
-    smap.scale = -1.0;
-    if (n > 0 && st2[0] >= st2[1])
+    unsigned long long kmax = st2[0], kmin = st2[1];
+    if (n > 0 && kmin == 0)
     {
-        double range = (double) (st2[0] - st2[1]) + 1.0;
-        if ((double) n >= range / (64.0 * ctx->nsegs))
-            smap.scale = (double) tslots / range;
+        set_err(ctx, "mid join key 0 received: 0 is the empty-slot "
+                     "sentinel (gpuexec.h gx_q3_prepare_desc)%s", "");
+        return GX_ERR_INVALID;
     }
-    HIP_CHK(ctx, key_b.alloc(tslots * 8));
+    const gx_tbl_layout TL = m3_table_layout(
+        n, kmin, kmax, ctx->nsegs, env_int("GX_TABLE_FACTOR_PCT", 300));
+    if (lay) test_fill_layout(lay, TL, kmin, kmax);
+    uint64_t tslots = TL.slots;
+    HIP_CHK(ctx, key_b.alloc(tslots * TL.key_width));
     HIP_CHK(ctx, attr_b.alloc(tslots * sizeof(gx_attrpair)));
     HIP_CHK(ctx, agg_b.alloc(tslots * sizeof(gx_aggslot)));
-    HIP_CHK(ctx, hipMemsetAsync(key_b.p, 0, tslots * 8, s));
-    hipLaunchKernelGGL(k_build_from_rows<unsigned long long>, dim3(GRID), dim3(TPB), 0, s,
-                       rows_b.as<gx_qual_row>(), n,
-                       (const unsigned long long *) nullptr,
-                       key_b.as<unsigned long long>(), attr_b.as<gx_attrpair>(),
-                       agg_b.as<gx_aggslot>(), smap);
+    HIP_CHK(ctx, hipMemsetAsync(key_b.p, 0, tslots * TL.key_width, s));
+    m3_launch_build(s, rows_b.as<gx_qual_row>(), n, nullptr, TL.key_width,
+                    key_b.p, attr_b.as<gx_attrpair>(), agg_b.as<gx_aggslot>(),
+                    TL.smap);
     const gx_col &lk = lineitem->cols[0], &lp = lineitem->cols[1],
                  &ld = lineitem->cols[2], &ls = lineitem->cols[3];
     HIP_CHK(ctx, hit_b.alloc(8));
     HIP_CHK(ctx, hipMemsetAsync(hit_b.p, 0, 8, s));
-    hipLaunchKernelGGL((k_li_probe_agg_t<1, unsigned long long>), dim3(GRID), dim3(TPB), 0, s,
-                       lk.dstream, lk.m, lp.dstream, lp.m, ld.dstream, ld.m,
-                       ls.dstream, ls.m, (const uint8_t *) nullptr, 1, cutoff,
-                       key_b.as<unsigned long long>(),
-                       agg_b.as<gx_aggslot>(),
-                       smap, hit_b.as<unsigned long long>());
+    {
+        gx_status pst = q3_launch_probe(
+            ctx, s, lk, lp, ld, ls, lineitem->dvmap, fop, (int32_t) flit,
+            TL.key_width, key_b.p, agg_b.as<gx_aggslot>(), TL.smap,
+            hit_b.as<unsigned long long>(), false, nullptr, nullptr, nullptr, 0);
+        if (pst != GX_OK) return pst;
+    }
     devbuf r_okey, r_odate, r_oprio, r_rev, r_cnt;
     int64_t cap = std::max<int64_t>(n, 1);
     HIP_CHK(ctx, r_okey.alloc(cap * 8));
@@ -6595,14 +6883,14 @@ extern "C" gx_status gx_test_q3_from_qual(gx_ctx *ctx,
     HIP_CHK(ctx, r_cnt.alloc(cap * 8));
     HIP_CHK(ctx, cur_b.alloc(8));
     HIP_CHK(ctx, hipMemsetAsync(cur_b.p, 0, 8, s));
-    hipLaunchKernelGGL(k_extract<unsigned long long>,
-                       dim3((unsigned) ((tslots + GX_EXTRACT_TILE - 1) / GX_EXTRACT_TILE)),
-                       dim3(TPB), 0, s,
-                       key_b.as<unsigned long long>(), attr_b.as<gx_attrpair>(),
-                       agg_b.as<gx_aggslot>(), tslots, 0,
-                       r_okey.as<int64_t>(), r_odate.as<int32_t>(),
-                       r_oprio.as<int32_t>(), r_rev.as<double>(),
-                       r_cnt.as<int64_t>(), cur_b.as<unsigned long long>());
+    {
+        gx_status est = q3_launch_extract(
+            ctx, s, TL.key_width, key_b.p, attr_b.as<gx_attrpair>(),
+            agg_b.as<gx_aggslot>(), tslots, 0, r_okey.as<int64_t>(),
+            r_odate.as<int32_t>(), r_oprio.as<int32_t>(), r_rev.as<double>(),
+            r_cnt.as<int64_t>(), cur_b.as<unsigned long long>());
+        if (est != GX_OK) return est;
+    }
     unsigned long long ng = 0;
     HIP_CHK(ctx, hipMemcpyAsync(&ng, cur_b.p, 8, hipMemcpyDeviceToHost, s));
     HIP_CHK(ctx, hipStreamSynchronize(s));
@@ -6622,7 +6910,9 @@ extern "C" gx_status gx_test_q3_from_qual(gx_ctx *ctx,
     std::vector<int64_t> idx(m);
     for (int64_t i = 0; i < m; i++) idx[i] = i;
     std::sort(idx.begin(), idx.end(), [&](int64_t a, int64_t b) { return okey[a] < okey[b]; });
-    gx_q3_group *g = (gx_q3_group *) malloc(sizeof(gx_q3_group) * std::max<int64_t>(m, 1));
+    /* zeroed: key_is_null / attrs_null / _pad are read by the callers */
+    gx_q3_group *g = (gx_q3_group *) calloc(std::max<int64_t>(m, 1), sizeof(gx_q3_group));
+    if (!g) return GX_ERR_OOM;
     for (int64_t i = 0; i < m; i++)
     {
         g[i].l_orderkey = okey[idx[i]];
@@ -6635,6 +6925,105 @@ extern "C" gx_status gx_test_q3_from_qual(gx_ctx *ctx,
     *out = g;
     *ngroups = m;
     return GX_OK;
+}
+
+extern "C" gx_status gx_test_m1(gx_ctx *ctx, gx_table *orders,
+                                const gx_filter *mid_filter, int nsegs,
+                                int dim_join, const uint64_t *bloom_all,
+                                uint64_t bwords, int64_t *out_counts,
+                                gx_ord_row *out_rows, int64_t cap,
+                                int64_t *out_total)
+{
+    if (!mid_filter) return GX_ERR_INVALID;
+    return test_m1_impl(ctx, orders, *mid_filter, nsegs, dim_join, bloom_all,
+                        bwords, out_counts, out_rows, cap, out_total);
+}
+
+extern "C" gx_status gx_test_m2(gx_ctx *ctx, gx_table *customer, int32_t op,
+                                int64_t literal, uint64_t bwords,
+                                const gx_ord_row *rows, int64_t n,
+                                int dim_join, int nsegs, int64_t *out_counts,
+                                gx_qual_row_abi *out_rows, int64_t cap,
+                                int64_t *out_total, int32_t *out_set_width)
+{
+    return test_m2_impl(ctx, customer, op, literal, bwords, rows, n, dim_join,
+                        nsegs, out_counts, out_rows, cap, out_total,
+                        out_set_width);
+}
+
+extern "C" gx_status gx_test_m3(gx_ctx *ctx, const gx_qual_row_abi *rows,
+                                int64_t n, gx_table *lineitem, int32_t op,
+                                int64_t literal, gx_q3_group **out,
+                                int64_t *ngroups, gx_test_tbl_layout *layout)
+{
+    return test_m3_impl(ctx, rows, n, lineitem, op, literal, out, ngroups, layout);
+}
+
+/* the three original entry points: the Q3 constants on the same stages.
+ * orders filter o_orderdate < cutoff, no prefilter */
+extern "C" gx_status gx_test_motion1(gx_ctx *ctx, gx_table *orders,
+                                     int32_t cutoff, int nsegs,
+                                     int64_t *out_counts /* nsegs */,
+                                     gx_ord_row *out_rows /* cap */,
+                                     int64_t cap, int64_t *out_total)
+{
+    gx_filter f = {2, 0, cutoff};
+    return test_m1_impl(ctx, orders, f, nsegs, 0, nullptr, 0, out_counts,
+                        out_rows, cap, out_total);
+}
+
+/* dim filter c_mktsegment == 0, semi join, this rank's own bloom size */
+extern "C" gx_status gx_test_qual(gx_ctx *ctx, gx_table *customer,
+                                  const gx_ord_row *host_rows, int64_t n,
+                                  int nsegs, int64_t *out_counts,
+                                  gx_qual_row_abi *out_rows, int64_t cap,
+                                  int64_t *out_total)
+{
+    return test_m2_impl(ctx, customer, 2, 0, 0, host_rows, n, 0, nsegs,
+                        out_counts, out_rows, cap, out_total, nullptr);
+}
+
+/* fact filter l_shipdate > cutoff.  Caller frees *out with gx_free. */
+extern "C" gx_status gx_test_q3_from_qual(gx_ctx *ctx,
+                                          const gx_qual_row_abi *host_rows,
+                                          int64_t n, gx_table *lineitem,
+                                          int32_t cutoff, gx_q3_group **out,
+                                          int64_t *ngroups)
+{
+    return test_m3_impl(ctx, host_rows, n, lineitem, 1, cutoff, out, ngroups,
+                        nullptr);
+}
+
+/* The two pure host helpers of the Motion path on caller-supplied inputs
+ * (callable without a GPU).  cnts_all (n×n, optional): this rank's send /
+ * receive counts (n each) and offsets (n + 1 each).  layout (optional): the
+ * table layout for qual keys in [kmin,kmax].  Returns 0, or 1 for bad
+ * arguments. */
+extern "C" int gx_selftest_motion_layout(const uint64_t *cnts_all, int n, int seg,
+                                         uint64_t *scnt, uint64_t *soff,
+                                         uint64_t *rcnt, uint64_t *roff,
+                                         int64_t qual, uint64_t kmin,
+                                         uint64_t kmax, int nsegs, int tf_pct,
+                                         gx_test_tbl_layout *layout)
+{
+    if (cnts_all)
+    {
+        if (n < 1 || seg < 0 || seg >= n || !scnt || !soff || !rcnt || !roff)
+            return 1;
+        static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "u64");
+        gx_mlayout L = m_exchange_layout((const unsigned long long *) cnts_all,
+                                         n, seg);
+        for (int i = 0; i < n; i++) { scnt[i] = L.scnt[i]; rcnt[i] = L.rcnt[i]; }
+        for (int i = 0; i <= n; i++) { soff[i] = L.soff[i]; roff[i] = L.roff[i]; }
+    }
+    if (layout)
+    {
+        if (qual < 0 || nsegs < 1 || tf_pct < 0) return 1;
+        test_fill_layout(layout,
+                         m3_table_layout(qual, kmin, kmax, nsegs, tf_pct),
+                         kmin, kmax);
+    }
+    return 0;
 }
 
 /* RCCL linkage self-check: init a 1-rank communicator and run one

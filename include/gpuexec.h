@@ -321,8 +321,8 @@ gx_status gx_q3_free(gx_q3 *q);
 void gx_free(void *p);
 
 /* ABI self-description for foreign mirrors (0 stats, 1 q3_group,
- * 2 kv_group, 3 q3_desc, 4 coldesc, 5 filter, 6 gb_stats); -1 for unknown
- * kinds */
+ * 2 kv_group, 3 q3_desc, 4 coldesc, 5 filter, 6 gb_stats,
+ * 7 test_tbl_layout); -1 for unknown kinds */
 int64_t gx_abi_sizeof(int kind);
 
 /* ---- standalone hash GROUP BY (nodeAgg.c:2288 hash strategy over one key;
@@ -391,6 +391,71 @@ gx_status gx_test_gb_partial(gx_ctx *ctx, const gx_table *t, int key_col, int va
 gx_status gx_test_gb_combine(gx_ctx *ctx, const gx_kv_group *rows, int64_t n,
                              gx_kv_group **out, int64_t *ngroups);
 int gx_selftest_addressing(void);
+
+/* ---- the Motion stages of the nsegs>1 Q3 path, one rank at a time.  These
+ * run the same launches, dispatch and layout rules as gx_q3_run for any
+ * nsegs on one GPU; the caller moves rows between "ranks" on the host with
+ * the per-destination counts returned.  Output rows are packed contiguously
+ * by destination in destination order (order within one unspecified);
+ * GX_ERR_INVALID if the total exceeds cap. ---- */
+
+/* Motion 1 over orders [okey i64, ocust i64, odate i32, oprio i32], visimap
+ * honoured.  mid_filter = <col 2 or 3, op, literal>, folded as
+ * gx_q3_prepare_desc folds it; as in gx_q3_run the filter column is also the
+ * one carried as odate.  bloom_all (optional, host) = nsegs * bwords words,
+ * rank r's dim bloom at r * bwords, bwords a power of two >= 4096; it is used
+ * for dim_join == 0 only (the destination prefilter is off for anti joins). */
+gx_status gx_test_m1(gx_ctx *ctx, gx_table *orders, const gx_filter *mid_filter,
+                     int nsegs, int dim_join, const uint64_t *bloom_all,
+                     uint64_t bwords, int64_t *out_counts /* nsegs */,
+                     gx_ord_row *out_rows, int64_t cap, int64_t *out_total);
+/* Dim side of one rank: customer [ckey i64, attr i8] filtered by <op,
+ * literal> on the i8 column (visimap honoured) into the hash set + bloom of
+ * the Motion path.  bwords (power of two >= 4096) stands in for the
+ * max-over-ranks agreement; out_bloom receives bwords words.  out_set_width:
+ * 4 when every selected key is < 2^32, else 8. */
+gx_status gx_test_dim(gx_ctx *ctx, gx_table *customer, int32_t op,
+                      int64_t literal, uint64_t bwords, uint64_t *out_bloom,
+                      int64_t *out_nsel, int32_t *out_set_width);
+/* Motion 2: rows received by this rank against its dim set (built as
+ * gx_test_dim builds it; bwords 0 = this rank's own size), semi (dim_join 0)
+ * or anti, qualifying rows routed by okey. */
+gx_status gx_test_m2(gx_ctx *ctx, gx_table *customer, int32_t op,
+                     int64_t literal, uint64_t bwords, const gx_ord_row *rows,
+                     int64_t n, int dim_join, int nsegs,
+                     int64_t *out_counts /* nsegs */, gx_qual_row_abi *out_rows,
+                     int64_t cap, int64_t *out_total, int32_t *out_set_width);
+/* Layout of the join/agg table built from received rows (what gx_q3_run
+ * derives before a cached-table reuse decision). */
+typedef struct gx_test_tbl_layout {
+    int32_t  key_width;        /* 4 when kmax < 2^32, else 8 */
+    int32_t  interpolated;     /* 1 = order-preserving slot map, 0 = hashed */
+    uint64_t slots;            /* power of two, > qual */
+    int64_t  kmin;
+    double   scale;            /* slots / range; < 0 when hashed */
+    uint64_t slot_kmin, slot_kmax;   /* first-probe slots of kmin and kmax */
+} gx_test_tbl_layout;
+/* Motion 3: table from received qualifying rows (nsegs of ctx enters the
+ * density rule), then probe + aggregate lineitem [lkey i64, price f64,
+ * disc f64, shipdate i32] filtered by <op, literal> on shipdate, visimap
+ * honoured.  Groups sorted by key; caller frees *out with gx_free.  layout
+ * may be NULL. */
+gx_status gx_test_m3(gx_ctx *ctx, const gx_qual_row_abi *rows, int64_t n,
+                     gx_table *lineitem, int32_t op, int64_t literal,
+                     gx_q3_group **out, int64_t *ngroups,
+                     gx_test_tbl_layout *layout);
+/* The two pure host helpers of the Motion path, no GPU needed.  cnts_all
+ * (optional) is the all-gathered n×n count matrix (row r = rank r's
+ * per-destination counts): rank seg's send/receive counts (n entries) and
+ * exclusive offsets (n + 1 entries, the last the total).  layout (optional):
+ * table layout for qual keys spanning [kmin, kmax] at nsegs with fill factor
+ * tf_pct.  Returns 0, or 1 for bad arguments. */
+int gx_selftest_motion_layout(const uint64_t *cnts_all, int n, int seg,
+                              uint64_t *scnt, uint64_t *soff,
+                              uint64_t *rcnt, uint64_t *roff,
+                              int64_t qual, uint64_t kmin, uint64_t kmax,
+                              int nsegs, int tf_pct,
+                              gx_test_tbl_layout *layout);
 
 #ifdef __cplusplus
 }
