@@ -268,6 +268,16 @@ def _load():
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
         ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
         ctypes.POINTER(_TblLayout)]
+    lib.gx_test_topn.argtypes = [ctypes.c_void_p] * 7 + [
+        ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+        ctypes.POINTER(ctypes.c_int64)]
+    lib.gx_selftest_topn_merge.restype = ctypes.c_int
+    lib.gx_selftest_topn_merge.argtypes = [ctypes.c_void_p] * 7 + [
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+        ctypes.POINTER(ctypes.c_int64)]
+    lib.gx_selftest_unmatched_bound.restype = ctypes.c_uint64
+    lib.gx_selftest_unmatched_bound.argtypes = [ctypes.c_int64, ctypes.c_uint64,
+                                                ctypes.c_uint64]
     return lib
 
 
@@ -313,6 +323,44 @@ def motion_table_layout(qual, kmin, kmax, nsegs, tf_pct=300):
     if rc != 0:
         raise ValueError(f"gx_selftest_motion_layout: bad arguments ({rc})")
     return _layout_dict(lay)
+
+
+def unmatched_bound(nrows, lmin, lmax):
+    """Sizing's bound on the LEFT-OUTER unmatched groups of a fact key column
+    of nrows rows whose keys span [lmin, lmax] as unsigned 64-bit words (host
+    only, no GPU)."""
+    return int(lib().gx_selftest_unmatched_bound(
+        int(nrows), int(lmin) & (2**64 - 1), int(lmax) & (2**64 - 1)))
+
+
+def _topn_soa(okey, odate, oprio, rev, cnt, flags, numeric):
+    okey = np.ascontiguousarray(okey, np.int64)
+    n = len(okey)
+    rev = np.ascontiguousarray(rev, np.int64 if numeric else np.float64)
+    arrs = [okey, np.ascontiguousarray(odate, np.int32),
+            np.ascontiguousarray(oprio, np.int32), rev,
+            np.ascontiguousarray(cnt, np.int64),
+            None if flags is None else np.ascontiguousarray(flags, np.uint8)]
+    assert all(a is None or len(a) == n for a in arrs)
+    return n, arrs
+
+
+def topn_merge(cidx, okey, odate, oprio, rev, cnt, flags, topn=10,
+               numeric=False):
+    """The host merge of the top-N stage over candidate arrays (host only, no
+    GPU): cidx < 0 marks an empty candidate; rev is int64 numerators when
+    numeric.  Returns the selected rows as a Q3_GROUP_DTYPE array."""
+    n, arrs = _topn_soa(okey, odate, oprio, rev, cnt, flags, numeric)
+    cidx = np.ascontiguousarray(cidx, np.int64)
+    assert len(cidx) == n and arrs[5] is not None
+    out = np.zeros(max(topn, 1), Q3_GROUP_DTYPE)
+    m = ctypes.c_int64()
+    rc = lib().gx_selftest_topn_merge(
+        cidx.ctypes.data, *[a.ctypes.data for a in arrs], n,
+        1 if numeric else 0, topn, out.ctypes.data, ctypes.byref(m))
+    if rc != 0:
+        raise ValueError(f"gx_selftest_topn_merge: bad arguments ({rc})")
+    return out[:m.value]
 
 
 class Context:
@@ -588,6 +636,22 @@ class Context:
                "attrs_null": g["attrs_null"].copy(),
                "_pad": g["_pad"].copy()}
         return res, _layout_dict(lay)
+
+    def test_topn(self, okey, odate, oprio, rev, cnt, flags=None, topn=10,
+                  numeric=False, out=None):
+        """The top-N stage of gx_q3_topn over host SoA arrays of groups (rev:
+        float64, or int64 numerators when numeric; flags optional).  Returns
+        the selected rows as a Q3_GROUP_DTYPE array; `out` (a Q3_GROUP_DTYPE
+        array of >= 10 rows) replaces the internal output buffer."""
+        n, arrs = _topn_soa(okey, odate, oprio, rev, cnt, flags, numeric)
+        if out is None:
+            out = np.zeros(10, Q3_GROUP_DTYPE)
+        assert out.dtype == Q3_GROUP_DTYPE and len(out) >= 10
+        m = ctypes.c_int64(-1)
+        self._chk(self._lib.gx_test_topn(
+            self._h, *[None if a is None else a.ctypes.data for a in arrs], n,
+            1 if numeric else 0, topn, out.ctypes.data, ctypes.byref(m)))
+        return out[:m.value]
 
     def q1(self, lineitem_q1, cutoff):
         """TPC-H Q1 core: returns dict of 6-group arrays + kernel ms."""

@@ -2229,12 +2229,14 @@ d_wave_claim(unsigned long long *ctr, bool mine, int lane,
 
 /* append LEFT-OUTER unmatched groups after the matched extract: same
  * cursor, NULL mid attrs (attrs_null), biased key 2^63 = the NULL-key
- * group (key_is_null).  flags bit0 = key_is_null, bit1 = attrs_null. */
+ * group (key_is_null).  flags bit0 = key_is_null, bit1 = attrs_null.
+ * Rows past cap (the result arrays' capacity) are counted but not written;
+ * the host turns cursor > cap into an error. */
 __global__ void k_extract_u(const unsigned long long *ukey, const double *urev,
                             const unsigned long long *ucnt, uint64_t uslots,
                             int64_t *okey, int32_t *odate, int32_t *oprio,
                             double *rev, int64_t *cnt, uint8_t *flags,
-                            unsigned long long *cursor)
+                            unsigned long long *cursor, int64_t cap)
 {
     int lane = threadIdx.x & 63;
     int64_t base0 = blockIdx.x * (int64_t) blockDim.x + threadIdx.x - lane;
@@ -2245,7 +2247,7 @@ __global__ void k_extract_u(const unsigned long long *ukey, const double *urev,
         bool mine = i < (int64_t) uslots && ukey[i] != 0ULL;
         unsigned long long w;
         unsigned long long m = d_wave_claim(cursor, mine, lane, &w);
-        if (m && mine)
+        if (m && mine && w < (unsigned long long) cap)
         {
             int64_t k = (int64_t) (ukey[i] ^ (1ULL << 63));
             okey[w] = k;
@@ -2769,6 +2771,29 @@ __global__ void k_col_minmax(const uint8_t *col_s, gx_colmeta m,
     }
 }
 
+/* LEFT-OUTER prepare check: count the non-NULL rows of an i64 key column
+ * that hold one of the two values the unmatched table cannot represent —
+ * counts[0]: key 0 (biased 2^63 = the NULL-key group), counts[1]: key
+ * INT64_MIN (biased 0 = the empty-slot mark).  validity (optional): one
+ * byte per row, 0 = NULL (decoded as 0, not counted). */
+__global__ void k_col_count_reserved(const uint8_t *col_s, gx_colmeta m,
+                                     const uint8_t *validity,
+                                     unsigned long long *counts)
+{
+    int64_t i = blockIdx.x * (int64_t) blockDim.x + threadIdx.x;
+    int64_t stride = gridDim.x * (int64_t) blockDim.x;
+    unsigned long long nzero = 0, nmin = 0;
+    for (; i < m.nrows; i += stride)
+    {
+        if (validity && !validity[i]) continue;
+        int64_t k = gx_col_get<int64_t>(col_s, m, i);
+        if (k == 0) nzero++;
+        if (k == INT64_MIN) nmin++;
+    }
+    gx_wave_count_add(&counts[0], nzero);
+    gx_wave_count_add(&counts[1], nmin);
+}
+
 __global__ void k_rows_minmax(const gx_qual_row *rows, int64_t n,
                               unsigned long long *maxkey,
                               unsigned long long *minkey)
@@ -2901,19 +2926,35 @@ __global__ void k_orders_emitq(const uint8_t *ok_s, gx_colmeta ok_m,
  * stage, so the result is exact. */
 static constexpr int TOPK = 10;
 
-__device__ __forceinline__ bool topn_less(double ra, int32_t da,
-                                          double rb, int32_t db)
+/* "a ranks after b"? ORDER BY revenue DESC, o_orderdate ASC.  NUM: the
+ * revenue words are the numeric mode's int64 numerators stored in the f64
+ * result array; they are compared as the integers they are, never through
+ * their bit patterns read as doubles (small numerators are denormal
+ * patterns and would tie under a flush-to-zero mode).  Host and device. */
+template <bool NUM>
+__host__ __device__ __forceinline__ bool topn_less(double ra, int32_t da,
+                                                   double rb, int32_t db)
 {
-    /* "a ranks after b"? ORDER BY revenue DESC, o_orderdate ASC */
-    if (ra != rb) return ra < rb;
+    if constexpr (NUM)
+    {
+        int64_t ia, ib;
+        memcpy(&ia, &ra, 8);
+        memcpy(&ib, &rb, 8);
+        if (ia != ib) return ia < ib;
+    }
+    else if (ra != rb) return ra < rb;
     return da > db;
 }
 
+/* c_idx carries a candidate's validity: the source row index, or -1 for an
+ * empty candidate (fewer than K rows in the block's slices).  Keys are data
+ * and take any int64 value, so they cannot mark anything. */
+template <bool NUM>
 __global__ void __launch_bounds__(64)
 k_topn(const int64_t *okey, const int32_t *odate,
        const int32_t *oprio, const double *rev,
        const int64_t *cnt, const uint8_t *flags, int64_t n,
-       int64_t *c_okey, int32_t *c_odate, int32_t *c_oprio,
+       int64_t *c_idx, int64_t *c_okey, int32_t *c_odate, int32_t *c_oprio,
        double *c_rev, int64_t *c_cnt, uint8_t *c_flags)
 {
     /* one wave per block: 64 threads × K candidates → 640 in LDS */
@@ -2936,16 +2977,34 @@ k_topn(const int64_t *okey, const int32_t *odate,
          * ORDER BY o_orderdate ASC defaults to NULLS LAST */
         int32_t d = (flags && (flags[i] & 2)) ? INT32_MAX : odate[i];
         /* fails here for all but ~K·blocks·log(n) elements */
-        if (t_idx[TOPK - 1] >= 0 && topn_less(r, d, t_rev[TOPK - 1], t_date[TOPK - 1]))
+        if (t_idx[TOPK - 1] >= 0 && topn_less<NUM>(r, d, t_rev[TOPK - 1], t_date[TOPK - 1]))
             continue;
-        int k = TOPK - 1;
-        while (k > 0 && (t_idx[k - 1] < 0 ||
-                         topn_less(t_rev[k - 1], t_date[k - 1], r, d)))
+        /* sorted insert as a carry walking down the list: the carry swaps
+         * with every entry that ranks after it (or is empty), so the old
+         * entries move down one place and the last one falls out.  Every
+         * index is a compile-time constant after unrolling.  The earlier
+         * form, a shift loop over a run-time index k, lost t[0] whenever a
+         * new row went in front of an occupied t[0]: in the gfx950 code
+         * the compiler made of it, that path left t[1] as it was. */
+        double cr = r;
+        int32_t cd = d;
+        int64_t ci = i;
+#pragma unroll
+        for (int k = 0; k < TOPK; k++)
         {
-            t_rev[k] = t_rev[k - 1]; t_date[k] = t_date[k - 1]; t_idx[k] = t_idx[k - 1];
-            k--;
+            bool take = ci >= 0 &&
+                        (t_idx[k] < 0 ||
+                         topn_less<NUM>(t_rev[k], t_date[k], cr, cd));
+            double xr = t_rev[k];
+            int32_t xd = t_date[k];
+            int64_t xi = t_idx[k];
+            t_rev[k] = take ? cr : xr;
+            t_date[k] = take ? cd : xd;
+            t_idx[k] = take ? ci : xi;
+            cr = take ? xr : cr;
+            cd = take ? xd : cd;
+            ci = take ? xi : ci;
         }
-        t_rev[k] = r; t_date[k] = d; t_idx[k] = i;
     }
 #pragma unroll
     for (int k = 0; k < TOPK; k++)
@@ -2963,14 +3022,16 @@ k_topn(const int64_t *okey, const int32_t *odate,
             for (int j = 0; j < 64 * TOPK; j++)
             {
                 if (s_idx[j] < 0) continue;
-                if (best < 0 || topn_less(s_rev[best], s_date[best],
+                if (best < 0 || topn_less<NUM>(s_rev[best], s_date[best],
                                           s_rev[j], s_date[j]))
                     best = j;
             }
             int64_t w = (int64_t) blockIdx.x * TOPK + k;
-            if (best < 0) { c_okey[w] = -1; c_rev[w] = -1.0; c_odate[w] = 0;
-                            c_oprio[w] = 0; c_cnt[w] = 0; continue; }
+            if (best < 0) { c_idx[w] = -1; c_okey[w] = 0; c_rev[w] = 0.0;
+                            c_odate[w] = 0; c_oprio[w] = 0; c_cnt[w] = 0;
+                            c_flags[w] = 0; continue; }
             int64_t ib = s_idx[best];
+            c_idx[w] = ib;
             c_okey[w] = okey[ib];
             c_odate[w] = odate[ib];
             c_oprio[w] = oprio[ib];
@@ -4837,7 +4898,8 @@ static gx_status q3_ensure_hidden(gx_ctx *ctx, gx_table *t, uint8_t **hidden);
  * (execScan.c:241).  The per-step kernels run unchanged. */
 static gx_status q3_materialize_col(gx_ctx *ctx, gx_q3 *q, gx_table *t,
                                     int cidx, uint8_t **hidden,
-                                    bool fold_nulls = true)
+                                    bool fold_nulls = true,
+                                    devbuf *val_out = nullptr)
 {
     const gx_col &c = t->cols[cidx];
     int64_t n = c.m.nrows;
@@ -4897,6 +4959,47 @@ static gx_status q3_materialize_col(gx_ctx *ctx, gx_q3 *q, gx_table *t,
     q->mat[std::make_pair((const gx_table *) t, cidx)] = oc;
     q->mat_mem.push_back(flat.p);
     flat.p = nullptr;            /* ownership moves to gx_q3 */
+    if (val_out)                 /* the caller wants the per-row validity */
+    {
+        val_out->p = val.p;
+        val.p = nullptr;
+    }
+    return GX_OK;
+}
+
+/* LEFT OUTER restriction (gpuexec.h gx_q3_prepare_desc): the unmatched-group
+ * table stores keys biased by 2^63 with 0 as its empty-slot mark and 2^63 as
+ * the NULL-key group, so a non-NULL fact key INT64_MIN or 0 has no slot of
+ * its own.  Reject both here, by name, instead of dropping or merging rows.
+ * validity: the fact key's per-row validity when it was materialized. */
+static gx_status q3_check_outer_fact_keys(gx_ctx *ctx, gx_q3 *q,
+                                          const uint8_t *validity)
+{
+    const gx_col &lk = q3_col(q, q->li, q->desc.fact_key_col);
+    hipStream_t s = ctx->stream;
+    devbuf cb;
+    HIP_CHK(ctx, cb.alloc(16));
+    HIP_CHK(ctx, hipMemsetAsync(cb.p, 0, 16, s));
+    hipLaunchKernelGGL(k_col_count_reserved, dim3(GRID), dim3(TPB), 0, s,
+                       lk.dstream, lk.m, validity,
+                       cb.as<unsigned long long>());
+    unsigned long long hc[2] = {0, 0};
+    HIP_CHK(ctx, hipMemcpyAsync(hc, cb.p, 16, hipMemcpyDeviceToHost, s));
+    HIP_CHK(ctx, hipStreamSynchronize(s));
+    HIP_CHK(ctx, hipGetLastError());
+    if (hc[1])
+    {
+        set_err(ctx, "LEFT OUTER: fact key INT64_MIN "
+                     "(-9223372036854775808) is the unmatched table's "
+                     "empty-slot mark (gpuexec.h gx_q3_prepare_desc)%s", "");
+        return GX_ERR_INVALID;
+    }
+    if (hc[0])
+    {
+        set_err(ctx, "LEFT OUTER: non-NULL fact key 0 would be filed into "
+                     "the NULL-key group (gpuexec.h gx_q3_prepare_desc)%s", "");
+        return GX_ERR_INVALID;
+    }
     return GX_OK;
 }
 
@@ -5101,6 +5204,7 @@ extern "C" gx_status gx_q3_prepare_desc(gx_ctx *ctx, const gx_q3_desc *desc,
     /* materialize format-1 key/filter role columns FIRST (strict-NULL
      * reject seeds the hidden masks; the qual masks then AND into them
      * and may reference the materialized columns) */
+    devbuf fact_key_val;                /* LEFT OUTER fact key validity */
     for (auto &e : ex)                  /* table/mask trio */
         for (size_t ci = 0; ci < e.t->cols.size(); ci++)
         {
@@ -5128,17 +5232,30 @@ extern "C" gx_status gx_q3_prepare_desc(gx_ctx *ctx, const gx_q3_desc *desc,
             /* LEFT OUTER keeps fact rows that fail the ON clause: a NULL
              * fact key never matches, so the row EMITS with NULL attrs
              * (decoded 0 -> the NULL-key group) — do not hide it */
-            if (desc->fact_join == 1 && e.t == lineitem &&
-                (int) ci == desc->fact_key_col)
+            bool outer_key = desc->fact_join == 1 && e.t == lineitem &&
+                             (int) ci == desc->fact_key_col;
+            if (outer_key)
                 fold = false;
             gx_status st = q3_materialize_col(ctx, q, e.t, (int) ci, e.dst,
-                                              fold);
+                                              fold,
+                                              outer_key ? &fact_key_val
+                                                        : nullptr);
             if (st != GX_OK)
             {
                 gx_q3_free(q);
                 return st;
             }
         }
+    if (desc->fact_join == 1)
+    {
+        gx_status st = q3_check_outer_fact_keys(ctx, q,
+                                                fact_key_val.as<uint8_t>());
+        if (st != GX_OK)
+        {
+            gx_q3_free(q);
+            return st;
+        }
+    }
     /* AND-ed extra qual lists → per-table hidden bitmaps */
     for (auto &e : ex)
         if (e.nq > 0)
@@ -5270,6 +5387,21 @@ static gx_status q3_build_dim(gx_q3 *q, bool bitmap)
     else
         launch_cb((unsigned long long *) q->cset, std::false_type{});
     return GX_OK;
+}
+
+/* Bound on the LEFT-OUTER unmatched groups of a fact key column with nrows
+ * rows whose raw keys, reduced as UNSIGNED words (k_col_minmax), span
+ * [lmin, lmax]: distinct keys <= min(nrows, span), plus one for the NULL-key
+ * group.  The span lmax - lmin + 1 is computed modulo 2^64: a column holding
+ * both 0 and -1 (2^64-1) spans all 2^64 values and the sum wraps to 0, so a
+ * zero span (or inverted stats) falls back to nrows, which always bounds the
+ * distinct count.  Pure host function; gx_selftest_unmatched_bound. */
+static uint64_t q3_unmatched_bound(int64_t nrows, uint64_t lmin, uint64_t lmax)
+{
+    if (nrows <= 0) return 1;
+    uint64_t span = lmax - lmin + 1;
+    if (lmax < lmin || span == 0) span = (uint64_t) nrows;
+    return std::min<uint64_t>((uint64_t) nrows, span) + 1;
 }
 
 /* first run only: size the dimension membership structures and join/agg
@@ -5417,8 +5549,8 @@ static gx_status q3_size_and_alloc(gx_q3 *q)
     if (D.fact_join == 1)
     {
         /* LEFT OUTER: bound the unmatched table by the fact key stats
-         * (distinct keys <= min(nrows, range); NULL-decoded zeros only
-         * widen the range, which stays a valid bound).  Sized here for
+         * (q3_unmatched_bound; NULL-decoded zeros only widen the span,
+         * which stays a valid bound).  Sized here for
          * BOTH the local and Motion paths — the unmatched side is always
          * this rank's local fact shard. */
         const gx_q3_desc &DD = q->desc;
@@ -5431,9 +5563,7 @@ static gx_status q3_size_and_alloc(gx_q3 *q)
         HIP_CHK(ctx, hipMemcpyAsync(&lmax, q->dhits, 8, hipMemcpyDeviceToHost, s));
         HIP_CHK(ctx, hipMemcpyAsync(&lmin, q->dmin, 8, hipMemcpyDeviceToHost, s));
         HIP_CHK(ctx, hipStreamSynchronize(s));
-        uint64_t range = (q->li->nrows > 0 && lmax >= lmin)
-                             ? lmax - lmin + 1 : 1;
-        uint64_t bound = std::min<uint64_t>((uint64_t) q->li->nrows, range) + 1;
+        uint64_t bound = q3_unmatched_bound(q->li->nrows, lmin, lmax);
         uint64_t uslots = (uint64_t) pow2_at_least((int64_t) bound * 2);
         gx_status bs = hbm_budget_check(
             ctx, uslots * 24 + (bound + 1) * 33, "left-outer unmatched table");
@@ -6354,7 +6484,7 @@ extern "C" gx_status gx_q3_run(gx_q3 *q)
         hipLaunchKernelGGL(k_extract_u, dim3(egrid), dim3(TPB), 0, s,
                            q->ukey, q->urev, q->ucnt_u, q->umask + 1,
                            q->r_okey, q->r_odate, q->r_oprio, q->r_rev,
-                           q->r_cnt, q->r_flags, dcount);
+                           q->r_cnt, q->r_flags, dcount, q->rescap);
     HIP_CHK(ctx, hipEventRecord(ev[4], s));
 
     unsigned long long ngroups = 0, hits = 0;
@@ -6362,6 +6492,17 @@ extern "C" gx_status gx_q3_run(gx_q3 *q)
     HIP_CHK(ctx, hipMemcpyAsync(&hits, dhits, 8, hipMemcpyDeviceToHost, s));
     HIP_CHK(ctx, hipStreamSynchronize(s));
     HIP_CHK(ctx, hipGetLastError());
+    if (q->desc.fact_join == 1 && (int64_t) ngroups > q->rescap)
+    {
+        /* a sizing error must be an error, not a stray write: k_extract_u
+         * stopped writing at rescap */
+        q->ran = false;
+        char buf[96];
+        snprintf(buf, sizeof buf, "%lld groups, capacity %lld",
+                 (long long) ngroups, (long long) q->rescap);
+        set_err(ctx, "q3: extract overflow (%s)", buf);
+        return GX_ERR_INVALID;
+    }
     q->ngroups = (int64_t) ngroups;
 
     float t01 = 0, t12 = 0, t23 = 0, t34 = 0, t04 = 0;
@@ -6459,72 +6600,192 @@ extern "C" gx_status gx_q3_result(gx_q3 *q, gx_q3_group **out, int64_t *ngroups)
 /* top-N of THIS segment's groups (ORDER BY revenue DESC, o_orderdate ASC);
  * device-side per-block selection, host merge of blocks×K candidates.
  * At nsegs>1 each rank returns its local top-N; the coordinator-side merge
- * of nsegs×N rows is the reference's final Gather/Limit (trivial). */
-extern "C" gx_status gx_q3_topn(gx_q3 *q, int topn, gx_q3_group *out, int64_t *nout)
+ * of nsegs×N rows is the reference's final Gather/Limit (trivial).
+ * Two pieces, shared by gx_q3_topn and the test-only entry points: the
+ * launch + copy over device SoA pointers, and a pure host merge. */
+static constexpr int TOPN_GRID = 256;
+
+struct topn_cands {
+    std::vector<int64_t> idx, okey, cnt;  /* idx < 0: empty candidate */
+    std::vector<int32_t> odate, oprio;
+    std::vector<double> rev;
+    std::vector<uint8_t> flags;
+};
+
+static gx_status topn_launch_copy(gx_ctx *ctx, const int64_t *okey,
+                                  const int32_t *odate, const int32_t *oprio,
+                                  const double *rev, const int64_t *cnt,
+                                  const uint8_t *flags, int64_t n, int numeric,
+                                  topn_cands &C)
 {
-    if (!q || !q->ran || topn <= 0 || topn > 10) return GX_ERR_STATE;
-    gx_ctx *ctx = q->ctx;
     hipStream_t s = ctx->stream;
-    int64_t n = q->ngroups;
-    int grid = 256;
-    devbuf c_okey, c_odate, c_oprio, c_rev, c_cnt, c_fl;
-    HIP_CHK(ctx, c_okey.alloc(grid * 10 * 8));
-    HIP_CHK(ctx, c_odate.alloc(grid * 10 * 4));
-    HIP_CHK(ctx, c_oprio.alloc(grid * 10 * 4));
-    HIP_CHK(ctx, c_rev.alloc(grid * 10 * 8));
-    HIP_CHK(ctx, c_cnt.alloc(grid * 10 * 8));
-    HIP_CHK(ctx, c_fl.alloc(grid * 10));
-    const uint8_t *gflags = q->desc.fact_join == 1 ? q->r_flags : nullptr;
-    hipLaunchKernelGGL(k_topn, dim3(grid), dim3(64), 0, s,
-                       q->r_okey, q->r_odate, q->r_oprio, q->r_rev, q->r_cnt,
-                       gflags, n,
-                       c_okey.as<int64_t>(), c_odate.as<int32_t>(),
-                       c_oprio.as<int32_t>(), c_rev.as<double>(),
-                       c_cnt.as<int64_t>(), c_fl.as<uint8_t>());
-    std::vector<int64_t> hk(grid * 10), hc(grid * 10);
-    std::vector<int32_t> hd(grid * 10), hp(grid * 10);
-    std::vector<double> hr(grid * 10);
-    std::vector<uint8_t> hf(grid * 10);
-    HIP_CHK(ctx, hipMemcpyAsync(hf.data(), c_fl.p, grid * 10, hipMemcpyDeviceToHost, s));
-    HIP_CHK(ctx, hipMemcpyAsync(hk.data(), c_okey.p, grid * 10 * 8, hipMemcpyDeviceToHost, s));
-    HIP_CHK(ctx, hipMemcpyAsync(hd.data(), c_odate.p, grid * 10 * 4, hipMemcpyDeviceToHost, s));
-    HIP_CHK(ctx, hipMemcpyAsync(hp.data(), c_oprio.p, grid * 10 * 4, hipMemcpyDeviceToHost, s));
-    HIP_CHK(ctx, hipMemcpyAsync(hr.data(), c_rev.p, grid * 10 * 8, hipMemcpyDeviceToHost, s));
-    HIP_CHK(ctx, hipMemcpyAsync(hc.data(), c_cnt.p, grid * 10 * 8, hipMemcpyDeviceToHost, s));
+    const int nc = TOPN_GRID * TOPK;
+    devbuf c_idx, c_okey, c_odate, c_oprio, c_rev, c_cnt, c_fl;
+    HIP_CHK(ctx, c_idx.alloc(nc * 8));
+    HIP_CHK(ctx, c_okey.alloc(nc * 8));
+    HIP_CHK(ctx, c_odate.alloc(nc * 4));
+    HIP_CHK(ctx, c_oprio.alloc(nc * 4));
+    HIP_CHK(ctx, c_rev.alloc(nc * 8));
+    HIP_CHK(ctx, c_cnt.alloc(nc * 8));
+    HIP_CHK(ctx, c_fl.alloc(nc));
+    auto launch = [&](auto num) {
+        hipLaunchKernelGGL((k_topn<decltype(num)::value>), dim3(TOPN_GRID),
+                           dim3(64), 0, s,
+                           okey, odate, oprio, rev, cnt, flags, n,
+                           c_idx.as<int64_t>(),
+                           c_okey.as<int64_t>(), c_odate.as<int32_t>(),
+                           c_oprio.as<int32_t>(), c_rev.as<double>(),
+                           c_cnt.as<int64_t>(), c_fl.as<uint8_t>());
+    };
+    if (numeric) launch(std::true_type{});
+    else launch(std::false_type{});
+    C.idx.resize(nc); C.okey.resize(nc); C.cnt.resize(nc);
+    C.odate.resize(nc); C.oprio.resize(nc); C.rev.resize(nc);
+    C.flags.resize(nc);
+    HIP_CHK(ctx, hipMemcpyAsync(C.idx.data(), c_idx.p, nc * 8, hipMemcpyDeviceToHost, s));
+    HIP_CHK(ctx, hipMemcpyAsync(C.flags.data(), c_fl.p, nc, hipMemcpyDeviceToHost, s));
+    HIP_CHK(ctx, hipMemcpyAsync(C.okey.data(), c_okey.p, nc * 8, hipMemcpyDeviceToHost, s));
+    HIP_CHK(ctx, hipMemcpyAsync(C.odate.data(), c_odate.p, nc * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHK(ctx, hipMemcpyAsync(C.oprio.data(), c_oprio.p, nc * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHK(ctx, hipMemcpyAsync(C.rev.data(), c_rev.p, nc * 8, hipMemcpyDeviceToHost, s));
+    HIP_CHK(ctx, hipMemcpyAsync(C.cnt.data(), c_cnt.p, nc * 8, hipMemcpyDeviceToHost, s));
     HIP_CHK(ctx, hipStreamSynchronize(s));
     HIP_CHK(ctx, hipGetLastError());
+    return GX_OK;
+}
+
+/* pure host: order the valid candidates (idx >= 0) by revenue DESC, then
+ * effective date ASC (flag bit 1 = NULL date = INT32_MAX, i.e. last), and
+ * write the first topn as result rows.  Returns the number written. */
+static int64_t topn_merge(const int64_t *cidx, const int64_t *okey,
+                          const int32_t *odate, const int32_t *oprio,
+                          const double *rev, const int64_t *cnt,
+                          const uint8_t *flags, int ncand, int numeric,
+                          int topn, gx_q3_group *out)
+{
     std::vector<int> idx;
-    for (int i = 0; i < grid * 10; i++)
-        if (hk[i] >= 0) idx.push_back(i);
-    std::sort(idx.begin(), idx.end(), [&](int a, int b) {
-        if (hr[a] != hr[b]) return hr[a] > hr[b];
-        int32_t da = (hf[a] & 2) ? INT32_MAX : hd[a];
-        int32_t db = (hf[b] & 2) ? INT32_MAX : hd[b];
-        return da < db;
-    });
+    for (int i = 0; i < ncand; i++)
+        if (cidx[i] >= 0) idx.push_back(i);
+    auto eff = [&](int i) { return (flags[i] & 2) ? INT32_MAX : odate[i]; };
+    /* "a before b" = "b ranks after a" */
+    if (numeric)
+        std::sort(idx.begin(), idx.end(), [&](int a, int b) {
+            return topn_less<true>(rev[b], eff(b), rev[a], eff(a));
+        });
+    else
+        std::sort(idx.begin(), idx.end(), [&](int a, int b) {
+            return topn_less<false>(rev[b], eff(b), rev[a], eff(a));
+        });
     int64_t m = std::min<int64_t>(topn, (int64_t) idx.size());
     for (int64_t i = 0; i < m; i++)
     {
-        out[i].l_orderkey = hk[idx[i]];
-        out[i].o_orderdate = hd[idx[i]];
-        out[i].o_shippriority = hp[idx[i]];
-        out[i].revenue = q->numeric ? 0.0 : hr[idx[i]];
-        if (q->numeric)
+        int c = idx[i];
+        out[i].l_orderkey = okey[c];
+        out[i].o_orderdate = odate[c];
+        out[i].o_shippriority = oprio[c];
+        if (numeric)
         {
             int64_t num;
-            memcpy(&num, &hr[idx[i]], 8);
+            memcpy(&num, &rev[c], 8);
             out[i].revenue_num = num;
             out[i].revenue = (double) num / 1e4;
         }
         else
+        {
+            out[i].revenue = rev[c];
             out[i].revenue_num = 0;
-        out[i].nitems = hc[idx[i]];
-        out[i].key_is_null = (uint8_t) (hf[idx[i]] & 1);
-        out[i].attrs_null = (uint8_t) ((hf[idx[i]] >> 1) & 1);
+        }
+        out[i].nitems = cnt[c];
+        out[i].key_is_null = (uint8_t) (flags[c] & 1);
+        out[i].attrs_null = (uint8_t) ((flags[c] >> 1) & 1);
         memset(out[i]._pad, 0, sizeof(out[i]._pad));
     }
-    *nout = m;
+    return m;
+}
+
+static gx_status topn_run(gx_ctx *ctx, const int64_t *okey,
+                          const int32_t *odate, const int32_t *oprio,
+                          const double *rev, const int64_t *cnt,
+                          const uint8_t *flags, int64_t n, int numeric,
+                          int topn, gx_q3_group *out, int64_t *nout)
+{
+    topn_cands C;
+    gx_status st = topn_launch_copy(ctx, okey, odate, oprio, rev, cnt, flags,
+                                    n, numeric, C);
+    if (st != GX_OK) return st;
+    *nout = topn_merge(C.idx.data(), C.okey.data(), C.odate.data(),
+                       C.oprio.data(), C.rev.data(), C.cnt.data(),
+                       C.flags.data(), (int) C.idx.size(), numeric, topn, out);
     return GX_OK;
+}
+
+extern "C" gx_status gx_q3_topn(gx_q3 *q, int topn, gx_q3_group *out, int64_t *nout)
+{
+    if (!q || !q->ran || topn <= 0 || topn > TOPK) return GX_ERR_STATE;
+    const uint8_t *gflags = q->desc.fact_join == 1 ? q->r_flags : nullptr;
+    return topn_run(q->ctx, q->r_okey, q->r_odate, q->r_oprio, q->r_rev,
+                    q->r_cnt, gflags, q->ngroups, q->numeric, topn, out, nout);
+}
+
+/* test-only: the top-N stage over caller-supplied host SoA arrays (rev holds
+ * int64 numerators when numeric != 0; flags may be NULL) — uploads them and
+ * runs exactly what gx_q3_topn runs */
+extern "C" gx_status gx_test_topn(gx_ctx *ctx, const int64_t *okey,
+                                  const int32_t *odate, const int32_t *oprio,
+                                  const double *rev, const int64_t *cnt,
+                                  const uint8_t *flags, int64_t n, int numeric,
+                                  int topn, gx_q3_group *out, int64_t *nout)
+{
+    if (!ctx) return GX_ERR_INVALID;
+    if (n < 0 || topn <= 0 || topn > TOPK || !out || !nout ||
+        (n > 0 && (!okey || !odate || !oprio || !rev || !cnt)))
+    {
+        set_err(ctx, "gx_test_topn: need n >= 0, 1 <= topn <= 10 and the "
+                     "five SoA arrays%s", "");
+        return GX_ERR_INVALID;
+    }
+    hipStream_t s = ctx->stream;
+    devbuf d_okey, d_odate, d_oprio, d_rev, d_cnt, d_fl;
+    HIP_CHK(ctx, d_okey.alloc(n * 8));
+    HIP_CHK(ctx, d_odate.alloc(n * 4));
+    HIP_CHK(ctx, d_oprio.alloc(n * 4));
+    HIP_CHK(ctx, d_rev.alloc(n * 8));
+    HIP_CHK(ctx, d_cnt.alloc(n * 8));
+    if (flags) HIP_CHK(ctx, d_fl.alloc(n));
+    if (n > 0)
+    {
+        HIP_CHK(ctx, hipMemcpyAsync(d_okey.p, okey, n * 8, hipMemcpyHostToDevice, s));
+        HIP_CHK(ctx, hipMemcpyAsync(d_odate.p, odate, n * 4, hipMemcpyHostToDevice, s));
+        HIP_CHK(ctx, hipMemcpyAsync(d_oprio.p, oprio, n * 4, hipMemcpyHostToDevice, s));
+        HIP_CHK(ctx, hipMemcpyAsync(d_rev.p, rev, n * 8, hipMemcpyHostToDevice, s));
+        HIP_CHK(ctx, hipMemcpyAsync(d_cnt.p, cnt, n * 8, hipMemcpyHostToDevice, s));
+        if (flags)
+            HIP_CHK(ctx, hipMemcpyAsync(d_fl.p, flags, n, hipMemcpyHostToDevice, s));
+        HIP_CHK(ctx, hipStreamSynchronize(s));
+    }
+    return topn_run(ctx, d_okey.as<int64_t>(), d_odate.as<int32_t>(),
+                    d_oprio.as<int32_t>(), d_rev.as<double>(),
+                    d_cnt.as<int64_t>(), flags ? d_fl.as<uint8_t>() : nullptr,
+                    n, numeric ? 1 : 0, topn, out, nout);
+}
+
+/* the host merge alone on caller-supplied candidate arrays (callable
+ * without a GPU): cidx < 0 marks an empty candidate.  Returns 0, or 1 for
+ * bad arguments. */
+extern "C" int gx_selftest_topn_merge(const int64_t *cidx, const int64_t *okey,
+                                      const int32_t *odate, const int32_t *oprio,
+                                      const double *rev, const int64_t *cnt,
+                                      const uint8_t *flags, int ncand,
+                                      int numeric, int topn, gx_q3_group *out,
+                                      int64_t *nout)
+{
+    if (ncand < 0 || topn <= 0 || topn > TOPK || !out || !nout ||
+        (ncand > 0 && (!cidx || !okey || !odate || !oprio || !rev || !cnt ||
+                       !flags)))
+        return 1;
+    *nout = topn_merge(cidx, okey, odate, oprio, rev, cnt, flags, ncand,
+                       numeric ? 1 : 0, topn, out);
+    return 0;
 }
 
 extern "C" gx_status gx_q3_free(gx_q3 *q)
@@ -7024,6 +7285,14 @@ extern "C" int gx_selftest_motion_layout(const uint64_t *cnts_all, int n, int se
                          kmin, kmax);
     }
     return 0;
+}
+
+/* sizing's bound on the LEFT-OUTER unmatched groups (q3_unmatched_bound) on
+ * caller-supplied column stats; callable without a GPU */
+extern "C" uint64_t gx_selftest_unmatched_bound(int64_t nrows, uint64_t lmin,
+                                                uint64_t lmax)
+{
+    return q3_unmatched_bound(nrows, lmin, lmax);
 }
 
 /* RCCL linkage self-check: init a 1-rank communicator and run one

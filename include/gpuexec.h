@@ -292,6 +292,15 @@ typedef struct gx_q3_desc {
  * - join keys must be >= 1: slot value 0 is the empty-slot sentinel (PG
  *   sequence-keyed tables start at 1); a key 0 on the build side returns
  *   GX_ERR_INVALID instead of silently dropping the row.
+ * - LEFT OUTER (fact_join = 1), checked at prepare: the fact key column must
+ *   hold neither a non-NULL 0 nor INT64_MIN in any stored row (filtered and
+ *   visimap-hidden rows included).  The unmatched-group table keeps keys
+ *   biased by 2^63, with 0 as its empty-slot mark (INT64_MIN would be
+ *   dropped or inherit another key's sums) and 2^63 as the NULL-key group (a
+ *   real 0 would be reported as key_is_null).  Both return GX_ERR_INVALID
+ *   from gx_q3_prepare_desc with the key named in gx_last_error; NULL fact
+ *   keys and every other int64 value, negative ones included, form their
+ *   own groups.
  * - HBM budget: if the semijoin set / join table would exceed free HBM
  *   (override: GX_HBM_BUDGET_MB), sizing fails with GX_ERR_OOM and the
  *   required vs available GB in gx_last_error BEFORE any allocation — the
@@ -314,7 +323,10 @@ gx_status gx_q3_dim_mode(gx_q3 *q, int *mode);
 gx_status gx_q3_result(gx_q3 *q, gx_q3_group **out, int64_t *ngroups);
 /* top-N of this segment's groups (Q3's ORDER BY revenue DESC, o_orderdate
  * LIMIT N; N ≤ 10) — the nodeSort/nodeLimit stage, device-selected.
- * Outer-join groups sort with NULL dates LAST (PG ASC NULLS LAST). */
+ * Outer-join groups sort with NULL dates LAST (PG ASC NULLS LAST).  Any
+ * int64 group key may come back, negative ones included; numeric mode orders
+ * by the int64 numerators.  GX_ERR_STATE before the first run or for N
+ * outside 1..10, with nothing written. */
 gx_status gx_q3_topn(gx_q3 *q, int topn, gx_q3_group *out, int64_t *nout);
 gx_status gx_q3_free(gx_q3 *q);
 
@@ -456,6 +468,34 @@ int gx_selftest_motion_layout(const uint64_t *cnts_all, int n, int seg,
                               int64_t qual, uint64_t kmin, uint64_t kmax,
                               int nsegs, int tf_pct,
                               gx_test_tbl_layout *layout);
+
+/* ---- the result tail of Q3: top-N select and the unmatched-table bound ---- */
+
+/* The top-N stage over caller-supplied host SoA arrays of n groups: uploads
+ * them and runs exactly what gx_q3_topn runs (same launch, copy and merge).
+ * rev holds f64 revenues, or the int64 numerators' words when numeric != 0;
+ * flags (bit 0 key_is_null, bit 1 attrs_null = NULL date) may be NULL.
+ * GX_ERR_INVALID, with nothing written, unless n >= 0 and 1 <= topn <= 10. */
+gx_status gx_test_topn(gx_ctx *ctx, const int64_t *okey, const int32_t *odate,
+                       const int32_t *oprio, const double *rev,
+                       const int64_t *cnt, const uint8_t *flags, int64_t n,
+                       int numeric, int topn, gx_q3_group *out, int64_t *nout);
+/* The host merge of that stage alone, no GPU needed: ncand candidates as the
+ * device stage hands them over, cidx[i] < 0 marking an empty one (its other
+ * fields are ignored; keys are data and mark nothing).  Writes the first
+ * min(topn, valid) rows by revenue DESC, effective date ASC (flag bit 1 set
+ * = NULL date = last).  Returns 0, or 1 for bad arguments. */
+int gx_selftest_topn_merge(const int64_t *cidx, const int64_t *okey,
+                           const int32_t *odate, const int32_t *oprio,
+                           const double *rev, const int64_t *cnt,
+                           const uint8_t *flags, int ncand, int numeric,
+                           int topn, gx_q3_group *out, int64_t *nout);
+/* Sizing's bound on the LEFT-OUTER unmatched groups for a fact key column of
+ * nrows rows whose keys, as unsigned words, span [lmin, lmax]; no GPU
+ * needed.  Never below min(nrows, lmax - lmin + 1) + 1, the span taken
+ * without wrap-around. */
+uint64_t gx_selftest_unmatched_bound(int64_t nrows, uint64_t lmin,
+                                     uint64_t lmax);
 
 #ifdef __cplusplus
 }
