@@ -278,6 +278,9 @@ def _load():
     lib.gx_selftest_unmatched_bound.restype = ctypes.c_uint64
     lib.gx_selftest_unmatched_bound.argtypes = [ctypes.c_int64, ctypes.c_uint64,
                                                 ctypes.c_uint64]
+    lib.gx_selftest_rle_block_class.restype = ctypes.c_int64
+    lib.gx_selftest_rle_block_class.argtypes = [ctypes.c_void_p, ctypes.c_int64,
+                                                ctypes.c_void_p, ctypes.c_int64]
     return lib
 
 
@@ -331,6 +334,23 @@ def unmatched_bound(nrows, lmin, lmax):
     only, no GPU)."""
     return int(lib().gx_selftest_unmatched_bound(
         int(nrows), int(lmin) & (2**64 - 1), int(lmax) & (2**64 - 1)))
+
+
+RLEBLK_UNFUSED, RLEBLK_NOBITMAP, RLEBLK_VARINT, RLEBLK_FIXED2 = 0, 1, 2, 3
+
+
+def rle_block_classes(stream):
+    """How bind routes each block of a format-1 int64 stream for the fused RLE
+    fact-key probe (host only, no GPU): an int32 array of RLEBLK_* values, one
+    per block.  One RLEBLK_UNFUSED block sends the column to materialize."""
+    arr = np.frombuffer(stream, np.uint8)
+    n = lib().gx_selftest_rle_block_class(arr.ctypes.data, len(arr), None, 0)
+    if n < 0:
+        raise ValueError("gx_selftest_rle_block_class: bad stream")
+    out = np.zeros(n, np.int32)
+    lib().gx_selftest_rle_block_class(arr.ctypes.data, len(arr),
+                                      out.ctypes.data, n)
+    return out
 
 
 def _topn_soa(okey, odate, oprio, rev, cnt, flags, numeric):
@@ -720,7 +740,10 @@ class Context:
         self._chk(self._lib.gx_q3_prepare(self._h, cust._t, orders._t, lineitem._t,
                                           cutoff, ctypes.byref(q)))
         if numeric:
-            self._chk(self._lib.gx_q3_set_numeric(q, 1))
+            st = self._lib.gx_q3_set_numeric(q, 1)
+            if st != 0:
+                self._lib.gx_q3_free(q)
+            self._chk(st)
         return Q3(self, q, tables=(cust, orders, lineitem))
 
     def close(self):

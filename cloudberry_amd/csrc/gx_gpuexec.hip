@@ -1930,9 +1930,13 @@ __global__ void k_li_probe_agg_t(const uint8_t *lk_s, gx_colmeta lk_m,
  * (lineitem is clustered by l_orderkey — the reference's own table order —
  * so a run is one order's lineitems), and the ship/price/discount columns
  * are touched only for runs whose key is in the join table.
- * Fast parallel count decode relies on this writer's fixed 2-byte repeat
- * encodings (csize == 2·ncnt detects it); other conforming streams take the
- * serial per-block walk. */
+ * The fast parallel count decode needs every repeat count of the block to
+ * be 2 bytes (this writer's fixed form, or a reference block whose runs all
+ * hold 65..16384 rows); the host decides that per block at bind
+ * (rle_block_class, gx_blockref.cls) and other conforming blocks take the
+ * serial per-block walk.  Columns with a block this kernel does not read
+ * (Orig, DELTA, NULLs, phys > RLE_MAX_PHYS) never get here: prepare
+ * materializes them. */
 static constexpr int RLE_MAX_PHYS = 4096;
 
 template <typename KT, bool VM = false>
@@ -1970,11 +1974,10 @@ __global__ void k_li_probe_agg_rle(const uint8_t *lk_s, const gx_blockref *dir,
         }
         const int64_t *datum;
         const uint8_t *bmp = nullptr, *cnts = nullptr;
-        int32_t ncnt = 0, csize = 0;
+        int32_t csize = 0;
         if (flags & 0x2)
         {
             int32_t bmbits = ((const int32_t *) c)[5];
-            ncnt = ((const int32_t *) c)[6];
             csize = ((const int32_t *) c)[7];
             bmp = c + 32;
             cnts = bmp + ((bmbits + 7) >> 3);
@@ -1991,7 +1994,7 @@ __global__ void k_li_probe_agg_rle(const uint8_t *lk_s, const gx_blockref *dir,
             datum = (const int64_t *) (c + 16);
 
         /* ---- phase 1: per-physical repeat counts into s_starts[p] ---- */
-        if (bmp && csize == 2 * ncnt)
+        if (bmp && dir[b].cls == GX_RLEBLK_FIXED2)
         {
             /* parallel: byte-popcount prefix of the bitmap, then fixed-stride
              * count lookup per ON bit */
@@ -3053,6 +3056,8 @@ struct gx_col {
     gx_blockref *ddir = nullptr; /* device block directory (format 1) */
     int64_t nblocks = 0;
     bool has_null = false;       /* any block carries a NULL bitmap (flags&1) */
+    bool fused_ok = false;       /* format 1: every block is one the fused RLE
+                                    probe reads (no GX_RLEBLK_UNFUSED) */
 };
 
 struct gx_table {
@@ -3441,14 +3446,63 @@ static bool host_decompress_stream(const uint8_t *s, int64_t nbytes,
     return any;
 }
 
+/* Class of one DatumStreamBlock for the fused RLE fact-key probe: c points at
+ * the block content (past the 24-byte AO envelope), datalen is its length,
+ * rows the envelope's row count.  The fused scan reads Dense/Dense_Enhanced
+ * blocks of 8-byte datums with at most RLE_MAX_PHYS physical datums and
+ * neither NULL bitmap nor DELTA; everything else, and any header whose
+ * sections do not fit datalen, is GX_RLEBLK_UNFUSED.  FIXED2 is claimed only
+ * when the leading byte of EVERY count says "2 bytes" and the bitmap has one
+ * ON bit per count: csize == 2*ncnt alone also holds for a 1-byte + 3-byte
+ * mix.  Pure host function; gx_selftest_rle_block_class. */
+static int rle_block_class(const uint8_t *c, int64_t datalen, int64_t rows)
+{
+    if (datalen < 16) return GX_RLEBLK_UNFUSED;
+    int16_t version, flags;
+    int32_t logical, phys, psize;
+    memcpy(&version, c, 2);
+    memcpy(&flags, c + 2, 2);
+    memcpy(&logical, c + 4, 4);
+    memcpy(&phys, c + 8, 4);
+    memcpy(&psize, c + 12, 4);
+    if ((version != 1 && version != 2) || (flags & ~0x2) != 0 ||
+        phys < 0 || phys > RLE_MAX_PHYS || psize != phys * 8 ||
+        logical != rows)
+        return GX_RLEBLK_UNFUSED;
+    if (!(flags & 0x2))
+        return (logical == phys && 16 + (int64_t) psize <= datalen)
+                   ? GX_RLEBLK_NOBITMAP : GX_RLEBLK_UNFUSED;
+    if (datalen < 32) return GX_RLEBLK_UNFUSED;
+    int32_t bmbits, ncnt, csize;
+    memcpy(&bmbits, c + 20, 4);
+    memcpy(&ncnt, c + 24, 4);
+    memcpy(&csize, c + 28, 4);
+    if (bmbits != phys || ncnt < 0 || csize < 0) return GX_RLEBLK_UNFUSED;
+    int64_t bmbytes = (bmbits + 7) >> 3;
+    int64_t hdr = 32 + bmbytes + csize;
+    if (((hdr + 7) & ~7LL) + psize > datalen) return GX_RLEBLK_UNFUSED;
+    if (csize != 2 * (int64_t) ncnt) return GX_RLEBLK_VARINT;
+    const uint8_t *bmp = c + 32, *cnts = bmp + bmbytes;
+    int64_t on = 0;
+    for (int32_t p = 0; p < phys; p++)
+        on += (bmp[p >> 3] >> (p & 7)) & 1;
+    if (on != ncnt) return GX_RLEBLK_VARINT;
+    for (int32_t i = 0; i < ncnt; i++)
+        if ((cnts[2 * i] >> 6) != 1) return GX_RLEBLK_VARINT;
+    return GX_RLEBLK_FIXED2;
+}
+
 /* walk a stream's AO envelope headers on the HOST, building the per-block
- * directory a variable-geometry (Dense/RLE) stream needs */
+ * directory a variable-geometry (Dense/RLE) stream needs.  fused_ok_out:
+ * every block is one the fused RLE probe reads (rle_block_class). */
 static gx_status parse_block_dir(const uint8_t *s, int64_t nbytes,
                                  std::vector<gx_blockref> &dir, int64_t *rows_out,
-                                 bool *has_null_out = nullptr)
+                                 bool *has_null_out = nullptr,
+                                 bool *fused_ok_out = nullptr)
 {
     int64_t off = 0, row = 0;
     if (has_null_out) *has_null_out = false;
+    if (fused_ok_out) *fused_ok_out = true;
     while (off + 24 <= nbytes)
     {
         uint32_t b03, b47;
@@ -3478,7 +3532,9 @@ static gx_status parse_block_dir(const uint8_t *s, int64_t nbytes,
             memcpy(&flags, s + off + 26, 2);
             if (flags & 1) *has_null_out = true; /* HAS_NULLBITMAP */
         }
-        dir.push_back({off, row, (int32_t) rows, 0});
+        int cls = rle_block_class(s + off + 24, datalen, rows);
+        if (fused_ok_out && cls == GX_RLEBLK_UNFUSED) *fused_ok_out = false;
+        dir.push_back({off, row, (int32_t) rows, cls});
         row += rows;
         off += blocklen;
     }
@@ -3586,7 +3642,7 @@ extern "C" gx_status gx_table_bind(gx_ctx *ctx, const gx_coldesc *cols, int ncol
             int64_t rows = 0;
             gx_status st = parse_block_dir((const uint8_t *) stream_src,
                                            stream_len, dir, &rows,
-                                           &col.has_null);
+                                           &col.has_null, &col.fused_ok);
             if (st != GX_OK || rows != cols[c].nrows)
             {
                 set_err(ctx, "bad Dense/RLE stream%s", "");
@@ -3834,7 +3890,8 @@ extern "C" gx_status gx_tpch_gen(gx_ctx *ctx, gx_tpch_table which, double sf,
             std::vector<gx_blockref> dir;
             int64_t rows = 0;
             if (parse_block_dir(stream_bytes.data(), (int64_t) stream_bytes.size(),
-                                dir, &rows) != GX_OK || rows != n)
+                                dir, &rows, &c0.has_null, &c0.fused_ok) != GX_OK ||
+                rows != n)
             { set_err(ctx, "rle self-encode mismatch%s", ""); delete t; (void) hipFree(dcounts); return GX_ERR_INVALID; }
             c0.format = 1;
             c0.nblocks = (int64_t) dir.size();
@@ -5133,6 +5190,15 @@ extern "C" gx_status gx_q3_prepare_desc(gx_ctx *ctx, const gx_q3_desc *desc,
         return ci == desc->fact_key_col || ci == desc->fact_a_col ||
                ci == desc->fact_b_col || ci == desc->fact_filter.col;
     };
+    /* the one column the fused RLE probe scans in place: an inner join's
+     * NULL-free fact key whose every block the kernel reads (classified at
+     * bind, gx_col.fused_ok).  Orig, DELTA and over-wide blocks send the
+     * column down the materialize route with the NULL-bearing ones. */
+    auto is_fused_key = [&](gx_table *t, int ci) {
+        const gx_col &c = t->cols[ci];
+        return t == lineitem && ci == desc->fact_key_col && c.format == 1 &&
+               !c.has_null && c.fused_ok && desc->fact_join == 0;
+    };
     for (auto *t : {customer, orders, lineitem})
         for (size_t ci = 0; ci < t->cols.size(); ci++)
         {
@@ -5140,8 +5206,7 @@ extern "C" gx_status gx_q3_prepare_desc(gx_ctx *ctx, const gx_q3_desc *desc,
             if (c.format == 0 || !is_used(t, (int) ci)) continue;
             if (dim_text && t == customer && (int) ci == desc->dim_filter.col)
                 continue;                              /* varlena texteq path */
-            if (t == lineitem && (int) ci == desc->fact_key_col &&
-                !c.has_null && desc->fact_join == 0)
+            if (is_fused_key(t, (int) ci))
                 continue;                              /* fused RLE scan */
             if (!is_matable(t, (int) ci))
             {
@@ -5212,8 +5277,7 @@ extern "C" gx_status gx_q3_prepare_desc(gx_ctx *ctx, const gx_q3_desc *desc,
             if (c.format == 0 || !is_used(e.t, (int) ci) ||
                 !is_matable(e.t, (int) ci))
                 continue;
-            if (e.t == lineitem && (int) ci == desc->fact_key_col &&
-                !c.has_null && desc->fact_join == 0)
+            if (is_fused_key(e.t, (int) ci))
                 continue;               /* fused RLE path */
             /* join-variety NULL rules (nodeHashjoin.c:425,442,652-659):
              * - LASJ (anti): a NULL mid fk never matches the dim set, so
@@ -5985,6 +6049,15 @@ static gx_status q3_launch_extract(gx_ctx *ctx, hipStream_t s, int key_width,
 extern "C" gx_status gx_q3_set_numeric(gx_q3 *q, int on)
 {
     if (!q) return GX_ERR_INVALID;
+    /* the fused RLE probe has no integer-aggregation form: say so here, the
+     * earliest point the mode is known, not at the first run.  A format-1
+     * fact key that prepare materialized is a flat column and is fine. */
+    if (on && q3_col(q, q->li, q->desc.fact_key_col).format == 1)
+    {
+        set_err(q->ctx, "numeric mode is not supported with a fused RLE fact "
+                        "key (numeric+RLE); bind the key plain%s", "");
+        return GX_ERR_INVALID;
+    }
     q->numeric = on ? 1 : 0;
     return GX_OK;
 }
@@ -7293,6 +7366,23 @@ extern "C" uint64_t gx_selftest_unmatched_bound(int64_t nrows, uint64_t lmin,
                                                 uint64_t lmax)
 {
     return q3_unmatched_bound(nrows, lmin, lmax);
+}
+
+/* bind's per-block routing of the fused RLE probe (parse_block_dir +
+ * rle_block_class) over a host stream of 8-byte datums; callable without a
+ * GPU.  Writes the gx_rle_class of the first min(blocks, cap) blocks and
+ * returns the number of blocks, or -1 for a stream bind would refuse. */
+extern "C" int64_t gx_selftest_rle_block_class(const uint8_t *stream,
+                                               int64_t nbytes, int32_t *cls,
+                                               int64_t cap)
+{
+    if (!stream || nbytes < 0 || (cap > 0 && !cls)) return -1;
+    std::vector<gx_blockref> dir;
+    int64_t rows = 0;
+    if (parse_block_dir(stream, nbytes, dir, &rows) != GX_OK) return -1;
+    for (int64_t b = 0; b < (int64_t) dir.size() && b < cap; b++)
+        cls[b] = dir[b].cls;
+    return (int64_t) dir.size();
 }
 
 /* RCCL linkage self-check: init a 1-rank communicator and run one

@@ -250,7 +250,18 @@ struct gx_blockref {
     int64_t offset;              /* byte offset of the AO block */
     int64_t first_row;           /* 0-based logical first row */
     int32_t rows;                /* logical rows in the block */
-    int32_t pad;
+    int32_t cls;                 /* gx_rle_class, set at bind (rle_block_class) */
+};
+
+/* What the fused RLE fact-key probe (k_li_probe_agg_rle) may do with a block.
+ * Classified once per block on the host at bind; a column with any
+ * GX_RLEBLK_UNFUSED block is materialized at prepare instead. */
+enum gx_rle_class {
+    GX_RLEBLK_UNFUSED = 0,       /* Orig, DELTA, NULL bitmap, phys > 4096, or
+                                    a header the fused scan cannot trust */
+    GX_RLEBLK_NOBITMAP = 1,      /* Dense, flags == 0: one row per datum */
+    GX_RLEBLK_VARINT = 2,        /* RLE, counts of mixed byte lengths */
+    GX_RLEBLK_FIXED2 = 3,        /* RLE, every repeat count is 2 bytes */
 };
 
 /* gx_ord_row (Motion-1 payload) is declared in include/gpuexec.h — it is

@@ -85,8 +85,15 @@ typedef struct gx_coldesc {
     int64_t     nrows;
     int32_t     blocksize;     /* AO blocksize the stream was written with */
     int32_t     format;        /* 0 = Orig (compresstype=none), 1 =
-                                  Dense/Dense_Enhanced incl. RLE_TYPE/DELTA
-                                  (no-null subset) */
+                                  Dense/Dense_Enhanced incl. RLE_TYPE/DELTA,
+                                  Orig blocks allowed too (concatenated
+                                  segment files).  As an inner join's Q3
+                                  fact key, a NULL-free column of Dense
+                                  blocks with at most 4096 physical datums
+                                  and no DELTA is scanned in place by the
+                                  fused RLE probe; any other block
+                                  materializes the column at prepare
+                                   */
     int32_t     codec;         /* bulk codec for compressedLength>0 blocks:
                                   0/1 = zlib, 2 = zstd (the pg_appendonly
                                   compresstype analog) */
@@ -496,6 +503,16 @@ int gx_selftest_topn_merge(const int64_t *cidx, const int64_t *okey,
  * without wrap-around. */
 uint64_t gx_selftest_unmatched_bound(int64_t nrows, uint64_t lmin,
                                      uint64_t lmax);
+/* How bind routes each block of a format-1 stream of 8-byte datums for the
+ * fused RLE fact-key probe; no GPU needed.  cls[b]: 0 = not fused (Orig,
+ * DELTA, NULL bitmap, more than 4096 physical datums: one such block and
+ * prepare materializes the whole column), 1 = Dense without a repeat bitmap,
+ * 2 = RLE with repeat counts of mixed byte lengths (serial count walk),
+ * 3 = RLE with every count 2 bytes (parallel count decode).  Writes at most
+ * cap entries; returns the number of blocks, or -1 for a stream bind
+ * refuses. */
+int64_t gx_selftest_rle_block_class(const uint8_t *stream, int64_t nbytes,
+                                    int32_t *cls, int64_t cap);
 
 #ifdef __cplusplus
 }

@@ -446,13 +446,13 @@ def q3_numeric(cust, orders, lineitem, cutoff=None):
     return res
 
 
-def aocs_encode_rle(vals):
+def aocs_encode_rle(vals, blocksize=32768):
     """RLE_TYPE (Dense_Enhanced) encode of a fixed-width NOT NULL column."""
     vals = np.ascontiguousarray(vals)
     width = vals.itemsize
     cap = len(vals) * width + (1 << 20)
     buf = np.zeros(cap, np.uint8)
-    got = lib.orc_aocs_encode_rle(vals.ctypes.data, width, len(vals), 1, 32768,
+    got = lib.orc_aocs_encode_rle(vals.ctypes.data, width, len(vals), 1, blocksize,
                                   buf.ctypes.data, cap)
     assert got >= 0
     return buf[:got].tobytes()
