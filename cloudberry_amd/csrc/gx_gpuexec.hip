@@ -95,6 +95,7 @@ extern "C" const char *gx_version(void) { return "gpuexec 0.1 (gfx950)"; }
 
 static constexpr int TPB = 256;          /* threads per block (4 waves) */
 static constexpr int GRID = 2048;        /* grid-stride grid (fills 256 CUs) */
+static constexpr int ORDERS_GRID = 32768; /* k_orders_build: measured optimum */
 
 /* RAII for TEMPORARY device buffers: early returns (HIP_CHK/RCCL_CHK) free
  * them automatically.  Long-lived state stays owned by gx_table / gx_q3. */
@@ -125,6 +126,31 @@ static inline int64_t pow2_at_least(int64_t want)
     int64_t sz = 1024;
     while (sz < want) sz <<= 1;
     return sz;
+}
+
+/* launch dispatch: kernels are compiled per key width and per boolean mode;
+ * these turn the run-time (width, void *) pair or flag into the typed call.
+ * f receives the pointer as unsigned int * (width 4) or unsigned long long *
+ * (any other width), resp. std::true_type / std::false_type. */
+template <typename F>
+static inline void by_width(int width, const void *p, F &&f)
+{
+    if (width == 4) f((const unsigned int *) p);
+    else f((const unsigned long long *) p);
+}
+
+template <typename F>
+static inline void by_width(int width, void *p, F &&f)
+{
+    if (width == 4) f((unsigned int *) p);
+    else f((unsigned long long *) p);
+}
+
+template <typename F>
+static inline void by_flag(bool on, F &&f)
+{
+    if (on) f(std::true_type{});
+    else f(std::false_type{});
 }
 
 /* ================= generation: count / scan / emit ================= */
@@ -667,7 +693,7 @@ __global__ void k_decode_dense(const uint8_t *stream, const gx_blockref *dir,
     }
 }
 
-/* ================= Motion routing ================= *//* ================= Motion routing ================= */
+/* ================= Motion routing ================= */
 
 __global__ void k_route(const int64_t *keys, int64_t n, int32_t nsegs, int32_t *out)
 {
@@ -846,6 +872,141 @@ __device__ __forceinline__ void gx_wave_count_add(unsigned long long *dst,
         v += __shfl_down((unsigned long long) v, o, 64);
     if ((threadIdx.x & 63) == 0 && v)
         atomicAdd(dst, v);
+}
+
+/* wave min/max of unsigned keys, then ONE atomicMax/atomicMin per wave.
+ * GUARD skips a wave that saw no key (kmax still 0 / kmin still ~0);
+ * k_col_minmax alone commits unconditionally, as it always has. */
+template <bool GUARD = true>
+__device__ __forceinline__ void d_wave_minmax_commit(unsigned long long kmax,
+                                                     unsigned long long kmin,
+                                                     unsigned long long *maxkey,
+                                                     unsigned long long *minkey)
+{
+    for (int o = 32; o; o >>= 1)
+    {
+        unsigned long long v = __shfl_down(kmax, o, 64);
+        if (v > kmax) kmax = v;
+        unsigned long long w = __shfl_down(kmin, o, 64);
+        if (w < kmin) kmin = w;
+    }
+    if ((threadIdx.x & 63) == 0)
+    {
+        if (!GUARD || kmax) atomicMax(maxkey, kmax);
+        if (!GUARD || kmin != ~0ULL) atomicMin(minkey, kmin);
+    }
+}
+
+/* Probe walk over an open-addressing key array (empty slot = 0), continuing
+ * from a first slot whose word v the caller has already loaded.  Returns the
+ * slot that holds k, or ~0ULL when k is absent.  The compare ZERO-EXTENDS
+ * the stored key, so in u32 mode a probe key >= 2^32 never matches —
+ * width-safe without a hot-loop branch (a per-row guard here measured +57%,
+ * the r1 visimap lesson). */
+template <typename KT>
+__device__ __forceinline__ uint64_t d_table_find(const KT *tkey, uint64_t tmask,
+                                                 uint64_t slot, KT v, uint64_t k)
+{
+    while (true)
+    {
+        if (v == (KT) 0) return ~0ULL;
+        if ((uint64_t) v == k) return slot;
+        slot = (slot + 1) & tmask;
+        v = tkey[slot];
+    }
+}
+
+/* The same walk for callers that have not loaded the first word: leaves the
+ * slot that holds k in `slot` and returns whether k is there.  Kept beside
+ * d_table_find on purpose: calling that one from k_li_probe_agg_num and
+ * k_li_probe_agg_rle compiles their loops differently (fewer SGPRs/VGPRs, one
+ * occupancy step, profiles/refactor_kernel_resources.txt), and the numeric
+ * probe has no benchmark leg that could show such a change costs nothing. */
+template <typename KT>
+__device__ __forceinline__ bool d_table_find_from(const KT *tkey, uint64_t tmask,
+                                                  uint64_t &slot, uint64_t k)
+{
+    bool found = false;
+    while (true)
+    {
+        KT v = tkey[slot];
+        if (v == (KT) 0) break;
+        if ((uint64_t) v == k) { found = true; break; }  /* zext */
+        slot = (slot + 1) & tmask;
+    }
+    return found;
+}
+
+/* insert k into an open-addressing key set (empty slot = 0; duplicates
+ * collapse) */
+template <typename KS>
+__device__ __forceinline__ void d_set_insert(KS *set, uint64_t mask, uint64_t k)
+{
+    uint64_t slot = gx_hmix64(k) & mask;
+    while (true)
+    {
+        KS prev = atomicCAS(&set[slot], (KS) 0, (KS) k);
+        if (prev == (KS) 0 || prev == (KS) k) break;
+        slot = (slot + 1) & mask;
+    }
+}
+
+/* LEFT OUTER (HJ_FILL_OUTER): claim the slot of unmatched fact key k in the
+ * second table.  Keys are stored biased (k ^ 2^63) so 0 stays the empty
+ * mark; NULL fact keys (decoded 0) coalesce into one group.  Returns the
+ * slot. */
+__device__ __forceinline__ uint64_t d_unmatched_claim(unsigned long long *ukey,
+                                                      uint64_t umask, uint64_t k)
+{
+    uint64_t bk = k ^ (1ULL << 63);
+    uint64_t slot = gx_hmix64(bk) & umask;
+    while (true)
+    {
+        unsigned long long prev = atomicCAS(&ukey[slot], 0ULL, bk);
+        if (prev == 0ULL || prev == bk) break;
+        slot = (slot + 1) & umask;
+    }
+    return slot;
+}
+
+/* Block exclusive scan of n values into out[0..n): thread t scans the
+ * contiguous chunk [t*C, (t+1)*C) serially (val(i) is read before out[i] is
+ * written, so val may read out itself), the per-thread sums are scanned by
+ * thread 0 through s_part[blockDim.x], and the bases are added back.  The
+ * grand total is stored to *total (when given) by thread 0 before the
+ * second barrier.  Three __syncthreads; every thread of the block calls. */
+template <typename F>
+__device__ __forceinline__ void d_block_excl_scan(uint32_t *out, int n,
+                                                  uint32_t *s_part,
+                                                  uint32_t *total, F val)
+{
+    int C = (n + blockDim.x - 1) / blockDim.x;
+    int lo = threadIdx.x * C, hi = min(lo + C, n);
+    uint32_t acc = 0;
+    for (int i = lo; i < hi; i++)
+    {
+        uint32_t v = val(i);
+        out[i] = acc;
+        acc += v;
+    }
+    s_part[threadIdx.x] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0)
+    {
+        uint32_t run = 0;
+        for (int t = 0; t < (int) blockDim.x; t++)
+        {
+            uint32_t v = s_part[t];
+            s_part[t] = run;
+            run += v;
+        }
+        if (total) *total = run;
+    }
+    __syncthreads();
+    uint32_t base = s_part[threadIdx.x];
+    for (int i = lo; i < hi; i++)
+        out[i] += base;
+    __syncthreads();
 }
 
 /* Standalone columnar scan + filter (BASELINE config 2; the SeqScan+qual
@@ -1088,18 +1249,41 @@ __global__ void k_texteq_mask_blocks(const uint8_t *stream,
     }
 }
 
-/* flat-mask variants of the customer scan (mask built by k_texteq_mask) */
-__global__ void k_cust_count_mask(const uint8_t *key_s, gx_colmeta key_m,
-                                  const uint8_t *mask, const uint8_t *vmap,
-                                  unsigned long long *count,
-                                  unsigned long long *maxkey,
-                                  unsigned long long *minkey)
+/* The dimension row predicate of the customer scans, in the two forms
+ * prepare can choose: a flat per-row mask (built once by k_texteq_mask for a
+ * text qual) or an int8 column compare (mktsegment = BUILDING). */
+struct gx_dim_pred_mask {
+    const uint8_t *mask;
+    __device__ __forceinline__ bool operator()(int64_t i) const
+    {
+        return mask[i] != 0;
+    }
+};
+
+struct gx_dim_pred_cmp {
+    const uint8_t *mkt_s;
+    gx_colmeta mkt_m;
+    int cop;
+    int8_t clit;
+    __device__ __forceinline__ bool operator()(int64_t i) const
+    {
+        return gx_cmp(cop, gx_col_get<int8_t>(mkt_s, mkt_m, i), clit);
+    }
+};
+
+/* customer: count qualifying rows and their key range (for set sizing) */
+template <typename PRED>
+__global__ void k_cust_count(const uint8_t *key_s, gx_colmeta key_m,
+                             PRED pred, const uint8_t *vmap,
+                             unsigned long long *count,
+                             unsigned long long *maxkey,
+                             unsigned long long *minkey)
 {
     int64_t i = blockIdx.x * (int64_t) blockDim.x + threadIdx.x;
     int64_t stride = gridDim.x * (int64_t) blockDim.x;
     unsigned long long local = 0, kmax = 0, kmin = ~0ULL;
     for (; i < key_m.nrows; i += stride)
-        if (mask[i] && !gx_vm_hidden(vmap, i))
+        if (!gx_vm_hidden(vmap, i) && pred(i))
         {
             local++;
             unsigned long long k = (unsigned long long)
@@ -1108,100 +1292,15 @@ __global__ void k_cust_count_mask(const uint8_t *key_s, gx_colmeta key_m,
             if (k < kmin) kmin = k;
         }
     gx_wave_count_add(count, local);
-    for (int o = 32; o; o >>= 1)
-    {
-        unsigned long long v = __shfl_down(kmax, o, 64);
-        if (v > kmax) kmax = v;
-        unsigned long long w = __shfl_down(kmin, o, 64);
-        if (w < kmin) kmin = w;
-    }
-    if ((threadIdx.x & 63) == 0)
-    {
-        if (kmax) atomicMax(maxkey, kmax);
-        if (kmin != ~0ULL) atomicMin(minkey, kmin);
-    }
+    d_wave_minmax_commit(kmax, kmin, maxkey, minkey);
 }
 
-template <typename KS, bool BM = false>
-__global__ void k_cust_build_mask(const uint8_t *key_s, gx_colmeta key_m,
-                                  const uint8_t *mask, const uint8_t *vmap,
-                                  KS *set, uint64_t cmask,
-                                  unsigned long long *bloom, uint64_t bwmask,
-                                  unsigned long long *bits, uint64_t kmin,
-                                  uint64_t range)
-{
-    int64_t i = blockIdx.x * (int64_t) blockDim.x + threadIdx.x;
-    int64_t stride = gridDim.x * (int64_t) blockDim.x;
-    if constexpr (BM)
-    {
-        /* bitmap form: whole waves iterate together (d_dimbits_set_wave) */
-        for (int64_t base = i - (threadIdx.x & 63); base < key_m.nrows;
-             base += stride)
-        {
-            int64_t r = base + (threadIdx.x & 63);
-            bool act = r < key_m.nrows && mask[r] && !gx_vm_hidden(vmap, r);
-            uint64_t k = act ? (uint64_t) gx_col_get<int64_t>(key_s, key_m, r) : 0;
-            d_dimbits_set_wave(bits, kmin, range, act, k);
-        }
-        return;
-    }
-    for (; i < key_m.nrows; i += stride)
-    {
-        if (!mask[i] || gx_vm_hidden(vmap, i)) continue;
-        uint64_t k = (uint64_t) gx_col_get<int64_t>(key_s, key_m, i);
-        d_bloom_set(bloom, bwmask, k);
-        uint64_t slot = gx_hmix64(k) & cmask;
-        while (true)
-        {
-            KS prev = atomicCAS(&set[slot], (KS) 0, (KS) k);
-            if (prev == (KS) 0 || prev == (KS) k) break;
-            slot = (slot + 1) & cmask;
-        }
-    }
-}
-
-/* customer: count BUILDING rows (for set sizing) *//* customer: count BUILDING rows (for set sizing) */
-__global__ void k_cust_count(const uint8_t *key_s, gx_colmeta key_m,
-                             const uint8_t *mkt_s, gx_colmeta mkt_m,
-                             const uint8_t *vmap, int cop, int8_t clit,
-                             unsigned long long *count,
-                             unsigned long long *maxkey,
-                             unsigned long long *minkey)
-{
-    int64_t i = blockIdx.x * (int64_t) blockDim.x + threadIdx.x;
-    int64_t stride = gridDim.x * (int64_t) blockDim.x;
-    unsigned long long local = 0, kmax = 0, kmin = ~0ULL;
-    for (; i < mkt_m.nrows; i += stride)
-        if (!gx_vm_hidden(vmap, i) &&
-            gx_cmp(cop, gx_col_get<int8_t>(mkt_s, mkt_m, i), clit))
-        {
-            local++;
-            unsigned long long k = (unsigned long long) gx_col_get<int64_t>(key_s, key_m, i);
-            if (k > kmax) kmax = k;
-            if (k < kmin) kmin = k;
-        }
-    gx_wave_count_add(count, local);
-    for (int o = 32; o; o >>= 1)
-    {
-        unsigned long long v = __shfl_down(kmax, o, 64);
-        if (v > kmax) kmax = v;
-        unsigned long long w = __shfl_down(kmin, o, 64);
-        if (w < kmin) kmin = w;
-    }
-    if ((threadIdx.x & 63) == 0)
-    {
-        if (kmax) atomicMax(maxkey, kmax);
-        if (kmin != ~0ULL) atomicMin(minkey, kmin);
-    }
-}
-
-/* customer: filter mktsegment=BUILDING, record c_custkey in the dimension
+/* customer: record the c_custkey of every qualifying row in the dimension
  * membership structure: its bit of the bitmap (BM), or bloom + open set.
  * Replaces the build side of the cust⋈orders join (nodeHash.c:1886). */
-template <typename KS, bool BM = false>
+template <typename KS, bool BM, typename PRED>
 __global__ void k_cust_build(const uint8_t *key_s, gx_colmeta key_m,
-                             const uint8_t *mkt_s, gx_colmeta mkt_m,
-                             const uint8_t *vmap, int cop, int8_t clit,
+                             PRED pred, const uint8_t *vmap,
                              KS *set, uint64_t mask,
                              unsigned long long *bloom, uint64_t bwmask,
                              unsigned long long *bits, uint64_t kmin,
@@ -1216,8 +1315,7 @@ __global__ void k_cust_build(const uint8_t *key_s, gx_colmeta key_m,
              base += stride)
         {
             int64_t r = base + (threadIdx.x & 63);
-            bool act = r < key_m.nrows && !gx_vm_hidden(vmap, r) &&
-                       gx_cmp(cop, gx_col_get<int8_t>(mkt_s, mkt_m, r), clit);
+            bool act = r < key_m.nrows && !gx_vm_hidden(vmap, r) && pred(r);
             uint64_t k = act ? (uint64_t) gx_col_get<int64_t>(key_s, key_m, r) : 0;
             d_dimbits_set_wave(bits, kmin, range, act, k);
         }
@@ -1225,17 +1323,10 @@ __global__ void k_cust_build(const uint8_t *key_s, gx_colmeta key_m,
     }
     for (; i < key_m.nrows; i += stride)
     {
-        if (gx_vm_hidden(vmap, i)) continue;
-        if (!gx_cmp(cop, gx_col_get<int8_t>(mkt_s, mkt_m, i), clit)) continue;
+        if (gx_vm_hidden(vmap, i) || !pred(i)) continue;
         uint64_t k = (uint64_t) gx_col_get<int64_t>(key_s, key_m, i);
         d_bloom_set(bloom, bwmask, k);
-        uint64_t slot = gx_hmix64(k) & mask;
-        while (true)
-        {
-            KS prev = atomicCAS(&set[slot], (KS) 0, (KS) k);
-            if (prev == (KS) 0 || prev == (KS) k) break;
-            slot = (slot + 1) & mask;
-        }
+        d_set_insert(set, mask, k);
     }
 }
 
@@ -1305,18 +1396,7 @@ __global__ void k_orders_count(const uint8_t *ok_s, gx_colmeta ok_m,
         if (k < kmin) kmin = k;
     }
     gx_wave_count_add(count, local);
-    for (int o = 32; o; o >>= 1)
-    {
-        unsigned long long v = __shfl_down(kmax, o, 64);
-        if (v > kmax) kmax = v;
-        unsigned long long w = __shfl_down(kmin, o, 64);
-        if (w < kmin) kmin = w;
-    }
-    if ((threadIdx.x & 63) == 0)
-    {
-        if (kmax) atomicMax(maxkey, kmax);
-        if (kmin != ~0ULL) atomicMin(minkey, kmin);
-    }
+    d_wave_minmax_commit(kmax, kmin, maxkey, minkey);
 }
 
 /* Join/agg table payload, beside the SoA key array tkey[]: one 16-byte
@@ -1353,8 +1433,8 @@ __device__ __forceinline__ void d_slot_claim(gx_attrpair *tattr, gx_aggslot *tag
  * key array then sits comfortably in the 256 MiB Infinity Cache), u64
  * otherwise.  Key compares stay exact either way (PG narrow-int hashing
  * spirit; sentinel 0 is safe — orderkeys start at 1). */
-template <typename KT, typename KS, bool CHUNKED = false, bool VM = false,
-          bool ANTI = false, bool BM = false>
+template <typename KT, typename KS, bool VM = false, bool ANTI = false,
+          bool BM = false>
 __global__ void k_orders_build(const uint8_t *ok_s, gx_colmeta ok_m,
                                const uint8_t *oc_s, gx_colmeta oc_m,
                                const uint8_t *od_s, gx_colmeta od_m,
@@ -1367,22 +1447,10 @@ __global__ void k_orders_build(const uint8_t *ok_s, gx_colmeta ok_m,
                                gx_attrpair *tattr, gx_aggslot *tagg,
                                gx_slotmap smap)
 {
-    int64_t i, stride, iend;
-    if constexpr (CHUNKED)
-    {
-        int64_t chunk = (ok_m.nrows + gridDim.x - 1) / gridDim.x;
-        i = blockIdx.x * chunk + threadIdx.x;
-        iend = min((int64_t) blockIdx.x * chunk + chunk, ok_m.nrows);
-        stride = blockDim.x;
-    }
-    else
-    {
-        i = blockIdx.x * (int64_t) blockDim.x + threadIdx.x;
-        iend = ok_m.nrows;
-        stride = gridDim.x * (int64_t) blockDim.x;
-    }
+    int64_t i = blockIdx.x * (int64_t) blockDim.x + threadIdx.x;
+    int64_t stride = gridDim.x * (int64_t) blockDim.x;
     uint64_t tmask = smap.mask;
-    for (; i < iend; i += stride)
+    for (; i < ok_m.nrows; i += stride)
     {
         if constexpr (VM)
             if (gx_vm_hidden(vmap, i)) continue;
@@ -1433,14 +1501,12 @@ __global__ void k_orders_build(const uint8_t *ok_s, gx_colmeta ok_m,
 /* lineitem probe + aggregate — THE dominant kernel.
  * scan (aocsam.c:1131 semantics) + probe (nodeHashjoin.c:553-652) +
  * SUM transition (nodeAgg.c:836 + float.c:769) fused; build slots ARE the
- * agg groups (group key functionally determined by l_orderkey). */
-/* lineitem probe+agg (the dominant kernel).  B = rows per thread per
- * iteration; the batched form keeps B independent load chains in flight
- * (the kernel is latency-bound at full occupancy: PMC shows 85% WAIT_ANY,
- * ~300M L3 probe round-trips).  Guard-free main region — the tail is a
- * separate scalar loop — and filtered lanes probe slot 0 (L1-resident)
- * instead of branching, so each load batch stays in one basic block. */
-template <int B, typename KT, bool VM = false, bool OUTER = false>
+ * agg groups (group key functionally determined by l_orderkey).
+ * One row per thread per grid-stride iteration.  The kernel is latency-bound
+ * at full occupancy (PMC: 85% WAIT_ANY, ~300M L3 probe round-trips); every
+ * batched, tiled and LDS-staged form measured slower and was removed
+ * (DESIGN.md "Measured bandwidth ceiling"). */
+template <typename KT, bool VM = false, bool OUTER = false>
 __global__ void k_li_probe_agg_t(const uint8_t *lk_s, gx_colmeta lk_m,
                                  const uint8_t *pr_s, gx_colmeta pr_m,
                                  const uint8_t *di_s, gx_colmeta di_m,
@@ -1464,14 +1530,7 @@ __global__ void k_li_probe_agg_t(const uint8_t *lk_s, gx_colmeta lk_m,
     auto umiss = [&](uint64_t k, int64_t i) {
         if constexpr (OUTER)
         {
-            uint64_t bk = k ^ (1ULL << 63);
-            uint64_t slot = gx_hmix64(bk) & umask;
-            while (true)
-            {
-                unsigned long long prev = atomicCAS(&ukey[slot], 0ULL, bk);
-                if (prev == 0ULL || prev == bk) break;
-                slot = (slot + 1) & umask;
-            }
+            uint64_t slot = d_unmatched_claim(ukey, umask, k);
             double price = gx_col_get<double>(pr_s, pr_m, i);
             double disc = gx_col_get<double>(di_s, di_m, i);
             atomicAdd(&urev[slot], price * (1.0 - disc));
@@ -1482,19 +1541,6 @@ __global__ void k_li_probe_agg_t(const uint8_t *lk_s, gx_colmeta lk_m,
             (void) k; (void) i;
         }
     };
-    auto resolve = [&](uint64_t k, uint64_t slot, KT v) -> uint64_t {
-        /* first slot already loaded as v; walk on collision; the compare
-         * ZERO-EXTENDS the stored key, so in u32 mode a probe key >= 2^32
-         * never matches — width-safe without a hot-loop branch (a per-row
-         * guard here measured +57%, the r1 visimap lesson) */
-        while (true)
-        {
-            if (v == (KT) 0) return ~0ULL;
-            if ((uint64_t) v == k) return slot;
-            slot = (slot + 1) & tmask;
-            v = tkey[slot];
-        }
-    };
     auto hit = [&](uint64_t slot, int64_t i) {
         double price = gx_col_get<double>(pr_s, pr_m, i);
         double disc = gx_col_get<double>(di_s, di_m, i);
@@ -1502,428 +1548,34 @@ __global__ void k_li_probe_agg_t(const uint8_t *lk_s, gx_colmeta lk_m,
         atomicAdd(&tagg[slot].cnt, 1.0);
         local_hits++;
     };
-    if constexpr (B == 1)
+    int64_t i = blockIdx.x * (int64_t) blockDim.x + threadIdx.x;
+    int64_t stride = gridDim.x * (int64_t) blockDim.x;
+    /* visimap via a compile-time template split (VM): the default
+     * instantiation carries no per-row check at all — a runtime guard
+     * here cost 57% (measured, profiles/bw_probe_r01.txt).  The two
+     * adds stay two plain atomics: pairing them into one wave
+     * instruction through an LDS queue measured 6.17 ms against 4.41
+     * (profiles/aggslot_probe_ab.txt).
+     * On the packed 16-B slot this kernel is 0.05-0.10 ms SLOWER than
+     * on separate sum/count arrays (4.37-4.42 against 4.30-4.32 ms at
+     * SF100: 4 slots per 64-B line instead of 8, so a wave's adds
+     * cover more lines).  The layout is kept because the orders build
+     * gives the same amount back (one 16-B claim store instead of two
+     * 8-B ones: 2.28 against 2.35-2.37 ms) and the whole step is equal
+     * within spread — three-way A/B in profiles/aggslot_abc.json. */
+    for (; i < lk_m.nrows; i += stride)
     {
-        int64_t i = blockIdx.x * (int64_t) blockDim.x + threadIdx.x;
-        int64_t stride = gridDim.x * (int64_t) blockDim.x;
-        /* visimap via a compile-time template split (VM): the default
-         * instantiation carries no per-row check at all — a runtime guard
-         * here cost 57% (measured, profiles/bw_probe_r01.txt).  The two
-         * adds stay two plain atomics: pairing them into one wave
-         * instruction through an LDS queue measured 6.17 ms against 4.41
-         * (profiles/aggslot_probe_ab.txt).
-         * On the packed 16-B slot this kernel is 0.05-0.10 ms SLOWER than
-         * on separate sum/count arrays (4.37-4.42 against 4.30-4.32 ms at
-         * SF100: 4 slots per 64-B line instead of 8, so a wave's adds
-         * cover more lines).  The layout is kept because the orders build
-         * gives the same amount back (one 16-B claim store instead of two
-         * 8-B ones: 2.28 against 2.35-2.37 ms) and the whole step is equal
-         * within spread — three-way A/B in profiles/aggslot_abc.json. */
-        for (; i < lk_m.nrows; i += stride)
-        {
-            if constexpr (VM)
-                if (gx_vm_hidden(vmap, i)) continue;
-            if (!gx_cmp(fop, gx_col_get<int32_t>(sh_s, sh_m, i), flit)) continue;
-            uint64_t k = (uint64_t) gx_col_get<int64_t>(lk_s, lk_m, i);
-            uint64_t slot = smap.slot0(k);
-            uint64_t r = resolve(k, slot, tkey[slot]);
-            if (r != ~0ULL) hit(r, i);
-            else umiss(k, i);
-        }
-    }
-    else if constexpr (B == -12 || B == -13)
-    {
-        /* TILE-COMPACT-THEN-PROBE: the per-thread batching variants lost
-         * because batching the SCAN breaks its coalescing; here each
-         * workgroup alternates phases over a tile — a coalesced scan
-         * compacts survivors (key,row) into LDS, then the probe phase
-         * works off LDS with fully independent iterations the compiler
-         * can overlap (the decomposition in profiles/bw_probe_r01.txt
-         * showed the three chain stages are exactly additive in the
-         * fused form). */
-        constexpr int TILE = (B == -13) ? 2048 : 1024;
-        __shared__ unsigned int s_cnt;
-        __shared__ uint64_t s_key[TILE];
-        __shared__ uint32_t s_row[TILE];
-        int64_t chunk = (lk_m.nrows + gridDim.x - 1) / gridDim.x;
-        int64_t lo = blockIdx.x * chunk;
-        int64_t hi = min(lo + chunk, lk_m.nrows);
-        int lane = threadIdx.x & 63;
-        for (int64_t t0 = lo; t0 < hi; t0 += TILE)
-        {
-            int64_t tend = min(t0 + TILE, hi);
-            if (threadIdx.x == 0) s_cnt = 0;
-            __syncthreads();
-            for (int64_t i = t0 + threadIdx.x; i < tend; i += blockDim.x)
-            {
-                bool keep = gx_cmp(fop, gx_col_get<int32_t>(sh_s, sh_m, i), flit);
-                uint64_t k = keep ? (uint64_t) gx_col_get<int64_t>(lk_s, lk_m, i) : 0;
-                unsigned long long m = __ballot(keep);
-                if (m)
-                {
-                    unsigned wb = 0;
-                    int leader = __ffsll((long long) m) - 1;
-                    if (lane == leader)
-                        wb = atomicAdd(&s_cnt, (unsigned) __popcll(m));
-                    wb = __shfl(wb, leader, 64);
-                    if (keep)
-                    {
-                        unsigned o = __popcll(m & ((lane == 0) ? 0ULL
-                                                  : (~0ULL >> (64 - lane))));
-                        s_key[wb + o] = k;
-                        s_row[wb + o] = (uint32_t) (i - lo);
-                    }
-                }
-            }
-            __syncthreads();
-            int nsv = (int) s_cnt;
-            for (int j = threadIdx.x; j < nsv; j += blockDim.x)
-            {
-                uint64_t k = s_key[j];
-                uint64_t slot = smap.slot0(k);
-                uint64_t r = resolve(k, slot, tkey[slot]);
-                if (r != ~0ULL) hit(r, lo + (int64_t) s_row[j]);
-            }
-            __syncthreads();
-        }
-    }
-    else if constexpr (B == -14)
-    {
-        /* glds double-buffered tile scan: the ship+key STREAM loads move
-         * to async global->LDS DMA (fire-and-forget on the VM counter, no
-         * VGPR destinations, no wave stall at issue), so each wave's
-         * latency budget is spent exclusively on the probe gathers and
-         * hit processing while the NEXT tile's stream bytes are already
-         * in flight.  The r1 decomposition showed the three chain stages
-         * exactly additive at max occupancy — this is the one formulation
-         * that adds outstanding-request capacity instead of re-scheduling
-         * the same per-wave budget (cdna_hip_programming.md §5 glds).
-         * Requires: fixed-format streams, even rpb for the 8-B key column
-         * (16-B glds covers two consecutive rows; rpb 4090 at the default
-         * 32 KB blocksize), no visimap.  Env-gated experiment. */
-        constexpr int TILE = 1024;
-        __shared__ int32_t s_ship[2][TILE];
-        __shared__ int64_t s_key[2][TILE];
-        const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-        const int nwaves = blockDim.x >> 6;
-        const int wrows = TILE / nwaves;
-        int64_t chunk = (((lk_m.nrows + gridDim.x - 1) / gridDim.x) + 1) & ~1LL;
-        int64_t lo = blockIdx.x * chunk;
-        int64_t hi = min(lo + chunk, lk_m.nrows);
-        if (lo >= hi) { gx_wave_count_add(hits, local_hits); return; }
-        int64_t full_end = lo + ((hi - lo) / TILE) * TILE;
-        auto goff = [](const gx_colmeta &m, int64_t row) -> int64_t {
-            int64_t b = (int64_t) gx_mulhi64((uint64_t) row, m.magic);
-            return b * m.full_block_len + GX_AOCS_DATUM_OFF +
-                   (row - b * m.rpb) * m.width;
-        };
-        auto issue_tile = [&](int64_t t0, int buf) {
-            int64_t wbase = t0 + wave * wrows;
-            for (int g = 0; g < wrows / 64; g++)
-            {
-                const uint8_t *ga = sh_s + goff(sh_m, wbase + g * 64 + lane);
-                __builtin_amdgcn_global_load_lds(
-                    (const __attribute__((address_space(1))) void *) ga,
-                    (__attribute__((address_space(3))) void *)
-                        &s_ship[buf][wave * wrows + g * 64], 4, 0, 0);
-            }
-            for (int g = 0; g < wrows / 128; g++)
-            {
-                const uint8_t *ga = lk_s + goff(lk_m, wbase + g * 128 + lane * 2);
-                __builtin_amdgcn_global_load_lds(
-                    (const __attribute__((address_space(1))) void *) ga,
-                    (__attribute__((address_space(3))) void *)
-                        &s_key[buf][wave * wrows + g * 128], 16, 0, 0);
-            }
-        };
-        if (lo < full_end)
-            issue_tile(lo, 0);
-        for (int64_t t0 = lo; t0 < full_end; t0 += TILE)
-        {
-            int cur = (int) (((t0 - lo) / TILE) & 1);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();      /* tile cur visible to all */
-            if (t0 + TILE < full_end)
-                issue_tile(t0 + TILE, cur ^ 1);
-            for (int i = threadIdx.x; i < TILE; i += blockDim.x)
-            {
-                if (!gx_cmp(fop, s_ship[cur][i], flit)) continue;
-                uint64_t k = (uint64_t) s_key[cur][i];
-                uint64_t slot = smap.slot0(k);
-                uint64_t r = resolve(k, slot, tkey[slot]);
-                if (r != ~0ULL) hit(r, t0 + i);
-            }
-            __builtin_amdgcn_s_barrier();      /* done reading buf cur */
-        }
-        for (int64_t i = full_end + threadIdx.x; i < hi; i += blockDim.x)
-        {
-            if (!gx_cmp(fop, gx_col_get<int32_t>(sh_s, sh_m, i), flit)) continue;
-            uint64_t k = (uint64_t) gx_col_get<int64_t>(lk_s, lk_m, i);
-            uint64_t slot = smap.slot0(k);
-            uint64_t r = resolve(k, slot, tkey[slot]);
-            if (r != ~0ULL) hit(r, i);
-        }
-    }
-    else if constexpr (B == -9)
-    {
-        /* DIAGNOSTIC ONLY (wrong results): B=1 without the ship filter —
-         * isolates how much of the probe's critical path is the
-         * ship→key→table dependent chain vs the key→table chain alone. */
-        int64_t i = blockIdx.x * (int64_t) blockDim.x + threadIdx.x;
-        int64_t stride = gridDim.x * (int64_t) blockDim.x;
-        for (; i < lk_m.nrows; i += stride)
-        {
-            uint64_t k = (uint64_t) gx_col_get<int64_t>(lk_s, lk_m, i);
-            uint64_t slot = smap.slot0(k);
-            uint64_t r = resolve(k, slot, tkey[slot]);
-            if (r != ~0ULL) hit(r, i);
-        }
-    }
-    else if constexpr (B == -10)
-    {
-        /* DIAGNOSTIC ONLY: ship+key loads and filter, NO table probe —
-         * the pure two-stream scan cost. */
-        int64_t i = blockIdx.x * (int64_t) blockDim.x + threadIdx.x;
-        int64_t stride = gridDim.x * (int64_t) blockDim.x;
-        unsigned long long acc = 0;
-        for (; i < lk_m.nrows; i += stride)
-        {
-            if (!gx_cmp(fop, gx_col_get<int32_t>(sh_s, sh_m, i), flit)) continue;
-            acc += (uint64_t) gx_col_get<int64_t>(lk_s, lk_m, i);
-        }
-        local_hits += acc & 1;       /* keep the loads */
-    }
-    else if constexpr (B == -11)
-    {
-        /* DIAGNOSTIC ONLY: filter + key + table probe, NO aggregation
-         * (no price/disc loads, no atomics) — isolates the table-lookup
-         * chain from the hit processing. */
-        int64_t i = blockIdx.x * (int64_t) blockDim.x + threadIdx.x;
-        int64_t stride = gridDim.x * (int64_t) blockDim.x;
-        for (; i < lk_m.nrows; i += stride)
-        {
-            if (!gx_cmp(fop, gx_col_get<int32_t>(sh_s, sh_m, i), flit)) continue;
-            uint64_t k = (uint64_t) gx_col_get<int64_t>(lk_s, lk_m, i);
-            uint64_t slot = smap.slot0(k);
-            uint64_t r = resolve(k, slot, tkey[slot]);
-            if (r != ~0ULL) local_hits++;
-        }
-    }
-    else if constexpr (B == -5)
-    {
-        /* software-pipelined B=1: next iteration's ship+key loads issue
-         * BEFORE the current iteration's table round-trip is consumed —
-         * same perfect coalescing as B=1, one row per lane per step. */
-        int64_t i = blockIdx.x * (int64_t) blockDim.x + threadIdx.x;
-        int64_t stride = gridDim.x * (int64_t) blockDim.x;
-        if (i < lk_m.nrows)
-        {
-            int32_t ship = gx_col_get<int32_t>(sh_s, sh_m, i);
-            uint64_t key = (uint64_t) gx_col_get<int64_t>(lk_s, lk_m, i);
-            while (true)
-            {
-                int64_t nx = i + stride;
-                int32_t ship_n = 0;
-                uint64_t key_n = 0;
-                if (nx < lk_m.nrows)
-                {
-                    ship_n = gx_col_get<int32_t>(sh_s, sh_m, nx);
-                    key_n = (uint64_t) gx_col_get<int64_t>(lk_s, lk_m, nx);
-                }
-                if (gx_cmp(fop, ship, flit))
-                {
-                    uint64_t slot = smap.slot0(key);
-                    uint64_t r = resolve(key, slot, tkey[slot]);
-                    if (r != ~0ULL) hit(r, i);
-                }
-                if (nx >= lk_m.nrows) break;
-                i = nx;
-                ship = ship_n;
-                key = key_n;
-            }
-        }
-    }
-    else if constexpr (B == -6)
-    {
-        /* 2-deep pipeline: ship/key AND the first table word for the NEXT
-         * row are all in flight while the CURRENT row is resolved, so the
-         * serial chain ship->key->table never stalls back-to-back.
-         * Filtered lanes prefetch slot 0 (stays L1-resident). */
-        int64_t i = blockIdx.x * (int64_t) blockDim.x + threadIdx.x;
-        int64_t stride = gridDim.x * (int64_t) blockDim.x;
-        if (i < lk_m.nrows)
-        {
-            int32_t ship = gx_col_get<int32_t>(sh_s, sh_m, i);
-            uint64_t key = (uint64_t) gx_col_get<int64_t>(lk_s, lk_m, i);
-            bool pass = gx_cmp(fop, ship, flit);
-            uint64_t slot = pass ? smap.slot0(key) : 0;
-            KT v = tkey[slot];
-            while (true)
-            {
-                int64_t nx = i + stride;
-                int32_t ship_n = 0;
-                uint64_t key_n = 0;
-                if (nx < lk_m.nrows)
-                {
-                    ship_n = gx_col_get<int32_t>(sh_s, sh_m, nx);
-                    key_n = (uint64_t) gx_col_get<int64_t>(lk_s, lk_m, nx);
-                }
-                bool pass_n = gx_cmp(fop, ship_n, flit) && nx < lk_m.nrows;
-                uint64_t slot_n = pass_n ? smap.slot0(key_n) : 0;
-                KT v_n = tkey[slot_n];
-                if (pass)
-                {
-                    uint64_t r = resolve(key, slot, v);
-                    if (r != ~0ULL) hit(r, i);
-                }
-                if (nx >= lk_m.nrows) break;
-                i = nx;
-                key = key_n;
-                pass = pass_n;
-                slot = slot_n;
-                v = v_n;
-            }
-        }
-    }
-    else if constexpr (B == -2)
-    {
-        /* non-temporal stream loads: keep L2/L3 for the table */
-        int64_t i = blockIdx.x * (int64_t) blockDim.x + threadIdx.x;
-        int64_t stride = gridDim.x * (int64_t) blockDim.x;
-        for (; i < lk_m.nrows; i += stride)
-        {
-            if (!gx_cmp(fop, gx_col_get_nt<int32_t>(sh_s, sh_m, i), flit)) continue;
-            uint64_t k = (uint64_t) gx_col_get_nt<int64_t>(lk_s, lk_m, i);
-            uint64_t slot = smap.slot0(k);
-            uint64_t r = resolve(k, slot, tkey[slot]);
-            if (r == ~0ULL) continue;
-            double price = gx_col_get_nt<double>(pr_s, pr_m, i);
-            double disc = gx_col_get_nt<double>(di_s, di_m, i);
-            atomicAdd(&tagg[slot].sum, price * (1.0 - disc));
-            atomicAdd(&tagg[slot].cnt, 1.0);
-            local_hits++;
-        }
-    }
-    else if constexpr (B == -4)
-    {
-        /* WAVE-batched: each BLOCK window covers blockDim.x*4 consecutive
-         * rows; lane handles rows {w + tid + b*blockDim.x} — every load
-         * instruction still spans 64 consecutive rows (coalescing identical
-         * to B=1) while each lane keeps 4 independent chains in flight. */
-        const int WB = 4;
-        int64_t win = (int64_t) blockDim.x * WB;
-        int64_t w0 = blockIdx.x * win;
-        int64_t stride = (int64_t) gridDim.x * win;
-        for (; w0 + win <= lk_m.nrows; w0 += stride)
-        {
-            int32_t ship[WB];
-            int64_t key[WB];
-            int64_t r[WB];
-#pragma unroll
-            for (int b = 0; b < WB; b++)
-            {
-                r[b] = w0 + threadIdx.x + (int64_t) b * blockDim.x;
-                ship[b] = gx_col_get<int32_t>(sh_s, sh_m, r[b]);
-            }
-#pragma unroll
-            for (int b = 0; b < WB; b++)
-                key[b] = gx_col_get<int64_t>(lk_s, lk_m, r[b]);
-            bool pass[WB];
-            uint64_t slot[WB];
-            KT v[WB];
-#pragma unroll
-            for (int b = 0; b < WB; b++)
-            {
-                pass[b] = gx_cmp(fop, ship[b], flit);
-                slot[b] = pass[b] ? smap.slot0((uint64_t) key[b]) : 0;
-            }
-#pragma unroll
-            for (int b = 0; b < WB; b++)
-                v[b] = tkey[slot[b]];
-#pragma unroll
-            for (int b = 0; b < WB; b++)
-            {
-                if (!pass[b]) continue;
-                uint64_t res = resolve((uint64_t) key[b], slot[b], v[b]);
-                if (res != ~0ULL) hit(res, r[b]);
-            }
-        }
-        /* tail: rows the full windows missed */
-        int64_t done = (lk_m.nrows / win) * win;
-        for (int64_t i = done + blockIdx.x * (int64_t) blockDim.x + threadIdx.x;
-             i < lk_m.nrows; i += gridDim.x * (int64_t) blockDim.x)
-        {
-            if (!gx_cmp(fop, gx_col_get<int32_t>(sh_s, sh_m, i), flit)) continue;
-            uint64_t k = (uint64_t) gx_col_get<int64_t>(lk_s, lk_m, i);
-            uint64_t s0 = smap.slot0(k);
-            uint64_t res = resolve(k, s0, tkey[s0]);
-            if (res != ~0ULL) hit(res, i);
-        }
-    }
-    else if constexpr (B == -1)
-    {
-        /* block-chunked: each workgroup owns a contiguous row range, so with
-         * the interpolation slot layout its probes (and rev/cnt atomics)
-         * stay inside a tiny contiguous table window — L2-resident. */
-        int64_t chunk = (lk_m.nrows + gridDim.x - 1) / gridDim.x;
-        int64_t lo = blockIdx.x * chunk;
-        int64_t hi = min(lo + chunk, lk_m.nrows);
-        for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x)
-        {
-            if (!gx_cmp(fop, gx_col_get<int32_t>(sh_s, sh_m, i), flit)) continue;
-            uint64_t k = (uint64_t) gx_col_get<int64_t>(lk_s, lk_m, i);
-            uint64_t slot = smap.slot0(k);
-            uint64_t r = resolve(k, slot, tkey[slot]);
-            if (r != ~0ULL) hit(r, i);
-        }
-    }
-    else
-    {
-        int64_t base = (blockIdx.x * (int64_t) blockDim.x + threadIdx.x) * B;
-        int64_t stride = gridDim.x * (int64_t) blockDim.x * B;
-        for (; base + B <= lk_m.nrows; base += stride)
-        {
-            int32_t ship[B];
-            int64_t key[B];
-#pragma unroll
-            for (int b = 0; b < B; b++)
-                ship[b] = gx_col_get<int32_t>(sh_s, sh_m, base + b);
-#pragma unroll
-            for (int b = 0; b < B; b++)
-                key[b] = gx_col_get<int64_t>(lk_s, lk_m, base + b);
-            bool pass[B];
-            uint64_t slot[B];
-            KT v[B];
-#pragma unroll
-            for (int b = 0; b < B; b++)
-            {
-                pass[b] = gx_cmp(fop, ship[b], flit);
-                slot[b] = pass[b] ? smap.slot0((uint64_t) key[b]) : 0;
-            }
-#pragma unroll
-            for (int b = 0; b < B; b++)
-                v[b] = tkey[slot[b]];        /* filtered lanes hit slot 0 in L1 */
-#pragma unroll
-            for (int b = 0; b < B; b++)
-            {
-                if (!pass[b]) continue;
-                uint64_t r = resolve((uint64_t) key[b], slot[b], v[b]);
-                if (r != ~0ULL) hit(r, base + b);
-            }
-        }
-        /* tail rows (at most B-1 per thread, only near nrows) */
-        for (int64_t i = base; i < lk_m.nrows && i < base + B; i++)
-        {
-            if (!gx_cmp(fop, gx_col_get<int32_t>(sh_s, sh_m, i), flit)) continue;
-            uint64_t k = (uint64_t) gx_col_get<int64_t>(lk_s, lk_m, i);
-            uint64_t slot0 = smap.slot0(k);
-            uint64_t r = resolve(k, slot0, tkey[slot0]);
-            if (r != ~0ULL) hit(r, i);
-        }
+        if constexpr (VM)
+            if (gx_vm_hidden(vmap, i)) continue;
+        if (!gx_cmp(fop, gx_col_get<int32_t>(sh_s, sh_m, i), flit)) continue;
+        uint64_t k = (uint64_t) gx_col_get<int64_t>(lk_s, lk_m, i);
+        uint64_t slot = smap.slot0(k);
+        uint64_t r = d_table_find(tkey, tmask, slot, tkey[slot], k);
+        if (r != ~0ULL) hit(r, i);
+        else umiss(k, i);
     }
     gx_wave_count_add(hits, local_hits);
 }
-
 
 /* Fused Q3 probe+agg over an RLE-compressed l_orderkey column (the real
  * §8f-2 payoff): one workgroup per Dense/RLE block, ONE probe per RUN
@@ -1999,31 +1651,9 @@ __global__ void k_li_probe_agg_rle(const uint8_t *lk_s, const gx_blockref *dir,
             /* parallel: byte-popcount prefix of the bitmap, then fixed-stride
              * count lookup per ON bit */
             int nbytes = (phys + 7) >> 3;
-            int C = (nbytes + blockDim.x - 1) / blockDim.x;
-            int lo = threadIdx.x * C, hi = min(lo + C, nbytes);
-            uint32_t acc = 0;
-            for (int i = lo; i < hi; i++)
-            {
-                s_bytepop[i] = acc;
-                acc += __popc((unsigned) bmp[i]);
-            }
-            s_part[threadIdx.x] = acc;
-            __syncthreads();
-            if (threadIdx.x == 0)
-            {
-                uint32_t run = 0;
-                for (int t = 0; t < (int) blockDim.x; t++)
-                {
-                    uint32_t v = s_part[t];
-                    s_part[t] = run;
-                    run += v;
-                }
-            }
-            __syncthreads();
-            uint32_t base = s_part[threadIdx.x];
-            for (int i = lo; i < hi; i++)
-                s_bytepop[i] += base;
-            __syncthreads();
+            d_block_excl_scan(s_bytepop, nbytes, s_part, nullptr, [&](int i) {
+                return (uint32_t) __popc((unsigned) bmp[i]);
+            });
             for (int p = threadIdx.x; p < phys; p += blockDim.x)
             {
                 uint32_t reps = 1;
@@ -2070,33 +1700,9 @@ __global__ void k_li_probe_agg_rle(const uint8_t *lk_s, const gx_blockref *dir,
 
         /* ---- phase 2: exclusive scan of repeats → row starts ---- */
         {
-            int C = (phys + blockDim.x - 1) / blockDim.x;
-            int lo = threadIdx.x * C, hi = min(lo + C, phys);
-            uint32_t acc = 0;
-            for (int i = lo; i < hi; i++)
-            {
-                uint32_t v = s_starts[i];
-                s_starts[i] = acc;
-                acc += v;
-            }
-            s_part[threadIdx.x] = acc;
-            __syncthreads();
-            if (threadIdx.x == 0)
-            {
-                uint32_t run = 0;
-                for (int t = 0; t < (int) blockDim.x; t++)
-                {
-                    uint32_t v = s_part[t];
-                    s_part[t] = run;
-                    run += v;
-                }
-                s_starts[phys] = run;   /* == logical, checked below */
-            }
-            __syncthreads();
-            uint32_t base = s_part[threadIdx.x];
-            for (int i = lo; i < hi; i++)
-                s_starts[i] += base;
-            __syncthreads();
+            /* s_starts[phys] = the total (== logical, checked below) */
+            d_block_excl_scan(s_starts, phys, s_part, &s_starts[phys],
+                              [&](int i) { return s_starts[i]; });
             if (threadIdx.x == 0 && (int32_t) s_starts[phys] != logical)
                 atomicOr(err, 1);
         }
@@ -2107,15 +1713,7 @@ __global__ void k_li_probe_agg_rle(const uint8_t *lk_s, const gx_blockref *dir,
         {
             uint64_t k = (uint64_t) datum[p];
             uint64_t slot = smap.slot0(k);
-            bool found = false;
-            while (true)
-            {
-                KT v = tkey[slot];
-                if (v == (KT) 0) break;
-                if ((uint64_t) v == k) { found = true; break; }  /* zext */
-                slot = (slot + 1) & tmask;
-            }
-            if (!found) continue;
+            if (!d_table_find_from(tkey, tmask, slot, k)) continue;
             uint32_t rs = s_starts[p], re = s_starts[p + 1];
             for (uint32_t r = rs; r < re; r++)
             {
@@ -2167,26 +1765,11 @@ __global__ void k_li_probe_agg_num(const uint8_t *lk_s, gx_colmeta lk_m,
         if (!gx_cmp(fop, gx_col_get<int32_t>(sh_s, sh_m, i), flit)) continue;
         uint64_t k = (uint64_t) gx_col_get<int64_t>(lk_s, lk_m, i);
         uint64_t slot = smap.slot0(k);
-        bool found = false;
-        while (true)
-        {
-            KT v = tkey[slot];
-            if (v == (KT) 0) break;
-            if ((uint64_t) v == k) { found = true; break; }  /* zext */
-            slot = (slot + 1) & tmask;
-        }
-        if (!found)
+        if (!d_table_find_from(tkey, tmask, slot, k))
         {
             if constexpr (OUTER)
             {
-                uint64_t bk = k ^ (1ULL << 63);
-                uint64_t uslot = gx_hmix64(bk) & umask;
-                while (true)
-                {
-                    unsigned long long prev = atomicCAS(&ukey[uslot], 0ULL, bk);
-                    if (prev == 0ULL || prev == bk) break;
-                    uslot = (uslot + 1) & umask;
-                }
+                uint64_t uslot = d_unmatched_claim(ukey, umask, k);
                 int64_t pc = gx_col_get<int64_t>(pr_s, pr_m, i);
                 int64_t dc = gx_col_get<int64_t>(di_s, di_m, i);
                 unsigned long long uadd =
@@ -2392,6 +1975,65 @@ static ncclResult_t gx_nccl_recv_chunked(void *buf, size_t bytes, int peer,
     return ncclSuccess;
 }
 
+/* Send/receive layout of one Motion (pure host).  cnts_all is the
+ * all-gathered n×n count matrix, row r = rank r's per-destination histogram.
+ * Rank seg sends its own row (cnts_all[seg*n + i] rows to rank i) and
+ * receives its column (cnts_all[r*n + seg] rows from rank r); the offsets
+ * are the exclusive prefix sums, entry n the totals. */
+struct gx_mlayout {
+    std::vector<unsigned long long> scnt, soff, rcnt, roff;
+    unsigned long long send_n = 0, recv_n = 0;
+};
+
+static gx_mlayout m_exchange_layout(const unsigned long long *cnts_all, int n,
+                                    int seg)
+{
+    gx_mlayout L;
+    L.scnt.assign(n, 0); L.rcnt.assign(n, 0);
+    L.soff.assign(n + 1, 0); L.roff.assign(n + 1, 0);
+    for (int i = 0; i < n; i++) L.scnt[i] = cnts_all[(int64_t) seg * n + i];
+    for (int i = 0; i < n; i++) L.soff[i + 1] = L.soff[i] + L.scnt[i];
+    for (int r = 0; r < n; r++) L.rcnt[r] = cnts_all[(int64_t) r * n + seg];
+    for (int r = 0; r < n; r++) L.roff[r + 1] = L.roff[r] + L.rcnt[r];
+    L.send_n = L.soff[n];
+    L.recv_n = L.roff[n];
+    return L;
+}
+
+/* Payload exchange of one Motion on stream s: rank seg's rows for rank r
+ * sit at send + soff[r] rows, the rows from rank r land at recv + roff[r].
+ * The self-share bypasses RCCL entirely (a device copy is both faster and
+ * avoids self-send at GB sizes, alltoallv standard practice); all peer
+ * transfers go through the <=512 MiB chunk helpers in one grouped call. */
+static gx_status m_exchange_payload(gx_ctx *ctx, hipStream_t s,
+                                    const void *send_rows, void *recv_rows,
+                                    const gx_mlayout &L, size_t row_bytes)
+{
+    const uint8_t *send = (const uint8_t *) send_rows;
+    uint8_t *recv = (uint8_t *) recv_rows;
+    const int n = ctx->nsegs;
+    if (L.scnt[ctx->seg])
+        HIP_CHK(ctx, hipMemcpyAsync(recv + L.roff[ctx->seg] * row_bytes,
+                                    send + L.soff[ctx->seg] * row_bytes,
+                                    L.scnt[ctx->seg] * row_bytes,
+                                    hipMemcpyDeviceToDevice, s));
+    RCCL_CHK(ctx, ncclGroupStart());
+    for (int r = 0; r < n; r++)
+    {
+        if (r == ctx->seg) continue;
+        if (L.scnt[r])
+            RCCL_CHK(ctx, gx_nccl_send_chunked(send + L.soff[r] * row_bytes,
+                                               L.scnt[r] * row_bytes,
+                                               r, ctx->comm, s));
+        if (L.rcnt[r])
+            RCCL_CHK(ctx, gx_nccl_recv_chunked(recv + L.roff[r] * row_bytes,
+                                               L.rcnt[r] * row_bytes,
+                                               r, ctx->comm, s));
+    }
+    RCCL_CHK(ctx, ncclGroupEnd());
+    return GX_OK;
+}
+
 /* wave-aggregated per-destination counter claims: ONE atomic per wave per
  * destination instead of one per row (a single shared cursor serializes —
  * cdna_hip_programming.md G12; measured 68M same-address atomics ≈ 2 s). */
@@ -2576,7 +2218,6 @@ __global__ void k_gb_combine(const gx_kv_group *rows, int64_t n,
     }
 }
 
-/* filtered orders → per-destination histogram by route(o_custkey) (Motion 1) */
 /* Motion-1 histogram/emit carry an optional DESTINATION-AWARE bloom
  * prefilter (bloom_all = all ranks' dim blooms, all-gathered): an order
  * only ships when its custkey passes the bloom of the rank it routes to —
@@ -2585,6 +2226,29 @@ __global__ void k_gb_combine(const gx_kv_group *rows, int64_t n,
  * destination's exact set probe filters them); results stay bit-exact.
  * Disabled (nullptr) for anti joins, where non-membership is the keep
  * condition. */
+
+/* keep-and-route of mid row i, shared by the two Motion-1 passes: does the
+ * row pass visibility, the date filter and the destination's bloom, and
+ * which rank does route(fk) send it to?  The loaded date and fk come back
+ * in od / oc for the emit pass's output row (read only when kept). */
+__device__ __forceinline__ bool
+d_m1_keep_route(const uint8_t *od_s, const gx_colmeta &od_m,
+                const uint8_t *oc_s, const gx_colmeta &oc_m,
+                const uint8_t *vmap, int oop, int32_t olit, int nsegs,
+                const unsigned long long *bloom_all, uint64_t bwmask,
+                int64_t i, int32_t &d, int32_t &od, int64_t &oc)
+{
+    if (i >= od_m.nrows || gx_vm_hidden(vmap, i)) return false;
+    od = gx_col_get<int32_t>(od_s, od_m, i);
+    if (!gx_cmp(oop, od, olit)) return false;
+    oc = gx_col_get<int64_t>(oc_s, oc_m, i);
+    d = gx_route_i64(oc, nsegs);
+    return bloom_all == nullptr ||
+           d_bloom_test(bloom_all + (int64_t) d * (bwmask + 1), bwmask,
+                        (uint64_t) oc);
+}
+
+/* filtered orders → per-destination histogram by route(o_custkey) (Motion 1) */
 __global__ void k_ord_m1_hist(const uint8_t *od_s, gx_colmeta od_m,
                               const uint8_t *oc_s, gx_colmeta oc_m,
                               const uint8_t *vmap,
@@ -2599,17 +2263,10 @@ __global__ void k_ord_m1_hist(const uint8_t *od_s, gx_colmeta od_m,
     for (int64_t base = base0; base < od_m.nrows; base += stride)
     {
         int64_t i = base + lane;
-        bool keep = false;
-        int32_t d = 0;
-        if (i < od_m.nrows && !gx_vm_hidden(vmap, i) &&
-            gx_cmp(oop, gx_col_get<int32_t>(od_s, od_m, i), olit))
-        {
-            uint64_t ck = (uint64_t) gx_col_get<int64_t>(oc_s, oc_m, i);
-            d = gx_route_i64((int64_t) ck, nsegs);
-            keep = bloom_all == nullptr ||
-                   d_bloom_test(bloom_all + (int64_t) d * (bwmask + 1),
-                                bwmask, ck);
-        }
+        int32_t d = 0, od = 0;
+        int64_t oc = 0;
+        bool keep = d_m1_keep_route(od_s, od_m, oc_s, oc_m, vmap, oop, olit,
+                                    nsegs, bloom_all, bwmask, i, d, od, oc);
         for (int dd = 0; dd < nsegs; dd++)
         {
             unsigned long long m = __ballot(keep && d == dd);
@@ -2636,21 +2293,10 @@ __global__ void k_ord_m1_emit(const uint8_t *ok_s, gx_colmeta ok_m,
     for (int64_t base = base0; base < od_m.nrows; base += stride)
     {
         int64_t i = base + lane;
-        bool keep = false;
         int32_t d = 0, od = 0;
         int64_t oc = 0;
-        if (i < od_m.nrows && !gx_vm_hidden(vmap, i))
-        {
-            od = gx_col_get<int32_t>(od_s, od_m, i);
-            if (gx_cmp(oop, od, olit))
-            {
-                oc = gx_col_get<int64_t>(oc_s, oc_m, i);
-                d = gx_route_i64(oc, nsegs);
-                keep = bloom_all == nullptr ||
-                       d_bloom_test(bloom_all + (int64_t) d * (bwmask + 1),
-                                    bwmask, (uint64_t) oc);
-            }
-        }
+        bool keep = d_m1_keep_route(od_s, od_m, oc_s, oc_m, vmap, oop, olit,
+                                    nsegs, bloom_all, bwmask, i, d, od, oc);
         for (int dd = 0; dd < nsegs; dd++)
         {
             unsigned long long w;
@@ -2667,6 +2313,24 @@ __global__ void k_ord_m1_emit(const uint8_t *ok_s, gx_colmeta ok_m,
     }
 }
 
+/* keep-and-route of received row i, shared by the two Motion-2 passes: is
+ * its fk in the local dim set (semi) or not (ANTI), and which rank does
+ * route(mid key) send it to? */
+template <typename KS, bool ANTI>
+__device__ __forceinline__ bool
+d_m2_keep_route(const gx_ord_row *rows, int64_t n,
+                const KS *cset, uint64_t cmask,
+                const unsigned long long *bloom, uint64_t bwmask,
+                int nsegs, int64_t i, int32_t &d)
+{
+    if (i >= n) return false;
+    bool in_set = d_bloom_test(bloom, bwmask, (uint64_t) rows[i].ocust) &&
+                  d_set_contains(cset, cmask, (uint64_t) rows[i].ocust);
+    if (in_set == ANTI) return false;
+    d = gx_route_i64(rows[i].okey, nsegs);
+    return true;
+}
+
 /* received orders rows: probe local customer set, histogram by route(okey) */
 template <typename KS, bool ANTI = false>
 __global__ void k_qual_hist(const gx_ord_row *rows, int64_t n,
@@ -2680,19 +2344,9 @@ __global__ void k_qual_hist(const gx_ord_row *rows, int64_t n,
     for (int64_t base = base0; base < n; base += stride)
     {
         int64_t i = base + lane;
-        bool keep = false;
         int32_t d = 0;
-        if (i < n)
-        {
-            bool in_set =
-                d_bloom_test(bloom, bwmask, (uint64_t) rows[i].ocust) &&
-                d_set_contains(cset, cmask, (uint64_t) rows[i].ocust);
-            if (in_set != ANTI)
-            {
-                d = gx_route_i64(rows[i].okey, nsegs);
-                keep = true;
-            }
-        }
+        bool keep = d_m2_keep_route<KS, ANTI>(rows, n, cset, cmask, bloom,
+                                              bwmask, nsegs, i, d);
         for (int dd = 0; dd < nsegs; dd++)
         {
             unsigned long long m = __ballot(keep && d == dd);
@@ -2715,19 +2369,9 @@ __global__ void k_qual_emit(const gx_ord_row *rows, int64_t n,
     for (int64_t base = base0; base < n; base += stride)
     {
         int64_t i = base + lane;
-        bool keep = false;
         int32_t d = 0;
-        if (i < n)
-        {
-            bool in_set =
-                d_bloom_test(bloom, bwmask, (uint64_t) rows[i].ocust) &&
-                d_set_contains(cset, cmask, (uint64_t) rows[i].ocust);
-            if (in_set != ANTI)
-            {
-                d = gx_route_i64(rows[i].okey, nsegs);
-                keep = true;
-            }
-        }
+        bool keep = d_m2_keep_route<KS, ANTI>(rows, n, cset, cmask, bloom,
+                                              bwmask, nsegs, i, d);
         for (int dd = 0; dd < nsegs; dd++)
         {
             unsigned long long w;
@@ -2743,8 +2387,6 @@ __global__ void k_qual_emit(const gx_ord_row *rows, int64_t n,
     }
 }
 
-/* min/max key stats over received qualifying orders (sizes the motion
- * path's table layout exactly like the local path's counting pass) */
 /* min/max over an i64 column (sizing bound for the LEFT-OUTER unmatched
  * table: distinct keys <= min(nrows, range)) */
 __global__ void k_col_minmax(const uint8_t *col_s, gx_colmeta m,
@@ -2760,18 +2402,7 @@ __global__ void k_col_minmax(const uint8_t *col_s, gx_colmeta m,
         if (k > kmax) kmax = k;
         if (k < kmin) kmin = k;
     }
-    for (int o = 32; o; o >>= 1)
-    {
-        unsigned long long v = __shfl_down(kmax, o, 64);
-        if (v > kmax) kmax = v;
-        unsigned long long w = __shfl_down(kmin, o, 64);
-        if (w < kmin) kmin = w;
-    }
-    if ((threadIdx.x & 63) == 0)
-    {
-        atomicMax(maxkey, kmax);
-        atomicMin(minkey, kmin);
-    }
+    d_wave_minmax_commit<false>(kmax, kmin, maxkey, minkey);
 }
 
 /* LEFT-OUTER prepare check: count the non-NULL rows of an i64 key column
@@ -2797,6 +2428,8 @@ __global__ void k_col_count_reserved(const uint8_t *col_s, gx_colmeta m,
     gx_wave_count_add(&counts[1], nmin);
 }
 
+/* min/max key stats over received qualifying orders (sizes the motion
+ * path's table layout exactly like the local path's counting pass) */
 __global__ void k_rows_minmax(const gx_qual_row *rows, int64_t n,
                               unsigned long long *maxkey,
                               unsigned long long *minkey)
@@ -2810,33 +2443,16 @@ __global__ void k_rows_minmax(const gx_qual_row *rows, int64_t n,
         if (k > kmax) kmax = k;
         if (k < kmin) kmin = k;
     }
-    for (int o = 32; o; o >>= 1)
-    {
-        unsigned long long v = __shfl_down(kmax, o, 64);
-        if (v > kmax) kmax = v;
-        unsigned long long w = __shfl_down(kmin, o, 64);
-        if (w < kmin) kmin = w;
-    }
-    if ((threadIdx.x & 63) == 0)
-    {
-        if (kmax) atomicMax(maxkey, kmax);
-        if (kmin != ~0ULL) atomicMin(minkey, kmin);
-    }
+    d_wave_minmax_commit(kmax, kmin, maxkey, minkey);
 }
 
 /* received qualifying orders → build the join/agg table */
-/* dn (optional, device): the count actually emitted by a producer kernel —
- * authoritative over n when the two could diverge (e.g. GX_ORDERS_TWOPASS,
- * where n is the prepare-time capacity; inserting up to capacity would read
- * uninitialized rows if the emit ever fell short) */
 template <typename KT>
 __global__ void k_build_from_rows(const gx_qual_row *rows, int64_t n,
-                                  const unsigned long long *dn,
                                   KT *tkey,
                                   gx_attrpair *tattr, gx_aggslot *tagg,
                                   gx_slotmap smap)
 {
-    if (dn) n = min(n, (int64_t) *dn);
     int64_t i = blockIdx.x * (int64_t) blockDim.x + threadIdx.x;
     int64_t stride = gridDim.x * (int64_t) blockDim.x;
     uint64_t tmask = smap.mask;
@@ -2855,68 +2471,6 @@ __global__ void k_build_from_rows(const gx_qual_row *rows, int64_t n,
             if (prev == (KT) k) break;
             slot = (slot + 1) & tmask;
         }
-    }
-}
-
-/* two-pass orders build, pass 1 (GX_ORDERS_TWOPASS experiment): the
- * filter scan is kept HOMOGENEOUS (no table CAS in flight) and emits
- * qualifying orders compactly with per-BLOCK two-pass compaction (count,
- * LDS scan, ONE cursor atomic per block, then re-filter + write — the
- * block's range stays L2-resident between passes).  Pass 2 is the
- * existing k_build_from_rows insert. */
-template <typename KS, bool ANTI = false>
-__global__ void k_orders_emitq(const uint8_t *ok_s, gx_colmeta ok_m,
-                               const uint8_t *oc_s, gx_colmeta oc_m,
-                               const uint8_t *od_s, gx_colmeta od_m,
-                               const uint8_t *op_s, gx_colmeta op_m,
-                               const uint8_t *vmap, int oop, int32_t olit,
-                               const KS *cset, uint64_t cmask,
-                               const unsigned long long *bloom, uint64_t bwmask,
-                               gx_qual_row *outq, unsigned long long *cursor)
-{
-    __shared__ unsigned int scan[256];
-    __shared__ unsigned long long sbase;
-    int64_t range = (ok_m.nrows + gridDim.x - 1) / gridDim.x;
-    int64_t lo = blockIdx.x * range;
-    int64_t hi = min(lo + range, ok_m.nrows);
-    if (lo >= hi) return;
-
-    auto keep_row = [&](int64_t i) -> bool {
-        if (gx_vm_hidden(vmap, i)) return false;
-        int32_t od = gx_col_get<int32_t>(od_s, od_m, i);
-        if (!gx_cmp(oop, od, olit)) return false;
-        uint64_t ck = (uint64_t) gx_col_get<int64_t>(oc_s, oc_m, i);
-        bool in_set = d_bloom_test(bloom, bwmask, ck) &&
-                      d_set_contains(cset, cmask, ck);
-        return in_set != ANTI;
-    };
-
-    unsigned int mine = 0;
-    for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x)
-        if (keep_row(i)) mine++;
-    scan[threadIdx.x] = mine;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1)
-    {
-        unsigned int v = (threadIdx.x >= (unsigned) o) ? scan[threadIdx.x - o] : 0;
-        __syncthreads();
-        scan[threadIdx.x] += v;
-        __syncthreads();
-    }
-    if (threadIdx.x == blockDim.x - 1)
-        sbase = atomicAdd(cursor, (unsigned long long) scan[255]);
-    __syncthreads();
-    unsigned long long w = sbase + scan[threadIdx.x] - mine;
-
-    for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x)
-    {
-        if (!keep_row(i)) continue;
-        gx_qual_row r;
-        r.okey = gx_col_get<int64_t>(ok_s, ok_m, i);
-        r.odate = gx_col_get<int32_t>(od_s, od_m, i);
-        r.oprio = gx_col_get<int32_t>(op_s, op_m, i);
-        outq[w] = r;
-        w++;
     }
 }
 
@@ -4724,12 +4278,8 @@ extern "C" gx_status gx_groupby_dist(gx_ctx *ctx, const gx_table *t,
     HIP_CHK(ctx, hipMemcpyAsync(&herr, T.errb.p, 4, hipMemcpyDeviceToHost, s));
     HIP_CHK(ctx, hipStreamSynchronize(s));
     HIP_CHK(ctx, hipGetLastError());
-    std::vector<unsigned long long> h(n), off(n + 1, 0), rcv(n), roff(n + 1, 0);
-    for (int i = 0; i < n; i++) h[i] = cnts_all[(size_t) ctx->seg * n + i];
-    for (int i = 0; i < n; i++) off[i + 1] = off[i] + h[i];
-    for (int r = 0; r < n; r++) rcv[r] = cnts_all[(size_t) r * n + ctx->seg];
-    for (int r = 0; r < n; r++) roff[r + 1] = roff[r] + rcv[r];
-    unsigned long long send_n = off[n], recv_n = roff[n];
+    const gx_mlayout L = m_exchange_layout(cnts_all.data(), n, ctx->seg);
+    unsigned long long send_n = L.send_n, recv_n = L.recv_n;
     if ((int64_t) send_n > T.cap + 1)
     { set_err(ctx, "groupby_dist: partition overflow%s", ""); return GX_ERR_INVALID; }
     st = hbm_budget_check(ctx, (send_n + recv_n) * sizeof(gx_kv_group) + 64,
@@ -4739,31 +4289,14 @@ extern "C" gx_status gx_groupby_dist(gx_ctx *ctx, const gx_table *t,
     HIP_CHK(ctx, send_b.alloc(send_n * sizeof(gx_kv_group)));
     HIP_CHK(ctx, recv_b.alloc(recv_n * sizeof(gx_kv_group)));
     gx_kv_group *send = send_b.as<gx_kv_group>(), *recv = recv_b.as<gx_kv_group>();
-    HIP_CHK(ctx, hipMemcpyAsync(cur_b.p, off.data(), n * 8, hipMemcpyHostToDevice, s));
+    HIP_CHK(ctx, hipMemcpyAsync(cur_b.p, L.soff.data(), n * 8, hipMemcpyHostToDevice, s));
     HIP_CHK(ctx, hipEventRecord(ev[3], s));
     gb_part_emit(ctx, T, n, cur_b.as<unsigned long long>(), send);
     HIP_CHK(ctx, hipEventRecord(ev[4], s));
 
-    /* stage 3: exchange.  The self-share bypasses RCCL (device copy); peer
-     * transfers go through the <=512 MiB chunk helpers, one grouped call. */
-    if (h[ctx->seg])
-        HIP_CHK(ctx, hipMemcpyAsync(recv + roff[ctx->seg], send + off[ctx->seg],
-                                    h[ctx->seg] * sizeof(gx_kv_group),
-                                    hipMemcpyDeviceToDevice, s));
-    RCCL_CHK(ctx, ncclGroupStart());
-    for (int r = 0; r < n; r++)
-    {
-        if (r == ctx->seg) continue;
-        if (h[r])
-            RCCL_CHK(ctx, gx_nccl_send_chunked(send + off[r],
-                                               h[r] * sizeof(gx_kv_group),
-                                               r, ctx->comm, s));
-        if (rcv[r])
-            RCCL_CHK(ctx, gx_nccl_recv_chunked(recv + roff[r],
-                                               rcv[r] * sizeof(gx_kv_group),
-                                               r, ctx->comm, s));
-    }
-    RCCL_CHK(ctx, ncclGroupEnd());
+    /* stage 3: exchange */
+    st = m_exchange_payload(ctx, s, send, recv, L, sizeof(gx_kv_group));
+    if (st != GX_OK) return st;
     HIP_CHK(ctx, hipEventRecord(ev[5], s));
     /* a rejected key is reported only now, after this rank's sends and
      * receives are enqueued, so the peers' matching calls still complete */
@@ -5408,6 +4941,58 @@ static gx_status hbm_budget_check(gx_ctx *ctx, uint64_t want, const char *what)
     return GX_OK;
 }
 
+/* The customer scans, as the Q3 run and the test entry points launch them.
+ * dmask != nullptr selects the flat-mask row predicate, otherwise the int8
+ * compare <op, literal> on column cm. */
+template <typename F>
+static inline void by_dim_pred(const uint8_t *dmask, const gx_col &cm,
+                               int32_t op, int64_t literal, F &&f)
+{
+    if (dmask) f(gx_dim_pred_mask{dmask});
+    else f(gx_dim_pred_cmp{cm.dstream, cm.m, op, (int8_t) literal});
+}
+
+static void dim_launch_count(hipStream_t s, const gx_col &ck,
+                             const uint8_t *dmask, const gx_col &cm,
+                             int32_t op, int64_t literal, const uint8_t *cvm,
+                             unsigned long long *count,
+                             unsigned long long *maxkey,
+                             unsigned long long *minkey)
+{
+    by_dim_pred(dmask, cm, op, literal, [&](auto pred) {
+        hipLaunchKernelGGL(k_cust_count<decltype(pred)>,
+                           dim3(GRID), dim3(TPB), 0, s,
+                           ck.dstream, ck.m, pred, cvm, count, maxkey, minkey);
+    });
+}
+
+/* bits != nullptr fills the bitmap (no key set: one set-width instantiation),
+ * otherwise bloom + the cset_width-byte key set */
+static void dim_launch_build(hipStream_t s, const gx_col &ck,
+                             const uint8_t *dmask, const gx_col &cm,
+                             int32_t op, int64_t literal, const uint8_t *cvm,
+                             void *cset, int cset_width, uint64_t cmask,
+                             unsigned long long *bloom, uint64_t bwmask,
+                             unsigned long long *bits, uint64_t kmin,
+                             uint64_t range)
+{
+    by_dim_pred(dmask, cm, op, literal, [&](auto pred) {
+        auto go = [&](auto *cs, auto bmode) {
+            hipLaunchKernelGGL((k_cust_build<std::decay_t<decltype(*cs)>,
+                                             decltype(bmode)::value,
+                                             decltype(pred)>),
+                               dim3(GRID), dim3(TPB), 0, s,
+                               ck.dstream, ck.m, pred, cvm, cs, cmask,
+                               bloom, bwmask, bits, kmin, range);
+        };
+        if (bits)
+            go((unsigned int *) nullptr, std::true_type{});
+        else
+            by_width(cset_width, cset,
+                     [&](auto *cs) { go(cs, std::false_type{}); });
+    });
+}
+
 /* stage 1 of every run (and once at sizing): clear and fill the dimension
  * membership structure the caller's path reads — the bitmap, or set+bloom.
  * Only that one is touched; the other keeps whatever it held. */
@@ -5427,29 +5012,10 @@ static gx_status q3_build_dim(gx_q3 *q, bool bitmap)
         HIP_CHK(ctx, hipMemsetAsync(q->cset, 0, (q->cmask + 1) * q->cset_width, s));
         HIP_CHK(ctx, hipMemsetAsync(q->bloom, 0, (q->bwmask + 1) * 8, s));
     }
-    auto launch_cb = [&](auto *cs, auto bmode) {
-        using KS = std::decay_t<decltype(*cs)>;
-        constexpr bool BM = decltype(bmode)::value;
-        if (D.dim_text_len > 0)
-            hipLaunchKernelGGL((k_cust_build_mask<KS, BM>),
-                               dim3(GRID), dim3(TPB), 0, s,
-                               ck.dstream, ck.m, q->dmask, cvm, cs, q->cmask,
-                               q->bloom, q->bwmask,
-                               q->dbits, q->dim_kmin, q->dim_range);
-        else
-            hipLaunchKernelGGL((k_cust_build<KS, BM>),
-                               dim3(GRID), dim3(TPB), 0, s,
-                               ck.dstream, ck.m, cm.dstream, cm.m, cvm,
-                               D.dim_filter.op, (int8_t) D.dim_filter.literal,
-                               cs, q->cmask, q->bloom, q->bwmask,
-                               q->dbits, q->dim_kmin, q->dim_range);
-    };
-    if (bitmap)
-        launch_cb((unsigned int *) nullptr, std::true_type{});
-    else if (q->cset_width == 4)
-        launch_cb((unsigned int *) q->cset, std::false_type{});
-    else
-        launch_cb((unsigned long long *) q->cset, std::false_type{});
+    dim_launch_build(s, ck, D.dim_text_len > 0 ? q->dmask : nullptr, cm,
+                     D.dim_filter.op, D.dim_filter.literal, cvm,
+                     q->cset, q->cset_width, q->cmask, q->bloom, q->bwmask,
+                     bitmap ? q->dbits : nullptr, q->dim_kmin, q->dim_range);
     return GX_OK;
 }
 
@@ -5466,6 +5032,31 @@ static uint64_t q3_unmatched_bound(int64_t nrows, uint64_t lmin, uint64_t lmax)
     uint64_t span = lmax - lmin + 1;
     if (lmax < lmin || span == 0) span = (uint64_t) nrows;
     return std::min<uint64_t>((uint64_t) nrows, span) + 1;
+}
+
+/* (Re)allocate the join/agg table of tslots slots of q->key_width-byte keys
+ * and the result arrays for qual groups plus the LEFT-OUTER bound, freeing
+ * what was there.  Sizing calls it once; the Motion path again whenever a
+ * run's exchanged counts outgrow the cached table. */
+static gx_status q3_alloc_table(gx_q3 *q, uint64_t tslots, int64_t qual)
+{
+    gx_ctx *ctx = q->ctx;
+    auto fr = [](auto *&p) { if (p) { (void) hipFree(p); p = nullptr; } };
+    fr(q->tkey); fr(q->tattr); fr(q->tagg);
+    fr(q->r_okey); fr(q->r_odate); fr(q->r_oprio); fr(q->r_rev); fr(q->r_cnt);
+    fr(q->r_flags);
+    HIP_CHK(ctx, hipMalloc(&q->tkey, tslots * q->key_width));
+    HIP_CHK(ctx, hipMalloc(&q->tattr, tslots * sizeof(gx_attrpair)));
+    HIP_CHK(ctx, hipMalloc(&q->tagg, tslots * sizeof(gx_aggslot)));
+    q->rescap = std::max<int64_t>(qual + q->u_cap, 1);
+    HIP_CHK(ctx, hipMalloc(&q->r_okey, q->rescap * 8));
+    HIP_CHK(ctx, hipMalloc(&q->r_odate, q->rescap * 4));
+    HIP_CHK(ctx, hipMalloc(&q->r_oprio, q->rescap * 4));
+    HIP_CHK(ctx, hipMalloc(&q->r_rev, q->rescap * 8));
+    HIP_CHK(ctx, hipMalloc(&q->r_cnt, q->rescap * 8));
+    HIP_CHK(ctx, hipMalloc(&q->r_flags, q->rescap));
+    q->tmask = tslots - 1;
+    return GX_OK;
 }
 
 /* first run only: size the dimension membership structures and join/agg
@@ -5492,17 +5083,9 @@ static gx_status q3_size_and_alloc(gx_q3 *q)
     HIP_CHK(ctx, hipMemsetAsync(q->dcount, 0, 8, s));
     HIP_CHK(ctx, hipMemsetAsync(q->dhits, 0, 8, s));   /* borrowed for max custkey */
     HIP_CHK(ctx, hipMemsetAsync(q->dmin, 0xFF, 8, s)); /* borrowed for min custkey */
-    if (D.dim_text_len > 0)
-        hipLaunchKernelGGL(k_cust_count_mask, dim3(GRID), dim3(TPB), 0, s,
-                           ckk.dstream, ckk.m,
-                           q->dmask, cvm,
-                           q->dcount, q->dhits, q->dmin);
-    else
-        hipLaunchKernelGGL(k_cust_count, dim3(GRID), dim3(TPB), 0, s,
-                           ckk.dstream, ckk.m,
-                           cm.dstream, cm.m, cvm, D.dim_filter.op,
-                           (int8_t) D.dim_filter.literal, q->dcount, q->dhits,
-                           q->dmin);
+    dim_launch_count(s, ckk, D.dim_text_len > 0 ? q->dmask : nullptr, cm,
+                     D.dim_filter.op, D.dim_filter.literal, cvm,
+                     q->dcount, q->dhits, q->dmin);
     unsigned long long n_building = 0, cmax = 0, cmin = 0;
     HIP_CHK(ctx, hipMemcpyAsync(&n_building, q->dcount, 8, hipMemcpyDeviceToHost, s));
     HIP_CHK(ctx, hipMemcpyAsync(&cmax, q->dhits, 8, hipMemcpyDeviceToHost, s));
@@ -5651,39 +5234,28 @@ static gx_status q3_size_and_alloc(gx_q3 *q)
         HIP_CHK(ctx, hipMemsetAsync(q->dhits, 0, 8, s));   /* borrowed for maxkey */
         HIP_CHK(ctx, hipMemsetAsync(q->dmin, 0xFF, 8, s)); /* minkey = ~0 */
         gx_dimbits dbm = {q->dbits, q->dim_kmin, q->dim_range};
-        auto launch_ocount = [&](auto *cs, auto anti, auto bmode) {
-            hipLaunchKernelGGL((k_orders_count<std::decay_t<decltype(*cs)>,
-                                               decltype(anti)::value,
-                                               decltype(bmode)::value>),
-                               dim3(GRID), dim3(TPB), 0, s,
-                               q3_col(q, q->ord, D.mid_key_col).dstream,
-                               q3_col(q, q->ord, D.mid_key_col).m,
-                               od.dstream, od.m, oc.dstream, oc.m,
-                               ovm,
-                               D.mid_filter.op, (int32_t) D.mid_filter.literal,
-                               cs, q->cmask,
-                               q->bloom, q->bwmask, dbm, q->dcount,
-                               q->dhits, q->dmin);
+        auto launch_ocount = [&](auto *cs, auto bmode) {
+            by_flag(D.dim_join != 0, [&](auto anti) {
+                hipLaunchKernelGGL((k_orders_count<std::decay_t<decltype(*cs)>,
+                                                   decltype(anti)::value,
+                                                   decltype(bmode)::value>),
+                                   dim3(GRID), dim3(TPB), 0, s,
+                                   q3_col(q, q->ord, D.mid_key_col).dstream,
+                                   q3_col(q, q->ord, D.mid_key_col).m,
+                                   od.dstream, od.m, oc.dstream, oc.m,
+                                   ovm,
+                                   D.mid_filter.op, (int32_t) D.mid_filter.literal,
+                                   cs, q->cmask,
+                                   q->bloom, q->bwmask, dbm, q->dcount,
+                                   q->dhits, q->dmin);
+            });
         };
-        bool anti = D.dim_join != 0;
-        if (q->dim_bitmap && anti)
-            launch_ocount((const unsigned int *) nullptr, std::true_type{},
-                          std::true_type{});
-        else if (q->dim_bitmap)
-            launch_ocount((const unsigned int *) nullptr, std::false_type{},
-                          std::true_type{});
-        else if (q->cset_width == 4 && anti)
-            launch_ocount((const unsigned int *) q->cset, std::true_type{},
-                          std::false_type{});
-        else if (q->cset_width == 4)
-            launch_ocount((const unsigned int *) q->cset, std::false_type{},
-                          std::false_type{});
-        else if (anti)
-            launch_ocount((const unsigned long long *) q->cset, std::true_type{},
-                          std::false_type{});
+        if (q->dim_bitmap)  /* no key set: one set-width instantiation */
+            launch_ocount((const unsigned int *) nullptr, std::true_type{});
         else
-            launch_ocount((const unsigned long long *) q->cset, std::false_type{},
-                          std::false_type{});
+            by_width(q->cset_width, (const void *) q->cset, [&](auto *cs) {
+                launch_ocount(cs, std::false_type{});
+            });
         unsigned long long nq = 0, kmax = 0, kmin = 0;
         HIP_CHK(ctx, hipMemcpyAsync(&nq, q->dcount, 8, hipMemcpyDeviceToHost, s));
         HIP_CHK(ctx, hipMemcpyAsync(&kmax, q->dhits, 8, hipMemcpyDeviceToHost, s));
@@ -5716,11 +5288,10 @@ static gx_status q3_size_and_alloc(gx_q3 *q)
                 "join/agg table");
             if (st != GX_OK) return st;
         }
-        q->tmask = tslots - 1;
         /* order-preserving interpolation layout when the qualifying keys'
          * density over [kmin,kmax] is high enough that runs stay short;
          * otherwise multiplicative hashing */
-        q->smap.mask = q->tmask;
+        q->smap.mask = tslots - 1;
         q->smap.kmin = (int64_t) kmin;
         q->smap.scale = -1.0;
         if (qual > 0 && kmax >= kmin)
@@ -5729,16 +5300,10 @@ static gx_status q3_size_and_alloc(gx_q3 *q)
             if ((double) qual >= range / 64.0)
                 q->smap.scale = (double) tslots / range;
         }
-        HIP_CHK(ctx, hipMalloc(&q->tkey, tslots * q->key_width));
-        HIP_CHK(ctx, hipMalloc(&q->tattr, tslots * sizeof(gx_attrpair)));
-        HIP_CHK(ctx, hipMalloc(&q->tagg, tslots * sizeof(gx_aggslot)));
-        q->rescap = std::max<int64_t>(qual + q->u_cap, 1);
-        HIP_CHK(ctx, hipMalloc(&q->r_okey, q->rescap * 8));
-        HIP_CHK(ctx, hipMalloc(&q->r_odate, q->rescap * 4));
-        HIP_CHK(ctx, hipMalloc(&q->r_oprio, q->rescap * 4));
-        HIP_CHK(ctx, hipMalloc(&q->r_rev, q->rescap * 8));
-        HIP_CHK(ctx, hipMalloc(&q->r_cnt, q->rescap * 8));
-        HIP_CHK(ctx, hipMalloc(&q->r_flags, q->rescap));
+        {
+            gx_status st = q3_alloc_table(q, tslots, qual);
+            if (st != GX_OK) return st;
+        }
     }
     HIP_CHK(ctx, hipStreamSynchronize(s));
     q->sized = true;
@@ -5794,21 +5359,14 @@ static void m2_launch_hist(hipStream_t s, const gx_ord_row *recv, int64_t n,
                            const unsigned long long *bloom, uint64_t bwmask,
                            int dim_join, int nsegs, unsigned long long *dhist)
 {
-    auto go = [&](auto *cs, auto anti) {
-        hipLaunchKernelGGL((k_qual_hist<std::decay_t<decltype(*cs)>,
-                                        decltype(anti)::value>),
-                           dim3(GRID), dim3(TPB), 0, s,
-                           recv, n, cs, cmask, bloom, bwmask, nsegs, dhist);
-    };
-    bool anti_join = dim_join != 0;
-    if (cset_width == 4 && anti_join)
-        go((const unsigned int *) cset, std::true_type{});
-    else if (cset_width == 4)
-        go((const unsigned int *) cset, std::false_type{});
-    else if (anti_join)
-        go((const unsigned long long *) cset, std::true_type{});
-    else
-        go((const unsigned long long *) cset, std::false_type{});
+    by_width(cset_width, cset, [&](auto *cs) {
+        by_flag(dim_join != 0, [&](auto anti) {
+            hipLaunchKernelGGL((k_qual_hist<std::decay_t<decltype(*cs)>,
+                                            decltype(anti)::value>),
+                               dim3(GRID), dim3(TPB), 0, s,
+                               recv, n, cs, cmask, bloom, bwmask, nsegs, dhist);
+        });
+    });
 }
 
 static void m2_launch_emit(hipStream_t s, const gx_ord_row *recv, int64_t n,
@@ -5817,46 +5375,14 @@ static void m2_launch_emit(hipStream_t s, const gx_ord_row *recv, int64_t n,
                            int dim_join, int nsegs, unsigned long long *dcur,
                            gx_qual_row *send)
 {
-    auto go = [&](auto *cs, auto anti) {
-        hipLaunchKernelGGL((k_qual_emit<std::decay_t<decltype(*cs)>,
-                                        decltype(anti)::value>),
-                           dim3(GRID), dim3(TPB), 0, s,
-                           recv, n, cs, cmask, bloom, bwmask, nsegs, dcur, send);
-    };
-    bool anti_join = dim_join != 0;
-    if (cset_width == 4 && anti_join)
-        go((const unsigned int *) cset, std::true_type{});
-    else if (cset_width == 4)
-        go((const unsigned int *) cset, std::false_type{});
-    else if (anti_join)
-        go((const unsigned long long *) cset, std::true_type{});
-    else
-        go((const unsigned long long *) cset, std::false_type{});
-}
-
-/* Send/receive layout of one Motion (pure host).  cnts_all is the
- * all-gathered n×n count matrix, row r = rank r's per-destination histogram.
- * Rank seg sends its own row (cnts_all[seg*n + i] rows to rank i) and
- * receives its column (cnts_all[r*n + seg] rows from rank r); the offsets
- * are the exclusive prefix sums, entry n the totals. */
-struct gx_mlayout {
-    std::vector<unsigned long long> scnt, soff, rcnt, roff;
-    unsigned long long send_n = 0, recv_n = 0;
-};
-
-static gx_mlayout m_exchange_layout(const unsigned long long *cnts_all, int n,
-                                    int seg)
-{
-    gx_mlayout L;
-    L.scnt.assign(n, 0); L.rcnt.assign(n, 0);
-    L.soff.assign(n + 1, 0); L.roff.assign(n + 1, 0);
-    for (int i = 0; i < n; i++) L.scnt[i] = cnts_all[(int64_t) seg * n + i];
-    for (int i = 0; i < n; i++) L.soff[i + 1] = L.soff[i] + L.scnt[i];
-    for (int r = 0; r < n; r++) L.rcnt[r] = cnts_all[(int64_t) r * n + seg];
-    for (int r = 0; r < n; r++) L.roff[r + 1] = L.roff[r] + L.rcnt[r];
-    L.send_n = L.soff[n];
-    L.recv_n = L.roff[n];
-    return L;
+    by_width(cset_width, cset, [&](auto *cs) {
+        by_flag(dim_join != 0, [&](auto anti) {
+            hipLaunchKernelGGL((k_qual_emit<std::decay_t<decltype(*cs)>,
+                                            decltype(anti)::value>),
+                               dim3(GRID), dim3(TPB), 0, s,
+                               recv, n, cs, cmask, bloom, bwmask, nsegs, dcur, send);
+        });
+    });
 }
 
 /* Slot map of a join/agg table of `slots` slots over the received keys:
@@ -5904,118 +5430,44 @@ static gx_tbl_layout m3_table_layout(int64_t qual, unsigned long long kmin,
     return L;
 }
 
-/* Build the join/agg table from packed qualifying rows; dn (optional,
- * device) caps n (see k_build_from_rows). */
+/* Build the join/agg table from packed qualifying rows */
 static void m3_launch_build(hipStream_t s, const gx_qual_row *rows, int64_t n,
-                            const unsigned long long *dn, int key_width,
-                            void *tkey, gx_attrpair *tattr, gx_aggslot *tagg,
-                            gx_slotmap smap)
+                            int key_width, void *tkey, gx_attrpair *tattr,
+                            gx_aggslot *tagg, gx_slotmap smap)
 {
-    if (key_width == 4)
-        hipLaunchKernelGGL(k_build_from_rows<unsigned int>,
-                           dim3(GRID), dim3(TPB), 0, s, rows, n, dn,
-                           (unsigned int *) tkey, tattr, tagg, smap);
-    else
-        hipLaunchKernelGGL(k_build_from_rows<unsigned long long>,
-                           dim3(GRID), dim3(TPB), 0, s, rows, n, dn,
-                           (unsigned long long *) tkey, tattr, tagg, smap);
+    by_width(key_width, tkey, [&](auto *tk) {
+        hipLaunchKernelGGL(k_build_from_rows<std::decay_t<decltype(*tk)>>,
+                           dim3(GRID), dim3(TPB), 0, s, rows, n,
+                           tk, tattr, tagg, smap);
+    });
 }
 
-/* Stage 3, f64 measures over a plain fact key: probe + aggregate with the
- * variant GX_PROBE_VARIANT selects (0 = the tuned default; the others are
- * A/B experiments without visimap/outer support). */
-static gx_status q3_launch_probe(gx_ctx *ctx, hipStream_t s,
-                                 const gx_col &lk, const gx_col &lp,
-                                 const gx_col &ld, const gx_col &ls,
-                                 const uint8_t *lvm, int32_t fop, int32_t flit,
-                                 int key_width, const void *tkey,
-                                 gx_aggslot *tagg, gx_slotmap smap,
-                                 unsigned long long *dhits, bool outer,
-                                 unsigned long long *ukey, double *urev,
-                                 unsigned long long *ucnt_u, uint64_t umask)
+/* Stage 3, f64 measures over a plain fact key: probe + aggregate, compiled
+ * per key width x visimap x LEFT OUTER */
+static void q3_launch_probe(hipStream_t s,
+                            const gx_col &lk, const gx_col &lp,
+                            const gx_col &ld, const gx_col &ls,
+                            const uint8_t *lvm, int32_t fop, int32_t flit,
+                            int key_width, const void *tkey,
+                            gx_aggslot *tagg, gx_slotmap smap,
+                            unsigned long long *dhits, bool outer,
+                            unsigned long long *ukey, double *urev,
+                            unsigned long long *ucnt_u, uint64_t umask)
 {
-    const char *pv = getenv("GX_PROBE_VARIANT");
-    int variant = pv ? atoi(pv) : 0;
-    if (variant != 0 && (lvm || outer))
-    {
-        set_err(ctx, "visimap/extra quals/outer require the default probe variant%s", "");
-        return GX_ERR_INVALID;
-    }
-    const char *pg = getenv("GX_PROBE_GRID");
-    int pgrid = pg ? atoi(pg) : GRID;
-    const char *pt = getenv("GX_PROBE_TPB");
-    int ptpb = pt ? atoi(pt) : TPB;
-    auto launch = [&](auto kern, auto *keys) {
-        hipLaunchKernelGGL(kern, dim3(pgrid), dim3(ptpb), 0, s,
-                           lk.dstream, lk.m, lp.dstream, lp.m, ld.dstream, ld.m,
-                           ls.dstream, ls.m, lvm, fop, flit, keys,
-                           tagg, smap, dhits, ukey, urev, ucnt_u, umask);
-    };
-    if (key_width == 4)
-    {
-        auto *keys = (const unsigned int *) tkey;
-        switch (variant)
-        {
-            default:
-            case 0:
-                if (outer && lvm)
-                    launch((k_li_probe_agg_t<1, unsigned int, true, true>), keys);
-                else if (outer)
-                    launch((k_li_probe_agg_t<1, unsigned int, false, true>), keys);
-                else if (lvm)
-                    launch((k_li_probe_agg_t<1, unsigned int, true>), keys);
-                else
-                    launch(k_li_probe_agg_t<1, unsigned int>, keys);
-                break;
-            case 2: launch(k_li_probe_agg_t<4, unsigned int>, keys); break;
-            case 4: launch(k_li_probe_agg_t<2, unsigned int>, keys); break;
-            case 5: launch(k_li_probe_agg_t<8, unsigned int>, keys); break;
-            case 6: launch(k_li_probe_agg_t<-1, unsigned int>, keys); break;
-            case 7: launch(k_li_probe_agg_t<-4, unsigned int>, keys); break;
-            case 8: launch(k_li_probe_agg_t<-2, unsigned int>, keys); break;
-            case 9: launch(k_li_probe_agg_t<-5, unsigned int>, keys); break;
-            case 10: launch(k_li_probe_agg_t<-6, unsigned int>, keys); break;
-            case 11: launch(k_li_probe_agg_t<-9, unsigned int>, keys); break;
-            case 12: launch(k_li_probe_agg_t<-10, unsigned int>, keys); break;
-            case 13: launch(k_li_probe_agg_t<-11, unsigned int>, keys); break;
-            case 14: launch(k_li_probe_agg_t<-12, unsigned int>, keys); break;
-            case 15: launch(k_li_probe_agg_t<-13, unsigned int>, keys); break;
-            case 16: launch(k_li_probe_agg_t<-14, unsigned int>, keys); break;
-        }
-    }
-    else
-    {
-        auto *keys = (const unsigned long long *) tkey;
-        switch (variant)
-        {
-            default:
-            case 0:
-                if (outer && lvm)
-                    launch((k_li_probe_agg_t<1, unsigned long long, true, true>), keys);
-                else if (outer)
-                    launch((k_li_probe_agg_t<1, unsigned long long, false, true>), keys);
-                else if (lvm)
-                    launch((k_li_probe_agg_t<1, unsigned long long, true>), keys);
-                else
-                    launch(k_li_probe_agg_t<1, unsigned long long>, keys);
-                break;
-            case 2: launch(k_li_probe_agg_t<4, unsigned long long>, keys); break;
-            case 4: launch(k_li_probe_agg_t<2, unsigned long long>, keys); break;
-            case 5: launch(k_li_probe_agg_t<8, unsigned long long>, keys); break;
-            case 6: launch(k_li_probe_agg_t<-1, unsigned long long>, keys); break;
-            case 7: launch(k_li_probe_agg_t<-4, unsigned long long>, keys); break;
-            case 8: launch(k_li_probe_agg_t<-2, unsigned long long>, keys); break;
-            case 9: launch(k_li_probe_agg_t<-5, unsigned long long>, keys); break;
-            case 10: launch(k_li_probe_agg_t<-6, unsigned long long>, keys); break;
-            case 11: launch(k_li_probe_agg_t<-9, unsigned long long>, keys); break;
-            case 12: launch(k_li_probe_agg_t<-10, unsigned long long>, keys); break;
-            case 13: launch(k_li_probe_agg_t<-11, unsigned long long>, keys); break;
-            case 14: launch(k_li_probe_agg_t<-12, unsigned long long>, keys); break;
-            case 15: launch(k_li_probe_agg_t<-13, unsigned long long>, keys); break;
-            case 16: launch(k_li_probe_agg_t<-14, unsigned long long>, keys); break;
-        }
-    }
-    return GX_OK;
+    by_width(key_width, tkey, [&](auto *keys) {
+        by_flag(lvm != nullptr, [&](auto vm) {
+            by_flag(outer, [&](auto ou) {
+                hipLaunchKernelGGL((k_li_probe_agg_t<std::decay_t<decltype(*keys)>,
+                                                     decltype(vm)::value,
+                                                     decltype(ou)::value>),
+                                   dim3(GRID), dim3(TPB), 0, s,
+                                   lk.dstream, lk.m, lp.dstream, lp.m,
+                                   ld.dstream, ld.m, ls.dstream, ls.m, lvm,
+                                   fop, flit, keys, tagg, smap, dhits,
+                                   ukey, urev, ucnt_u, umask);
+            });
+        });
+    });
 }
 
 /* Stage 4: one block per fixed tile of the table, block-ordered extract */
@@ -6033,16 +5485,12 @@ static gx_status q3_launch_extract(gx_ctx *ctx, hipStream_t s, int key_width,
         set_err(ctx, "join/agg table too large for the extract grid%s", "");
         return GX_ERR_INVALID;
     }
-    if (key_width == 4)
-        hipLaunchKernelGGL(k_extract<unsigned int>, dim3((unsigned) etiles), dim3(TPB), 0, s,
-                           (const unsigned int *) tkey, tattr, tagg,
-                           tslots, numeric,
+    by_width(key_width, tkey, [&](auto *keys) {
+        hipLaunchKernelGGL(k_extract<std::decay_t<decltype(*keys)>>,
+                           dim3((unsigned) etiles), dim3(TPB), 0, s,
+                           keys, tattr, tagg, tslots, numeric,
                            r_okey, r_odate, r_oprio, r_rev, r_cnt, dcount);
-    else
-        hipLaunchKernelGGL(k_extract<unsigned long long>, dim3((unsigned) etiles), dim3(TPB), 0, s,
-                           (const unsigned long long *) tkey, tattr, tagg,
-                           tslots, numeric,
-                           r_okey, r_odate, r_oprio, r_rev, r_cnt, dcount);
+    });
     return GX_OK;
 }
 
@@ -6067,6 +5515,348 @@ extern "C" gx_status gx_q3_dim_mode(gx_q3 *q, int *mode)
     if (!q || !mode) return GX_ERR_INVALID;
     if (!q->ran) return GX_ERR_STATE;
     *mode = q->dim_mode;
+    return GX_OK;
+}
+
+/* the columns and effective visibility masks one Q3 run reads (extra-qual
+ * masks fold the visimap in) */
+struct q3_runcols {
+    const gx_col &ok, &oc, &od, &op;     /* mid: key, fk, filter, attr2 */
+    const gx_col &lk, &lp, &ld, &ls;     /* fact: key, a, b, filter */
+    const uint8_t *ovm, *lvm;
+};
+
+/* Stage 2, single segment: build the join/agg table straight from the mid
+ * table's columns (date filter + dim semi/anti join + insert in one pass) */
+static gx_status q3_orders_local(gx_q3 *q, const q3_runcols &C, bool use_bitmap)
+{
+    gx_ctx *ctx = q->ctx;
+    hipStream_t s = ctx->stream;
+    const gx_q3_desc &D = q->desc;
+    const gx_col &ok = C.ok, &oc = C.oc, &od = C.od, &op = C.op;
+    uint64_t tslots = q->tmask + 1;
+    /* keys only: agg/attr slots are initialised at claim (gx_aggslot) */
+    HIP_CHK(ctx, hipMemsetAsync(q->tkey, 0, tslots * q->key_width, s));
+    if (D.fact_join == 1)
+    {
+        HIP_CHK(ctx, hipMemsetAsync(q->ukey, 0, (q->umask + 1) * 8, s));
+        HIP_CHK(ctx, hipMemsetAsync(q->urev, 0, (q->umask + 1) * 8, s));
+        HIP_CHK(ctx, hipMemsetAsync(q->ucnt_u, 0, (q->umask + 1) * 8, s));
+    }
+    gx_dimbits dbm = {q->dbits, q->dim_kmin, q->dim_range};
+    auto launch_build = [&](auto *tk, auto *cs, auto bmode) {
+        by_flag(C.ovm != nullptr, [&](auto vm) {
+            by_flag(D.dim_join != 0, [&](auto anti) {
+                hipLaunchKernelGGL((k_orders_build<std::decay_t<decltype(*tk)>,
+                                                   std::decay_t<decltype(*cs)>,
+                                                   decltype(vm)::value,
+                                                   decltype(anti)::value,
+                                                   decltype(bmode)::value>),
+                                   dim3(ORDERS_GRID), dim3(TPB), 0, s,
+                                   ok.dstream, ok.m, oc.dstream, oc.m, od.dstream, od.m,
+                                   op.dstream, op.m, C.ovm, D.mid_filter.op,
+                                   (int32_t) D.mid_filter.literal, cs, q->cmask,
+                                   q->bloom, q->bwmask, dbm,
+                                   tk, q->tattr, q->tagg, q->smap);
+            });
+        });
+    };
+    by_width(q->key_width, q->tkey, [&](auto *tk) {
+        if (use_bitmap)     /* no key set: one set-width instantiation */
+            launch_build(tk, (const unsigned int *) nullptr, std::true_type{});
+        else
+            by_width(q->cset_width, (const void *) q->cset, [&](auto *cs) {
+                launch_build(tk, cs, std::false_type{});
+            });
+    });
+    return GX_OK;
+}
+
+/* Stage 2, nsegs > 1 (or GX_FORCE_MOTION): Motion 1 ships the filtered mid
+ * rows by route(fk), the local dim set filters them, Motion 2 ships the
+ * qualifying ones by route(mid key), and the join/agg table is built from
+ * what arrives.  dim_done: the dim build's completion on the primary stream.
+ * Ends in a host sync of the Motion stream. */
+static gx_status q3_orders_motion(gx_q3 *q, const q3_runcols &C,
+                                  hipEvent_t dim_done, int64_t *qual_out,
+                                  double *ms_motion)
+{
+    gx_ctx *ctx = q->ctx;
+    const gx_q3_desc &D = q->desc;
+    const gx_col &ok = C.ok, &oc = C.oc, &od = C.od, &op = C.op;
+    if (!ctx->comm) { set_err(ctx, "nsegs>1 but gx_comm_init not called%s", ""); return GX_ERR_STATE; }
+    int n = ctx->nsegs;
+    /* the exchange runs on stream2, concurrent with the dim-set build
+     * still in flight on the primary stream (they only meet at the
+     * local semijoin below, via a cross-stream event wait); the branch
+     * ends in a host sync, so stage 3 on the primary stream is ordered */
+    hipStream_t ms = ctx->stream2;
+    evholder mev0, mev1;
+    HIP_CHK(ctx, mev0.create()); HIP_CHK(ctx, mev1.create());
+    HIP_CHK(ctx, hipEventRecord(mev0, ms));
+
+    /* Motion 1: filtered orders by route(o_custkey).  Exchange buffers
+     * are cached in gx_q3 (grow-only) — per-step hipMalloc would
+     * dominate at high rank counts. */
+    auto grow = [&](auto *&p, uint64_t &cap, uint64_t want) -> gx_status {
+        if (want <= cap) return GX_OK;
+        if (p) (void) hipFree(p);
+        p = nullptr;
+        cap = 0;
+        hipError_t e = hipMalloc(&p, std::max<uint64_t>(want, 1) *
+                                      sizeof(**(&p)));
+        if (e != hipSuccess) return GX_ERR_OOM;
+        cap = want;
+        return GX_OK;
+    };
+    if (!q->m_hist)
+    {
+        HIP_CHK(ctx, hipMalloc(&q->m_hist, n * 8));
+        HIP_CHK(ctx, hipMalloc(&q->m_cur, n * 8));
+        HIP_CHK(ctx, hipMalloc(&q->m_cnts_mine, n * 8));
+        HIP_CHK(ctx, hipMalloc(&q->m_cnts_all, (int64_t) n * n * 8));
+    }
+    /* Motion-1 count exchange: the per-dest histogram goes straight
+     * into the all-gather, so ONE host sync yields both this rank's
+     * send layout (its own row) and every peer's counts (r2: the two
+     * separate count syncs were ~half the fixed motion latency) */
+    unsigned long long *dhist = q->m_hist;
+    /* destination-aware bloom prefilter (semi join only): all-gather
+     * every rank's dim bloom, then only ship orders whose fk passes
+     * the DESTINATION's bloom — the runtime filter pushed across the
+     * interconnect.  Requires the local dim build (primary stream). */
+    const unsigned long long *bloom_all = nullptr;
+    if (m1_prefilter_on(D.dim_join))
+    {
+        uint64_t bwords = q->bwmask + 1;
+        if (!q->m_bloom_all)
+            HIP_CHK(ctx, hipMalloc(&q->m_bloom_all,
+                                   (uint64_t) n * bwords * 8));
+        HIP_CHK(ctx, hipStreamWaitEvent(ms, dim_done, 0));
+        RCCL_CHK(ctx, ncclAllGather(q->bloom, q->m_bloom_all, bwords,
+                                    ncclUint64, ctx->comm, ms));
+        bloom_all = q->m_bloom_all;
+    }
+    HIP_CHK(ctx, hipMemsetAsync(dhist, 0, n * 8, ms));
+    m1_launch_hist(ms, od, oc, C.ovm, D.mid_filter.op,
+                   (int32_t) D.mid_filter.literal, n, D.dim_join,
+                   bloom_all, q->bwmask, dhist);
+    unsigned long long *dcnts_all = q->m_cnts_all;
+    double t_counts = 0;
+    auto now_ms = []() {
+        return (double) std::chrono::duration_cast<std::chrono::nanoseconds>(
+                   std::chrono::steady_clock::now().time_since_epoch())
+                   .count() / 1e6;
+    };
+    double tc0 = now_ms();
+    RCCL_CHK(ctx, ncclAllGather(dhist, dcnts_all, n, ncclUint64, ctx->comm, ms));
+    std::vector<unsigned long long> cnts_all(n * n);
+    HIP_CHK(ctx, hipMemcpyAsync(cnts_all.data(), dcnts_all, (int64_t) n * n * 8,
+                                hipMemcpyDeviceToHost, ms));
+    HIP_CHK(ctx, hipStreamSynchronize(ms));
+    t_counts += now_ms() - tc0;
+    const gx_mlayout L1 = m_exchange_layout(cnts_all.data(), n, ctx->seg);
+    if (grow(q->m_send1, q->m_send1_cap, L1.send_n) != GX_OK) return GX_ERR_OOM;
+    gx_ord_row *send1 = q->m_send1;
+    unsigned long long *dcur = q->m_cur;
+    HIP_CHK(ctx, hipMemcpyAsync(dcur, L1.soff.data(), n * 8, hipMemcpyHostToDevice, ms));
+    m1_launch_emit(ms, ok, oc, od, op, C.ovm, D.mid_filter.op,
+                   (int32_t) D.mid_filter.literal, n, D.dim_join,
+                   bloom_all, q->bwmask, dcur, send1);
+    unsigned long long recv1_n = L1.recv_n;
+    if (grow(q->m_recv1, q->m_recv1_cap, recv1_n) != GX_OK) return GX_ERR_OOM;
+    gx_ord_row *recv1 = q->m_recv1;
+    evholder pev0, pev1, pev2, pev3;
+    HIP_CHK(ctx, pev0.create()); HIP_CHK(ctx, pev1.create());
+    HIP_CHK(ctx, pev2.create()); HIP_CHK(ctx, pev3.create());
+    HIP_CHK(ctx, hipEventRecord(pev0, ms));
+    {
+        gx_status xst = m_exchange_payload(ctx, ms, send1, recv1, L1,
+                                           sizeof(gx_ord_row));
+        if (xst != GX_OK) return xst;
+    }
+    HIP_CHK(ctx, hipEventRecord(pev1, ms));
+
+    /* Motion 2: probe local customer set, route qualifying by o_orderkey
+     * — first wait (on-stream) for the dim-set build on the primary
+     * stream to finish */
+    HIP_CHK(ctx, hipStreamWaitEvent(ms, dim_done, 0));
+    HIP_CHK(ctx, hipMemsetAsync(dhist, 0, n * 8, ms));
+    m2_launch_hist(ms, recv1, (int64_t) recv1_n, q->cset, q->cset_width,
+                   q->cmask, q->bloom, q->bwmask, D.dim_join, n, dhist);
+    /* Motion-2 count exchange: same single-sync shape */
+    tc0 = now_ms();
+    RCCL_CHK(ctx, ncclAllGather(dhist, dcnts_all, n, ncclUint64, ctx->comm, ms));
+    HIP_CHK(ctx, hipMemcpyAsync(cnts_all.data(), dcnts_all, (int64_t) n * n * 8,
+                                hipMemcpyDeviceToHost, ms));
+    HIP_CHK(ctx, hipStreamSynchronize(ms));
+    t_counts += now_ms() - tc0;
+    const gx_mlayout L2 = m_exchange_layout(cnts_all.data(), n, ctx->seg);
+    if (grow(q->m_send2, q->m_send2_cap, L2.send_n) != GX_OK) return GX_ERR_OOM;
+    gx_qual_row *send2 = q->m_send2;
+    HIP_CHK(ctx, hipMemcpyAsync(dcur, L2.soff.data(), n * 8, hipMemcpyHostToDevice, ms));
+    m2_launch_emit(ms, recv1, (int64_t) recv1_n, q->cset, q->cset_width,
+                   q->cmask, q->bloom, q->bwmask, D.dim_join, n, dcur, send2);
+    unsigned long long recv2_n = L2.recv_n;
+    if (grow(q->m_recv2, q->m_recv2_cap, recv2_n) != GX_OK) return GX_ERR_OOM;
+    gx_qual_row *recv2 = q->m_recv2;
+    HIP_CHK(ctx, hipEventRecord(pev2, ms));
+    {
+        gx_status xst = m_exchange_payload(ctx, ms, send2, recv2, L2,
+                                           sizeof(gx_qual_row));
+        if (xst != GX_OK) return xst;
+    }
+    HIP_CHK(ctx, hipEventRecord(pev3, ms));
+
+    int64_t qual = (int64_t) recv2_n;
+    /* key stats over the received rows — the motion path then gets the
+     * same u32/interpolation table layout as the local path */
+    HIP_CHK(ctx, hipMemsetAsync(q->dhits, 0, 8, ms));
+    HIP_CHK(ctx, hipMemsetAsync(q->dmin, 0xFF, 8, ms));
+    hipLaunchKernelGGL(k_rows_minmax, dim3(GRID), dim3(TPB), 0, ms,
+                       recv2, qual, q->dhits, q->dmin);
+    unsigned long long kmax = 0, kmin = 0;
+    HIP_CHK(ctx, hipMemcpyAsync(&kmax, q->dhits, 8, hipMemcpyDeviceToHost, ms));
+    HIP_CHK(ctx, hipMemcpyAsync(&kmin, q->dmin, 8, hipMemcpyDeviceToHost, ms));
+    HIP_CHK(ctx, hipStreamSynchronize(ms));
+    if (qual > 0 && kmin == 0)
+    {
+        set_err(ctx, "mid join key 0 received: 0 is the empty-slot "
+                     "sentinel (gpuexec.h gx_q3_prepare_desc)%s", "");
+        return GX_ERR_INVALID;
+    }
+    /* same tuned fill factor as the local path (tf=300) */
+    const gx_tbl_layout TL = m3_table_layout(
+        qual, kmin, kmax, ctx->nsegs, env_int("GX_TABLE_FACTOR_PCT", 300));
+    int want_kw = TL.key_width;
+    uint64_t tslots = TL.slots;
+    /* motion path sizes from the exchanged counts each run; qual can
+     * grow within the same pow2 table size, so rescap is checked too */
+    if (q->tkey == nullptr || tslots > q->tmask + 1 || want_kw != q->key_width ||
+        qual + q->u_cap > q->rescap)
+    {
+        q->key_width = want_kw;
+        gx_status ast = q3_alloc_table(q, tslots, qual);
+        if (ast != GX_OK) return ast;
+    }
+    /* keys only: agg/attr slots are initialised at claim (gx_aggslot) */
+    HIP_CHK(ctx, hipMemsetAsync(q->tkey, 0, (q->tmask + 1) * q->key_width, ms));
+    if (D.fact_join == 1)
+    {
+        HIP_CHK(ctx, hipMemsetAsync(q->ukey, 0, (q->umask + 1) * 8, ms));
+        HIP_CHK(ctx, hipMemsetAsync(q->urev, 0, (q->umask + 1) * 8, ms));
+        HIP_CHK(ctx, hipMemsetAsync(q->ucnt_u, 0, (q->umask + 1) * 8, ms));
+    }
+    /* a reused cached table may be larger than this run's layout */
+    q->smap = (q->tmask + 1 == TL.slots)
+                  ? TL.smap
+                  : m3_slotmap(qual, kmin, kmax, ctx->nsegs, q->tmask + 1);
+    m3_launch_build(ms, recv2, qual, q->key_width, q->tkey,
+                    q->tattr, q->tagg, q->smap);
+    HIP_CHK(ctx, hipEventRecord(mev1, ms));
+    HIP_CHK(ctx, hipStreamSynchronize(ms));
+    float mms = 0, p01 = 0, p23 = 0;
+    (void) hipEventElapsedTime(&mms, mev0, mev1);
+    (void) hipEventElapsedTime(&p01, pev0, pev1);
+    (void) hipEventElapsedTime(&p23, pev2, pev3);
+    *ms_motion = mms;
+    q->stats.ms_motion_counts = t_counts;
+    q->stats.ms_motion_payload = (double) p01 + (double) p23;
+    *qual_out = qual;
+    return GX_OK;
+}
+
+/* Stage 3: lineitem scan+probe+agg (dominant kernel), in the form the fact
+ * key's format and the aggregation mode select: fused RLE, numeric, f64 */
+static gx_status q3_probe_agg(gx_q3 *q, const q3_runcols &C)
+{
+    gx_ctx *ctx = q->ctx;
+    hipStream_t s = ctx->stream;
+    const gx_q3_desc &D = q->desc;
+    const gx_col &lk = C.lk, &lp = C.lp, &ld = C.ld, &ls = C.ls;
+    unsigned long long *dhits = q->dhits;
+    HIP_CHK(ctx, hipMemsetAsync(dhits, 0, 8, s));
+    if (lk.format == 1)
+    {
+        if (q->numeric) { set_err(ctx, "numeric+RLE combo not supported%s", ""); return GX_ERR_INVALID; }
+        HIP_CHK(ctx, hipMemsetAsync(q->dmin, 0, 8, s));   /* borrowed err flag */
+        int64_t nb = lk.nblocks;
+        int rgrid = (int) std::min<int64_t>(std::max<int64_t>(nb, 1), 16384);
+        by_width(q->key_width, (const void *) q->tkey, [&](auto *keys) {
+            by_flag(C.lvm != nullptr, [&](auto vm) {
+                hipLaunchKernelGGL((k_li_probe_agg_rle<std::decay_t<decltype(*keys)>,
+                                                       decltype(vm)::value>),
+                                   dim3(rgrid), dim3(TPB), 0, s,
+                                   lk.dstream, lk.ddir, nb, lp.dstream, lp.m,
+                                   ld.dstream, ld.m, ls.dstream, ls.m, C.lvm,
+                                   D.fact_filter.op, (int32_t) D.fact_filter.literal,
+                                   keys, q->tagg, q->smap, dhits,
+                                   (int *) q->dmin);
+            });
+        });
+        int herr = 0;
+        HIP_CHK(ctx, hipMemcpyAsync(&herr, q->dmin, 4, hipMemcpyDeviceToHost, s));
+        HIP_CHK(ctx, hipStreamSynchronize(s));
+        if (herr) { set_err(ctx, "malformed RLE block in fused scan%s", ""); return GX_ERR_INVALID; }
+    }
+    else if (q->numeric)
+    {
+        HIP_CHK(ctx, hipMemsetAsync(q->dmin, 0, 8, s));   /* borrowed err flag */
+        by_width(q->key_width, (const void *) q->tkey, [&](auto *keys) {
+            by_flag(C.lvm != nullptr, [&](auto vm) {
+                by_flag(D.fact_join == 1, [&](auto outer) {
+                    hipLaunchKernelGGL((k_li_probe_agg_num<std::decay_t<decltype(*keys)>,
+                                                           decltype(vm)::value,
+                                                           decltype(outer)::value>),
+                                       dim3(GRID), dim3(TPB), 0, s,
+                                       lk.dstream, lk.m, lp.dstream, lp.m, ld.dstream, ld.m,
+                                       ls.dstream, ls.m, C.lvm, D.fact_filter.op,
+                                       (int32_t) D.fact_filter.literal, keys,
+                                       (gx_aggslot_num *) q->tagg, q->smap,
+                                       dhits, (int *) q->dmin,
+                                       q->ukey, (unsigned long long *) q->urev,
+                                       q->ucnt_u, q->umask);
+                });
+            });
+        });
+        int herr = 0;
+        HIP_CHK(ctx, hipMemcpyAsync(&herr, q->dmin, 4, hipMemcpyDeviceToHost, s));
+        HIP_CHK(ctx, hipStreamSynchronize(s));
+        if (herr) { set_err(ctx, "numeric overflow in aggregation%s", ""); return GX_ERR_INVALID; }
+    }
+    else
+        q3_launch_probe(
+            s, lk, lp, ld, ls, C.lvm, D.fact_filter.op,
+            (int32_t) D.fact_filter.literal, q->key_width, q->tkey, q->tagg,
+            q->smap, dhits, D.fact_join == 1, q->ukey, q->urev, q->ucnt_u,
+            q->umask);
+    return GX_OK;
+}
+
+/* Stage 4: extract the groups (and the LEFT-OUTER unmatched ones) into the
+ * result arrays; the group count lands in q->dcount */
+static gx_status q3_extract(gx_q3 *q)
+{
+    gx_ctx *ctx = q->ctx;
+    hipStream_t s = ctx->stream;
+    unsigned long long *dcount = q->dcount;
+    HIP_CHK(ctx, hipMemsetAsync(dcount, 0, 8, s));
+    if (q->r_flags)
+        HIP_CHK(ctx, hipMemsetAsync(q->r_flags, 0, q->rescap, s));
+    /* one block per fixed tile of the table; k_extract_u keeps its own grid */
+    const int egrid = 32768;
+    {
+        gx_status est = q3_launch_extract(ctx, s, q->key_width, q->tkey, q->tattr,
+                                          q->tagg, q->tmask + 1, q->numeric,
+                                          q->r_okey, q->r_odate, q->r_oprio,
+                                          q->r_rev, q->r_cnt, dcount);
+        if (est != GX_OK) return est;
+    }
+    if (q->desc.fact_join == 1)
+        hipLaunchKernelGGL(k_extract_u, dim3(egrid), dim3(TPB), 0, s,
+                           q->ukey, q->urev, q->ucnt_u, q->umask + 1,
+                           q->r_okey, q->r_odate, q->r_oprio, q->r_rev,
+                           q->r_cnt, q->r_flags, dcount, q->rescap);
     return GX_OK;
 }
 
@@ -6096,27 +5886,19 @@ extern "C" gx_status gx_q3_run(gx_q3 *q)
     for (auto &e : ev) HIP_CHK(ctx, e.create());
 
     const gx_q3_desc &D = q->desc;
-    const gx_col &ok = q3_col(q, q->ord, D.mid_key_col),
-                 &oc = q3_col(q, q->ord, D.mid_fk_col),
-                 &od = q3_col(q, q->ord, D.mid_filter.col),
-                 &op = q3_col(q, q->ord, D.mid_attr2_col);
-    const gx_col &lk = q3_col(q, q->li, D.fact_key_col),
-                 &lp = q3_col(q, q->li, D.fact_a_col),
-                 &ld = q3_col(q, q->li, D.fact_b_col),
-                 &ls = q3_col(q, q->li, D.fact_filter.col);
-    unsigned long long *dcount = q->dcount;
-    /* effective visibility (extra-qual masks fold the visimap in) */
-    const uint8_t *ovm_eff = q->qvm_mid ? q->qvm_mid : q->ord->dvmap;
-    const uint8_t *lvm_eff = q->qvm_fact ? q->qvm_fact
-                                         : (q->li ? q->li->dvmap : nullptr);
+    const q3_runcols C = {
+        q3_col(q, q->ord, D.mid_key_col), q3_col(q, q->ord, D.mid_fk_col),
+        q3_col(q, q->ord, D.mid_filter.col), q3_col(q, q->ord, D.mid_attr2_col),
+        q3_col(q, q->li, D.fact_key_col), q3_col(q, q->li, D.fact_a_col),
+        q3_col(q, q->li, D.fact_b_col), q3_col(q, q->li, D.fact_filter.col),
+        q->qvm_mid ? q->qvm_mid : q->ord->dvmap,
+        q->qvm_fact ? q->qvm_fact : (q->li ? q->li->dvmap : nullptr)};
 
     /* ---- stage 1: customer BUILDING membership (rebuilt every run) ----
      * the local path reads the bitmap when sizing chose one; the Motion path
-     * (and the two-pass experiment) read set+bloom.  Only that one is
-     * cleared and filled. */
+     * reads set+bloom.  Only that one is cleared and filled. */
     bool local_path = ctx->nsegs == 1 && env_int("GX_FORCE_MOTION", 0) == 0;
-    bool use_bitmap = q->dim_bitmap && local_path &&
-                      env_int("GX_ORDERS_TWOPASS", 0) == 0;
+    bool use_bitmap = q->dim_bitmap && local_path;
     q->dim_mode = use_bitmap ? 1 : 0;
     HIP_CHK(ctx, hipEventRecord(ev[0], s));
     {
@@ -6133,436 +5915,35 @@ extern "C" gx_status gx_q3_run(gx_q3 *q)
     double ms_motion = 0.0;
     if (local_path)
     {
-        uint64_t tslots = q->tmask + 1;
-        /* keys only: agg/attr slots are initialised at claim (gx_aggslot) */
-        HIP_CHK(ctx, hipMemsetAsync(q->tkey, 0, tslots * q->key_width, s));
-        if (D.fact_join == 1)
-        {
-            HIP_CHK(ctx, hipMemsetAsync(q->ukey, 0, (q->umask + 1) * 8, s));
-            HIP_CHK(ctx, hipMemsetAsync(q->urev, 0, (q->umask + 1) * 8, s));
-            HIP_CHK(ctx, hipMemsetAsync(q->ucnt_u, 0, (q->umask + 1) * 8, s));
-        }
-        int ogrid = env_int("GX_ORDERS_GRID", 32768);  /* measured optimum */
-        bool ochunk = env_int("GX_ORDERS_CHUNKED", 0) != 0;
-        const uint8_t *ovm = ovm_eff;
-        bool anti_join = D.dim_join != 0;
-        gx_dimbits dbm = {q->dbits, q->dim_kmin, q->dim_range};
-        auto launch_build = [&](auto *tk, auto *cs, auto bmode) {
-            auto go2 = [&](auto ch, auto vm, auto anti) {
-                hipLaunchKernelGGL((k_orders_build<std::decay_t<decltype(*tk)>,
-                                                   std::decay_t<decltype(*cs)>,
-                                                   decltype(ch)::value,
-                                                   decltype(vm)::value,
-                                                   decltype(anti)::value,
-                                                   decltype(bmode)::value>),
-                                   dim3(ogrid), dim3(TPB), 0, s,
-                                   ok.dstream, ok.m, oc.dstream, oc.m, od.dstream, od.m,
-                                   op.dstream, op.m, ovm, D.mid_filter.op,
-                                   (int32_t) D.mid_filter.literal, cs, q->cmask,
-                                   q->bloom, q->bwmask, dbm,
-                                   tk, q->tattr, q->tagg, q->smap);
-            };
-            auto go = [&](auto ch, auto vm) {
-                if (anti_join) go2(ch, vm, std::true_type{});
-                else go2(ch, vm, std::false_type{});
-            };
-            if (ochunk)
-            {
-                if (ovm) go(std::true_type{}, std::true_type{});
-                else go(std::true_type{}, std::false_type{});
-            }
-            else
-            {
-                if (ovm) go(std::false_type{}, std::true_type{});
-                else go(std::false_type{}, std::false_type{});
-            }
-        };
-        if (env_int("GX_ORDERS_TWOPASS", 0))
-        {
-            /* experiment: homogeneous filter/emit scan + separate insert */
-            if (!q->m_send2 || q->m_send2_cap < (uint64_t) q->rescap)
-            {
-                if (q->m_send2) (void) hipFree(q->m_send2);
-                q->m_send2 = nullptr; q->m_send2_cap = 0;
-                HIP_CHK(ctx, hipMalloc(&q->m_send2,
-                                       std::max<int64_t>(q->rescap, 1) *
-                                           sizeof(gx_qual_row)));
-                q->m_send2_cap = q->rescap;
-            }
-            HIP_CHK(ctx, hipMemsetAsync(q->dcount, 0, 8, s));
-            auto launch_emit = [&](auto *cs) {
-                auto goe = [&](auto anti) {
-                    hipLaunchKernelGGL((k_orders_emitq<std::decay_t<decltype(*cs)>,
-                                                       decltype(anti)::value>),
-                                       dim3(ogrid), dim3(TPB), 0, s,
-                                       ok.dstream, ok.m, oc.dstream, oc.m,
-                                       od.dstream, od.m, op.dstream, op.m,
-                                       ovm_eff,
-                                       D.mid_filter.op, (int32_t) D.mid_filter.literal,
-                                       cs, q->cmask, q->bloom, q->bwmask,
-                                       q->m_send2, q->dcount);
-                };
-                if (anti_join) goe(std::true_type{});
-                else goe(std::false_type{});
-            };
-            if (q->cset_width == 4)
-                launch_emit((const unsigned int *) q->cset);
-            else
-                launch_emit((const unsigned long long *) q->cset);
-            m3_launch_build(s, q->m_send2, q->rescap, q->dcount, q->key_width,
-                            q->tkey, q->tattr, q->tagg, q->smap);
-        }
-        else if (use_bitmap && q->key_width == 4)
-            launch_build((unsigned int *) q->tkey, (const unsigned int *) nullptr,
-                         std::true_type{});
-        else if (use_bitmap)
-            launch_build((unsigned long long *) q->tkey,
-                         (const unsigned int *) nullptr, std::true_type{});
-        else if (q->key_width == 4 && q->cset_width == 4)
-            launch_build((unsigned int *) q->tkey, (const unsigned int *) q->cset,
-                         std::false_type{});
-        else if (q->key_width == 4)
-            launch_build((unsigned int *) q->tkey,
-                         (const unsigned long long *) q->cset, std::false_type{});
-        else if (q->cset_width == 4)
-            launch_build((unsigned long long *) q->tkey,
-                         (const unsigned int *) q->cset, std::false_type{});
-        else
-            launch_build((unsigned long long *) q->tkey,
-                         (const unsigned long long *) q->cset, std::false_type{});
+        gx_status st = q3_orders_local(q, C, use_bitmap);
+        if (st != GX_OK) return st;
         qual = q->rescap;
     }
     else
     {
-        if (!ctx->comm) { set_err(ctx, "nsegs>1 but gx_comm_init not called%s", ""); return GX_ERR_STATE; }
-        int n = ctx->nsegs;
-        /* the exchange runs on stream2, concurrent with the dim-set build
-         * still in flight on the primary stream (they only meet at the
-         * local semijoin below, via a cross-stream event wait); the branch
-         * ends in a host sync, so stage 3 on the primary stream is ordered */
-        hipStream_t s = ctx->stream2;
-        evholder mev0, mev1;
-        HIP_CHK(ctx, mev0.create()); HIP_CHK(ctx, mev1.create());
-        HIP_CHK(ctx, hipEventRecord(mev0, s));
-
-        /* Motion 1: filtered orders by route(o_custkey).  Exchange buffers
-         * are cached in gx_q3 (grow-only) — per-step hipMalloc would
-         * dominate at high rank counts. */
-        auto grow = [&](auto *&p, uint64_t &cap, uint64_t want) -> gx_status {
-            if (want <= cap) return GX_OK;
-            if (p) (void) hipFree(p);
-            p = nullptr;
-            cap = 0;
-            hipError_t e = hipMalloc(&p, std::max<uint64_t>(want, 1) *
-                                          sizeof(**(&p)));
-            if (e != hipSuccess) return GX_ERR_OOM;
-            cap = want;
-            return GX_OK;
-        };
-        if (!q->m_hist)
-        {
-            HIP_CHK(ctx, hipMalloc(&q->m_hist, n * 8));
-            HIP_CHK(ctx, hipMalloc(&q->m_cur, n * 8));
-            HIP_CHK(ctx, hipMalloc(&q->m_cnts_mine, n * 8));
-            HIP_CHK(ctx, hipMalloc(&q->m_cnts_all, (int64_t) n * n * 8));
-        }
-        /* Motion-1 count exchange: the per-dest histogram goes straight
-         * into the all-gather, so ONE host sync yields both this rank's
-         * send layout (its own row) and every peer's counts (r2: the two
-         * separate count syncs were ~half the fixed motion latency) */
-        unsigned long long *dhist = q->m_hist;
-        /* destination-aware bloom prefilter (semi join only): all-gather
-         * every rank's dim bloom, then only ship orders whose fk passes
-         * the DESTINATION's bloom — the runtime filter pushed across the
-         * interconnect.  Requires the local dim build (primary stream). */
-        const unsigned long long *bloom_all = nullptr;
-        if (m1_prefilter_on(D.dim_join))
-        {
-            uint64_t bwords = q->bwmask + 1;
-            if (!q->m_bloom_all)
-                HIP_CHK(ctx, hipMalloc(&q->m_bloom_all,
-                                       (uint64_t) n * bwords * 8));
-            HIP_CHK(ctx, hipStreamWaitEvent(s, ev[1], 0));
-            RCCL_CHK(ctx, ncclAllGather(q->bloom, q->m_bloom_all, bwords,
-                                        ncclUint64, ctx->comm, s));
-            bloom_all = q->m_bloom_all;
-        }
-        HIP_CHK(ctx, hipMemsetAsync(dhist, 0, n * 8, s));
-        m1_launch_hist(s, od, oc, ovm_eff, D.mid_filter.op,
-                       (int32_t) D.mid_filter.literal, n, D.dim_join,
-                       bloom_all, q->bwmask, dhist);
-        unsigned long long *dcnts_all = q->m_cnts_all;
-        double t_counts = 0;
-        auto now_ms = []() {
-            return (double) std::chrono::duration_cast<std::chrono::nanoseconds>(
-                       std::chrono::steady_clock::now().time_since_epoch())
-                       .count() / 1e6;
-        };
-        double tc0 = now_ms();
-        RCCL_CHK(ctx, ncclAllGather(dhist, dcnts_all, n, ncclUint64, ctx->comm, s));
-        std::vector<unsigned long long> cnts_all(n * n);
-        HIP_CHK(ctx, hipMemcpyAsync(cnts_all.data(), dcnts_all, (int64_t) n * n * 8,
-                                    hipMemcpyDeviceToHost, s));
-        HIP_CHK(ctx, hipStreamSynchronize(s));
-        t_counts += now_ms() - tc0;
-        const gx_mlayout L1 = m_exchange_layout(cnts_all.data(), n, ctx->seg);
-        const auto &h1 = L1.scnt, &off1 = L1.soff, &rcv1 = L1.rcnt, &roff1 = L1.roff;
-        if (grow(q->m_send1, q->m_send1_cap, L1.send_n) != GX_OK) return GX_ERR_OOM;
-        gx_ord_row *send1 = q->m_send1;
-        unsigned long long *dcur = q->m_cur;
-        HIP_CHK(ctx, hipMemcpyAsync(dcur, off1.data(), n * 8, hipMemcpyHostToDevice, s));
-        m1_launch_emit(s, ok, oc, od, op, ovm_eff, D.mid_filter.op,
-                       (int32_t) D.mid_filter.literal, n, D.dim_join,
-                       bloom_all, q->bwmask, dcur, send1);
-        unsigned long long recv1_n = L1.recv_n;
-        if (grow(q->m_recv1, q->m_recv1_cap, recv1_n) != GX_OK) return GX_ERR_OOM;
-        gx_ord_row *recv1 = q->m_recv1;
-        /* self-share bypasses RCCL entirely: a device copy is both faster
-         * and avoids self-send at GB sizes (alltoallv standard practice) */
-        evholder pev0, pev1, pev2, pev3;
-        HIP_CHK(ctx, pev0.create()); HIP_CHK(ctx, pev1.create());
-        HIP_CHK(ctx, pev2.create()); HIP_CHK(ctx, pev3.create());
-        HIP_CHK(ctx, hipEventRecord(pev0, s));
-        if (h1[ctx->seg])
-            HIP_CHK(ctx, hipMemcpyAsync(recv1 + roff1[ctx->seg],
-                                        send1 + off1[ctx->seg],
-                                        h1[ctx->seg] * sizeof(gx_ord_row),
-                                        hipMemcpyDeviceToDevice, s));
-        RCCL_CHK(ctx, ncclGroupStart());
-        for (int r = 0; r < n; r++)
-        {
-            if (r == ctx->seg) continue;
-            if (h1[r])
-                RCCL_CHK(ctx, gx_nccl_send_chunked(send1 + off1[r],
-                                                   h1[r] * sizeof(gx_ord_row),
-                                                   r, ctx->comm, s));
-            if (rcv1[r])
-                RCCL_CHK(ctx, gx_nccl_recv_chunked(recv1 + roff1[r],
-                                                   rcv1[r] * sizeof(gx_ord_row),
-                                                   r, ctx->comm, s));
-        }
-        RCCL_CHK(ctx, ncclGroupEnd());
-        HIP_CHK(ctx, hipEventRecord(pev1, s));
-
-        /* Motion 2: probe local customer set, route qualifying by o_orderkey
-         * — first wait (on-stream) for the dim-set build on the primary
-         * stream to finish */
-        HIP_CHK(ctx, hipStreamWaitEvent(s, ev[1], 0));
-        HIP_CHK(ctx, hipMemsetAsync(dhist, 0, n * 8, s));
-        m2_launch_hist(s, recv1, (int64_t) recv1_n, q->cset, q->cset_width,
-                       q->cmask, q->bloom, q->bwmask, D.dim_join, n, dhist);
-        /* Motion-2 count exchange: same single-sync shape */
-        tc0 = now_ms();
-        RCCL_CHK(ctx, ncclAllGather(dhist, dcnts_all, n, ncclUint64, ctx->comm, s));
-        HIP_CHK(ctx, hipMemcpyAsync(cnts_all.data(), dcnts_all, (int64_t) n * n * 8,
-                                    hipMemcpyDeviceToHost, s));
-        HIP_CHK(ctx, hipStreamSynchronize(s));
-        t_counts += now_ms() - tc0;
-        const gx_mlayout L2 = m_exchange_layout(cnts_all.data(), n, ctx->seg);
-        const auto &h2 = L2.scnt, &off2 = L2.soff, &rcv2 = L2.rcnt, &roff2 = L2.roff;
-        if (grow(q->m_send2, q->m_send2_cap, L2.send_n) != GX_OK) return GX_ERR_OOM;
-        gx_qual_row *send2 = q->m_send2;
-        HIP_CHK(ctx, hipMemcpyAsync(dcur, off2.data(), n * 8, hipMemcpyHostToDevice, s));
-        m2_launch_emit(s, recv1, (int64_t) recv1_n, q->cset, q->cset_width,
-                       q->cmask, q->bloom, q->bwmask, D.dim_join, n, dcur, send2);
-        unsigned long long recv2_n = L2.recv_n;
-        if (grow(q->m_recv2, q->m_recv2_cap, recv2_n) != GX_OK) return GX_ERR_OOM;
-        gx_qual_row *recv2 = q->m_recv2;
-        HIP_CHK(ctx, hipEventRecord(pev2, s));
-        if (h2[ctx->seg])
-            HIP_CHK(ctx, hipMemcpyAsync(recv2 + roff2[ctx->seg],
-                                        send2 + off2[ctx->seg],
-                                        h2[ctx->seg] * sizeof(gx_qual_row),
-                                        hipMemcpyDeviceToDevice, s));
-        RCCL_CHK(ctx, ncclGroupStart());
-        for (int r = 0; r < n; r++)
-        {
-            if (r == ctx->seg) continue;
-            if (h2[r])
-                RCCL_CHK(ctx, gx_nccl_send_chunked(send2 + off2[r],
-                                                   h2[r] * sizeof(gx_qual_row),
-                                                   r, ctx->comm, s));
-            if (rcv2[r])
-                RCCL_CHK(ctx, gx_nccl_recv_chunked(recv2 + roff2[r],
-                                                   rcv2[r] * sizeof(gx_qual_row),
-                                                   r, ctx->comm, s));
-        }
-        RCCL_CHK(ctx, ncclGroupEnd());
-        HIP_CHK(ctx, hipEventRecord(pev3, s));
-
-        qual = (int64_t) recv2_n;
-        /* key stats over the received rows — the motion path then gets the
-         * same u32/interpolation table layout as the local path */
-        HIP_CHK(ctx, hipMemsetAsync(q->dhits, 0, 8, s));
-        HIP_CHK(ctx, hipMemsetAsync(q->dmin, 0xFF, 8, s));
-        hipLaunchKernelGGL(k_rows_minmax, dim3(GRID), dim3(TPB), 0, s,
-                           recv2, qual, q->dhits, q->dmin);
-        unsigned long long kmax = 0, kmin = 0;
-        HIP_CHK(ctx, hipMemcpyAsync(&kmax, q->dhits, 8, hipMemcpyDeviceToHost, s));
-        HIP_CHK(ctx, hipMemcpyAsync(&kmin, q->dmin, 8, hipMemcpyDeviceToHost, s));
-        HIP_CHK(ctx, hipStreamSynchronize(s));
-        if (qual > 0 && kmin == 0)
-        {
-            set_err(ctx, "mid join key 0 received: 0 is the empty-slot "
-                         "sentinel (gpuexec.h gx_q3_prepare_desc)%s", "");
-            return GX_ERR_INVALID;
-        }
-        /* same tuned fill factor as the local path (tf=300) */
-        const gx_tbl_layout TL = m3_table_layout(
-            qual, kmin, kmax, ctx->nsegs, env_int("GX_TABLE_FACTOR_PCT", 300));
-        int want_kw = TL.key_width;
-        uint64_t tslots = TL.slots;
-        /* motion path sizes from the exchanged counts each run; qual can
-         * grow within the same pow2 table size, so rescap is checked too */
-        if (q->tkey == nullptr || tslots > q->tmask + 1 || want_kw != q->key_width ||
-            qual + q->u_cap > q->rescap)
-        {
-            auto fr = [](auto *&p) { if (p) { (void) hipFree(p); p = nullptr; } };
-            fr(q->tkey); fr(q->tattr); fr(q->tagg);
-            fr(q->r_okey); fr(q->r_odate); fr(q->r_oprio); fr(q->r_rev); fr(q->r_cnt);
-            fr(q->r_flags);
-            q->key_width = want_kw;
-            HIP_CHK(ctx, hipMalloc(&q->tkey, tslots * q->key_width));
-            HIP_CHK(ctx, hipMalloc(&q->tattr, tslots * sizeof(gx_attrpair)));
-            HIP_CHK(ctx, hipMalloc(&q->tagg, tslots * sizeof(gx_aggslot)));
-            q->rescap = std::max<int64_t>(qual + q->u_cap, 1);
-            HIP_CHK(ctx, hipMalloc(&q->r_okey, q->rescap * 8));
-            HIP_CHK(ctx, hipMalloc(&q->r_odate, q->rescap * 4));
-            HIP_CHK(ctx, hipMalloc(&q->r_oprio, q->rescap * 4));
-            HIP_CHK(ctx, hipMalloc(&q->r_rev, q->rescap * 8));
-            HIP_CHK(ctx, hipMalloc(&q->r_cnt, q->rescap * 8));
-            HIP_CHK(ctx, hipMalloc(&q->r_flags, q->rescap));
-            q->tmask = tslots - 1;
-        }
-        /* keys only: agg/attr slots are initialised at claim (gx_aggslot) */
-        HIP_CHK(ctx, hipMemsetAsync(q->tkey, 0, (q->tmask + 1) * q->key_width, s));
-        if (D.fact_join == 1)
-        {
-            HIP_CHK(ctx, hipMemsetAsync(q->ukey, 0, (q->umask + 1) * 8, s));
-            HIP_CHK(ctx, hipMemsetAsync(q->urev, 0, (q->umask + 1) * 8, s));
-            HIP_CHK(ctx, hipMemsetAsync(q->ucnt_u, 0, (q->umask + 1) * 8, s));
-        }
-        /* a reused cached table may be larger than this run's layout */
-        q->smap = (q->tmask + 1 == TL.slots)
-                      ? TL.smap
-                      : m3_slotmap(qual, kmin, kmax, ctx->nsegs, q->tmask + 1);
-        m3_launch_build(s, recv2, qual, nullptr, q->key_width, q->tkey,
-                        q->tattr, q->tagg, q->smap);
-        HIP_CHK(ctx, hipEventRecord(mev1, s));
-        HIP_CHK(ctx, hipStreamSynchronize(s));
-        float mms = 0, p01 = 0, p23 = 0;
-        (void) hipEventElapsedTime(&mms, mev0, mev1);
-        (void) hipEventElapsedTime(&p01, pev0, pev1);
-        (void) hipEventElapsedTime(&p23, pev2, pev3);
-        ms_motion = mms;
-        q->stats.ms_motion_counts = t_counts;
-        q->stats.ms_motion_payload = (double) p01 + (double) p23;
+        gx_status st = q3_orders_motion(q, C, ev[1], &qual, &ms_motion);
+        if (st != GX_OK) return st;
     }
     q->qual_orders = qual;
     HIP_CHK(ctx, hipEventRecord(ev[2], s));
 
     /* ---- stage 3: lineitem scan+probe+agg (dominant kernel) ---- */
-    unsigned long long *dhits = q->dhits;
-    HIP_CHK(ctx, hipMemsetAsync(dhits, 0, 8, s));
-    if (lk.format == 1)
     {
-        if (q->numeric) { set_err(ctx, "numeric+RLE combo not supported%s", ""); return GX_ERR_INVALID; }
-        HIP_CHK(ctx, hipMemsetAsync(q->dmin, 0, 8, s));   /* borrowed err flag */
-        int64_t nb = lk.nblocks;
-        int rgrid = (int) std::min<int64_t>(std::max<int64_t>(nb, 1), 16384);
-        const uint8_t *lvm = lvm_eff;
-        auto launch_rle = [&](auto *keys, auto vm) {
-            hipLaunchKernelGGL((k_li_probe_agg_rle<std::decay_t<decltype(*keys)>,
-                                                   decltype(vm)::value>),
-                               dim3(rgrid), dim3(TPB), 0, s,
-                               lk.dstream, lk.ddir, nb, lp.dstream, lp.m,
-                               ld.dstream, ld.m, ls.dstream, ls.m, lvm,
-                               D.fact_filter.op, (int32_t) D.fact_filter.literal,
-                               keys, q->tagg, q->smap, dhits,
-                               (int *) q->dmin);
-        };
-        if (q->key_width == 4)
-        {
-            if (lvm) launch_rle((const unsigned int *) q->tkey, std::true_type{});
-            else launch_rle((const unsigned int *) q->tkey, std::false_type{});
-        }
-        else
-        {
-            if (lvm) launch_rle((const unsigned long long *) q->tkey, std::true_type{});
-            else launch_rle((const unsigned long long *) q->tkey, std::false_type{});
-        }
-        int herr = 0;
-        HIP_CHK(ctx, hipMemcpyAsync(&herr, q->dmin, 4, hipMemcpyDeviceToHost, s));
-        HIP_CHK(ctx, hipStreamSynchronize(s));
-        if (herr) { set_err(ctx, "malformed RLE block in fused scan%s", ""); return GX_ERR_INVALID; }
-    }
-    else if (q->numeric)
-    {
-        HIP_CHK(ctx, hipMemsetAsync(q->dmin, 0, 8, s));   /* borrowed err flag */
-        const uint8_t *lvm = lvm_eff;
-        auto launch_num = [&](auto *keys, auto vm, auto outer) {
-            hipLaunchKernelGGL((k_li_probe_agg_num<std::decay_t<decltype(*keys)>,
-                                                   decltype(vm)::value,
-                                                   decltype(outer)::value>),
-                               dim3(GRID), dim3(TPB), 0, s,
-                               lk.dstream, lk.m, lp.dstream, lp.m, ld.dstream, ld.m,
-                               ls.dstream, ls.m, lvm, D.fact_filter.op,
-                               (int32_t) D.fact_filter.literal, keys,
-                               (gx_aggslot_num *) q->tagg, q->smap,
-                               dhits, (int *) q->dmin,
-                               q->ukey, (unsigned long long *) q->urev,
-                               q->ucnt_u, q->umask);
-        };
-        auto dis_num = [&](auto *keys) {
-            bool outer = D.fact_join == 1;
-            if (lvm && outer) launch_num(keys, std::true_type{}, std::true_type{});
-            else if (lvm) launch_num(keys, std::true_type{}, std::false_type{});
-            else if (outer) launch_num(keys, std::false_type{}, std::true_type{});
-            else launch_num(keys, std::false_type{}, std::false_type{});
-        };
-        if (q->key_width == 4)
-            dis_num((const unsigned int *) q->tkey);
-        else
-            dis_num((const unsigned long long *) q->tkey);
-        int herr = 0;
-        HIP_CHK(ctx, hipMemcpyAsync(&herr, q->dmin, 4, hipMemcpyDeviceToHost, s));
-        HIP_CHK(ctx, hipStreamSynchronize(s));
-        if (herr) { set_err(ctx, "numeric overflow in aggregation%s", ""); return GX_ERR_INVALID; }
-    }
-    else
-    {
-        gx_status pst = q3_launch_probe(
-            ctx, s, lk, lp, ld, ls, lvm_eff, D.fact_filter.op,
-            (int32_t) D.fact_filter.literal, q->key_width, q->tkey, q->tagg,
-            q->smap, dhits, D.fact_join == 1, q->ukey, q->urev, q->ucnt_u,
-            q->umask);
-        if (pst != GX_OK) return pst;
+        gx_status st = q3_probe_agg(q, C);
+        if (st != GX_OK) return st;
     }
     HIP_CHK(ctx, hipEventRecord(ev[3], s));
 
     /* ---- stage 4: extract ---- */
-    HIP_CHK(ctx, hipMemsetAsync(dcount, 0, 8, s));
-    if (q->r_flags)
-        HIP_CHK(ctx, hipMemsetAsync(q->r_flags, 0, q->rescap, s));
-    /* one block per fixed tile of the table; k_extract_u keeps its own grid */
-    const int egrid = 32768;
     {
-        gx_status est = q3_launch_extract(ctx, s, q->key_width, q->tkey, q->tattr,
-                                          q->tagg, q->tmask + 1, q->numeric,
-                                          q->r_okey, q->r_odate, q->r_oprio,
-                                          q->r_rev, q->r_cnt, dcount);
-        if (est != GX_OK) return est;
+        gx_status st = q3_extract(q);
+        if (st != GX_OK) return st;
     }
-    if (q->desc.fact_join == 1)
-        hipLaunchKernelGGL(k_extract_u, dim3(egrid), dim3(TPB), 0, s,
-                           q->ukey, q->urev, q->ucnt_u, q->umask + 1,
-                           q->r_okey, q->r_odate, q->r_oprio, q->r_rev,
-                           q->r_cnt, q->r_flags, dcount, q->rescap);
     HIP_CHK(ctx, hipEventRecord(ev[4], s));
 
     unsigned long long ngroups = 0, hits = 0;
-    HIP_CHK(ctx, hipMemcpyAsync(&ngroups, dcount, 8, hipMemcpyDeviceToHost, s));
-    HIP_CHK(ctx, hipMemcpyAsync(&hits, dhits, 8, hipMemcpyDeviceToHost, s));
+    HIP_CHK(ctx, hipMemcpyAsync(&ngroups, q->dcount, 8, hipMemcpyDeviceToHost, s));
+    HIP_CHK(ctx, hipMemcpyAsync(&hits, q->dhits, 8, hipMemcpyDeviceToHost, s));
     HIP_CHK(ctx, hipStreamSynchronize(s));
     HIP_CHK(ctx, hipGetLastError());
     if (q->desc.fact_join == 1 && (int64_t) ngroups > q->rescap)
@@ -7022,9 +6403,7 @@ static gx_status test_build_dim(gx_ctx *ctx, gx_table *customer, int32_t op,
     unsigned long long *dc = cnt_b.as<unsigned long long>();
     HIP_CHK(ctx, hipMemsetAsync(dc, 0, 16, s));
     HIP_CHK(ctx, hipMemsetAsync(dc + 2, 0xFF, 8, s));
-    hipLaunchKernelGGL(k_cust_count, dim3(GRID), dim3(TPB), 0, s,
-                       ck.dstream, ck.m, cm.dstream, cm.m, cvm, op,
-                       (int8_t) literal, dc, dc + 1, dc + 2);
+    dim_launch_count(s, ck, nullptr, cm, op, literal, cvm, dc, dc + 1, dc + 2);
     unsigned long long st[3];
     HIP_CHK(ctx, hipMemcpyAsync(st, dc, 24, hipMemcpyDeviceToHost, s));
     HIP_CHK(ctx, hipStreamSynchronize(s));
@@ -7047,17 +6426,9 @@ static gx_status test_build_dim(gx_ctx *ctx, gx_table *customer, int32_t op,
     HIP_CHK(ctx, ds.bloom.alloc(bwords * 8));
     HIP_CHK(ctx, hipMemsetAsync(ds.set.p, 0, cslots * ds.width, s));
     HIP_CHK(ctx, hipMemsetAsync(ds.bloom.p, 0, bwords * 8, s));
-    auto go = [&](auto *cs) {
-        hipLaunchKernelGGL((k_cust_build<std::decay_t<decltype(*cs)>, false>),
-                           dim3(GRID), dim3(TPB), 0, s,
-                           ck.dstream, ck.m, cm.dstream, cm.m, cvm, op,
-                           (int8_t) literal, cs, ds.cmask,
-                           ds.bloom.as<unsigned long long>(), ds.bwmask,
-                           (unsigned long long *) nullptr, (uint64_t) 0,
-                           (uint64_t) 0);
-    };
-    if (ds.width == 4) go(ds.set.as<unsigned int>());
-    else go(ds.set.as<unsigned long long>());
+    dim_launch_build(s, ck, nullptr, cm, op, literal, cvm, ds.set.p, ds.width,
+                     ds.cmask, ds.bloom.as<unsigned long long>(), ds.bwmask,
+                     nullptr, 0, 0);
     return GX_OK;
 }
 
@@ -7194,20 +6565,17 @@ static gx_status test_m3_impl(gx_ctx *ctx, const gx_qual_row_abi *host_rows,
     HIP_CHK(ctx, attr_b.alloc(tslots * sizeof(gx_attrpair)));
     HIP_CHK(ctx, agg_b.alloc(tslots * sizeof(gx_aggslot)));
     HIP_CHK(ctx, hipMemsetAsync(key_b.p, 0, tslots * TL.key_width, s));
-    m3_launch_build(s, rows_b.as<gx_qual_row>(), n, nullptr, TL.key_width,
+    m3_launch_build(s, rows_b.as<gx_qual_row>(), n, TL.key_width,
                     key_b.p, attr_b.as<gx_attrpair>(), agg_b.as<gx_aggslot>(),
                     TL.smap);
     const gx_col &lk = lineitem->cols[0], &lp = lineitem->cols[1],
                  &ld = lineitem->cols[2], &ls = lineitem->cols[3];
     HIP_CHK(ctx, hit_b.alloc(8));
     HIP_CHK(ctx, hipMemsetAsync(hit_b.p, 0, 8, s));
-    {
-        gx_status pst = q3_launch_probe(
-            ctx, s, lk, lp, ld, ls, lineitem->dvmap, fop, (int32_t) flit,
-            TL.key_width, key_b.p, agg_b.as<gx_aggslot>(), TL.smap,
-            hit_b.as<unsigned long long>(), false, nullptr, nullptr, nullptr, 0);
-        if (pst != GX_OK) return pst;
-    }
+    q3_launch_probe(
+        s, lk, lp, ld, ls, lineitem->dvmap, fop, (int32_t) flit,
+        TL.key_width, key_b.p, agg_b.as<gx_aggslot>(), TL.smap,
+        hit_b.as<unsigned long long>(), false, nullptr, nullptr, nullptr, 0);
     devbuf r_okey, r_odate, r_oprio, r_rev, r_cnt;
     int64_t cap = std::max<int64_t>(n, 1);
     HIP_CHK(ctx, r_okey.alloc(cap * 8));

@@ -242,7 +242,7 @@ ALL_OUT = (("!=", 300), ("<", 3 * 10**9), (">", -3 * 10**9))
 
 
 def test_q3_edge_literals_forced_motion(ctx, q3t):
-    """the Motion kernels (k_ord_m1_*, k_orders_emitq) take the same folded
+    """the Motion kernels (k_ord_m1_hist, k_ord_m1_emit) take the same folded
     literals"""
     try:
         ctx.comm_init(ctx.comm_unique_id())

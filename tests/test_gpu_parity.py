@@ -2081,3 +2081,172 @@ def test_q3_desc_fuzz_outer(ctx, orc):
         assert int(got["nitems"].sum()) == int(matched.sum() + unmatched.sum()
                                                + nullrows.sum())
         li.free(); ordr.free(); cust.free()
+
+
+# ---------------- every instantiation of the probe and dim-build dispatch ----------------
+# Small plans that pin which compiled form of the probe kernels (f64 /
+# numeric / fused RLE x 4- or 8-byte table keys x visimap x LEFT OUTER) and
+# of the customer count/build kernels (compare or text-mask predicate x
+# bitmap or hash x 4- or 8-byte set keys) a run takes.  Row counts are no
+# multiple of 64 (partial waves) and the 8 KiB AO blocksize puts several
+# block boundaries inside every lineitem column.
+
+MX_NC, MX_NO, MX_NL, MX_BS = 301, 1001, 4999, 8192
+
+
+def _mx_plan(ctx, orc, wide_okeys=False, wide_ckeys=False, numeric=False,
+             rle=False, text=False):
+    """Tables for the dispatch matrix: host columns for the oracle and the
+    bound GPU tables.  About a tenth of the fact rows carry keys past the
+    orders domain (misses; unmatched groups under LEFT OUTER)."""
+    rng = np.random.default_rng(4242)
+    cut = gx.CUTOFF_19950315
+    koff = (1 << 33) if wide_okeys else 0
+    coff = (1 << 34) if wide_ckeys else 0
+    c = {"c_custkey": coff + np.arange(1, MX_NC + 1, dtype=np.int64),
+         "c_mktsegment": (np.arange(MX_NC) % 5).astype(np.uint8)}
+    o = {"o_orderkey": koff + np.arange(1, MX_NO + 1, dtype=np.int64),
+         "o_custkey": coff + rng.integers(1, MX_NC + 1, MX_NO).astype(np.int64),
+         "o_orderdate": (cut + rng.integers(-300, 300, MX_NO)).astype(np.int32),
+         "o_shippriority": rng.integers(0, 5, MX_NO).astype(np.int32)}
+    lkeys = np.sort(koff + rng.integers(1, MX_NO + MX_NO // 10, MX_NL)).astype(np.int64)
+    cents = rng.integers(100, 10_000_000, MX_NL).astype(np.int64)
+    dpct = rng.integers(0, 11, MX_NL).astype(np.int64)
+    l = {"l_orderkey": lkeys, "l_extendedprice": cents / 100.0,
+         "l_discount": dpct / 100.0,
+         "l_shipdate": (cut + rng.integers(-300, 300, MX_NL)).astype(np.int32)}
+    enc = lambda v: orc.aocs_encode(v, MX_BS)
+    if text:
+        segs = [b"BUILDING", b"AUTOMOBILE", b"MACHINERY", b"HOUSEHOLD", b"FURNITURE"]
+        seg_col = (orc.aocs_encode_varlena([segs[int(x)] for x in c["c_mktsegment"]]),
+                   -1, MX_NC, 1)
+    else:
+        seg_col = (enc(c["c_mktsegment"].astype(np.int8)), 1, MX_NC, 0, 0, MX_BS)
+    cust = ctx.bind([(enc(c["c_custkey"]), 8, MX_NC, 0, 0, MX_BS), seg_col])
+    ordr = ctx.bind([(enc(o[k]), w, MX_NO, 0, 0, MX_BS)
+                     for k, w in (("o_orderkey", 8), ("o_custkey", 8),
+                                  ("o_orderdate", 4), ("o_shippriority", 4))])
+    if rle:
+        key_stream = orc.aocs_encode_rle(lkeys, MX_BS)
+        # every block is one the fused probe reads in place: no block sends
+        # the column to materialize, so the run takes k_li_probe_agg_rle
+        cls = gx.rle_block_classes(key_stream)
+        assert len(cls) > 1 and (cls != gx.RLEBLK_UNFUSED).all()
+        key_col = (key_stream, 8, MX_NL, 1, 0, MX_BS)
+    else:
+        key_col = (enc(lkeys), 8, MX_NL, 0, 0, MX_BS)
+    a, b = (cents, dpct) if numeric else (l["l_extendedprice"], l["l_discount"])
+    li = ctx.bind([key_col, (enc(a), 8, MX_NL, 0, 0, MX_BS),
+                   (enc(b), 8, MX_NL, 0, 0, MX_BS),
+                   (enc(l["l_shipdate"]), 4, MX_NL, 0, 0, MX_BS)])
+    desc = {"dim": cust, "dim_key_col": 0,
+            "dim_filter": (1, "==", "BUILDING" if text else 0),
+            "mid": ordr, "mid_key_col": 0, "mid_fk_col": 1,
+            "mid_attr1_col": 2, "mid_attr2_col": 3, "mid_filter": (2, "<", cut),
+            "fact": li, "fact_key_col": 0, "fact_a_col": 1, "fact_b_col": 2,
+            "fact_filter": (3, ">", cut)}
+    return (c, o, l), (cust, ordr, li), desc, (cents, dpct)
+
+
+# the fused RLE probe is inner-only (LEFT OUTER materializes the key at
+# prepare, test_left_outer_rle_fact_key), so it has no outer forms
+MX_PROBE_FORMS = [(kind, wide, vm, outer)
+                  for kind in ("f64", "numeric", "rle")
+                  for wide in (False, True) for vm in (False, True)
+                  for outer in (False, True) if not (kind == "rle" and outer)]
+
+
+@pytest.mark.parametrize(
+    "kind,wide,vm,outer", MX_PROBE_FORMS,
+    ids=["-".join((k, "key8" if w else "key4", "vm" if v else "novm",
+                   "outer" if ou else "inner")) for k, w, v, ou in MX_PROBE_FORMS])
+def test_probe_dispatch_matrix(ctx, orc, kind, wide, vm, outer):
+    """One run per compiled form of the three probe kernels, against the
+    oracle on the visible rows: keys, attrs and counts exact, f64 revenue
+    rtol=1e-9, numeric numerators exact.  Under LEFT OUTER the matched groups
+    are the oracle's and the unmatched ones a numpy group-by of the misses."""
+    numeric = kind == "numeric"
+    (c, o, l), tables, desc, (cents, dpct) = _mx_plan(
+        ctx, orc, wide_okeys=wide, numeric=numeric, rle=kind == "rle")
+    cust, ordr, li = tables
+    hidden = np.random.default_rng(9).random(MX_NL) < 0.15 if vm else None
+    if vm:
+        li.set_visimap(hidden)
+        l = {k: v[~hidden] for k, v in l.items()}
+        cents, dpct = cents[~hidden], dpct[~hidden]
+    if outer:
+        desc = dict(desc, fact_join="left_outer")
+    q = ctx.q3_desc(desc)
+    if numeric:
+        ctx._chk(ctx._lib.gx_q3_set_numeric(q._q, 1))
+    got = q.run().result()
+    want = (orc.q3_numeric if numeric else orc.q3)(c, o, l)
+    assert len(want["l_orderkey"]) > 50
+    assert (want["l_orderkey"].max() >= 1 << 32) == wide
+    m = ~got["attrs_null"] if outer else np.ones(len(got["l_orderkey"]), bool)
+    np.testing.assert_array_equal(got["l_orderkey"][m], want["l_orderkey"])
+    np.testing.assert_array_equal(got["o_orderdate"][m], want["o_orderdate"])
+    np.testing.assert_array_equal(got["o_shippriority"][m], want["o_shippriority"])
+    np.testing.assert_array_equal(got["nitems"][m], want["nitems"])
+    if numeric:
+        np.testing.assert_array_equal(got["revenue_num"][m], want["revenue_num"])
+    else:
+        np.testing.assert_allclose(got["revenue"][m], want["revenue"], rtol=1e-9)
+    assert q.stats()["probe_hits"] == int(want["nitems"].sum())
+    if outer:
+        miss = (l["l_shipdate"] > gx.CUTOFF_19950315) & \
+               ~np.isin(l["l_orderkey"], want["l_orderkey"])
+        uk, inv, uc = np.unique(l["l_orderkey"][miss], return_inverse=True,
+                                return_counts=True)
+        assert len(uk) > 50 and not got["key_is_null"].any()
+        np.testing.assert_array_equal(got["l_orderkey"][~m], uk)
+        np.testing.assert_array_equal(got["nitems"][~m], uc)
+        if numeric:
+            unum = np.zeros(len(uk), np.int64)
+            np.add.at(unum, inv, cents[miss] * (100 - dpct[miss]))
+            np.testing.assert_array_equal(got["revenue_num"][~m], unum)
+        else:
+            urev = np.zeros(len(uk))
+            np.add.at(urev, inv, l["l_extendedprice"][miss] * (1.0 - l["l_discount"][miss]))
+            np.testing.assert_allclose(got["revenue"][~m], urev, rtol=1e-9)
+    q.free()
+    for t in (li, ordr, cust):
+        t.free()
+
+
+# the bitmap form has no key set, hence one build kernel per predicate
+MX_DIM_FORMS = [(pred, form, wide)
+                for pred in ("compare", "textmask")
+                for form, wide in (("bitmap", False), ("hash", False), ("hash", True))]
+
+
+@pytest.mark.parametrize(
+    "pred,form,wide", MX_DIM_FORMS,
+    ids=["-".join((p, f) + (("set8" if w else "set4",) if f == "hash" else ()))
+         for p, f, w in MX_DIM_FORMS])
+def test_dim_dispatch_matrix(ctx, orc, monkeypatch, pred, form, wide):
+    """One run per compiled form of the customer count/build kernels: int8
+    compare or text-mask row predicate, bitmap or bloom + hash set with 4- or
+    8-byte set keys (dim keys past 2^32); hidden dim rows on top.  Which
+    membership form the run read is pinned through dim_mode()."""
+    monkeypatch.delenv("GX_FORCE_MOTION", raising=False)
+    monkeypatch.setenv("GX_DIM_BITMAP", "1" if form == "bitmap" else "0")
+    (c, o, l), tables, desc, _ = _mx_plan(ctx, orc, wide_ckeys=wide,
+                                          text=pred == "textmask")
+    cust, ordr, li = tables
+    hidden = np.zeros(MX_NC, bool)
+    hidden[[0, 65, MX_NC - 1]] = True          # BUILDING rows, first and last key among them
+    cust.set_visimap(hidden)
+    q = ctx.q3_desc(desc).run()
+    got = q.result()
+    assert q.dim_mode() == (1 if form == "bitmap" else 0)
+    want = orc.q3({k: v[~hidden] for k, v in c.items()}, o, l)
+    assert len(want["l_orderkey"]) > 50
+    assert (c["c_custkey"].max() >= 1 << 32) == wide
+    np.testing.assert_array_equal(got["l_orderkey"], want["l_orderkey"])
+    np.testing.assert_array_equal(got["o_orderdate"], want["o_orderdate"])
+    np.testing.assert_array_equal(got["nitems"], want["nitems"])
+    np.testing.assert_allclose(got["revenue"], want["revenue"], rtol=1e-9)
+    q.free()
+    for t in (li, ordr, cust):
+        t.free()

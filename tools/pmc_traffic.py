@@ -35,7 +35,6 @@ def probe_kernel_fetch_bytes(sf, steps=2, timeout=480):
     outdir = tempfile.mkdtemp(prefix="gxpmc_", dir="/tmp")
     env = dict(os.environ)
     env["TMPDIR"] = "/tmp"
-    env.pop("GX_PROBE_VARIANT", None)
     cmd = [rocprof, "--pmc", "FETCH_SIZE", "--output-format", "csv",
            "-d", outdir, "-o", "t",
            "--", sys.executable, bench, "--steps", str(steps),
