@@ -94,6 +94,42 @@ class _Filter(ctypes.Structure):
                 ("literal", ctypes.c_int64)]
 
 
+GB_MAX_KEYS, GB_MAX_AGGS, MAX_EXTRA_QUALS = 4, 8, 4
+AGG_COUNT_STAR, AGG_COUNT, AGG_SUM, AGG_MIN, AGG_MAX = 0, 1, 2, 3, 4
+_AGG_FNS = {"count*": AGG_COUNT_STAR, "count": AGG_COUNT, "sum": AGG_SUM,
+            "min": AGG_MIN, "max": AGG_MAX}
+
+
+class _Agg(ctypes.Structure):
+    _fields_ = [("fn", ctypes.c_int32), ("col", ctypes.c_int32),
+                ("is_f64", ctypes.c_int32), ("_pad", ctypes.c_int32)]
+
+
+class _GbDesc(ctypes.Structure):
+    _fields_ = [("t", ctypes.c_void_p),
+                ("nkeys", ctypes.c_int32),
+                ("key_cols", ctypes.c_int32 * GB_MAX_KEYS),
+                ("naggs", ctypes.c_int32),
+                ("aggs", _Agg * GB_MAX_AGGS),
+                ("nquals", ctypes.c_int32),
+                ("quals", _Filter * MAX_EXTRA_QUALS),
+                ("max_groups", ctypes.c_int64)]
+
+
+class _GbResult(ctypes.Structure):
+    _fields_ = [("ngroups", ctypes.c_int64),
+                ("nkeys", ctypes.c_int32), ("naggs", ctypes.c_int32),
+                ("keys", ctypes.c_void_p), ("key_null", ctypes.c_void_p),
+                ("aggs", ctypes.c_void_p), ("agg_null", ctypes.c_void_p)]
+
+
+class _GbdStats(ctypes.Structure):
+    _fields_ = [("ms_kernel", ctypes.c_double),
+                ("rows_in", ctypes.c_int64), ("rows_pass", ctypes.c_int64),
+                ("rows_lds", ctypes.c_int64), ("rows_global", ctypes.c_int64),
+                ("groups", ctypes.c_int64)]
+
+
 class _TblLayout(ctypes.Structure):
     _fields_ = [("key_width", ctypes.c_int32), ("interpolated", ctypes.c_int32),
                 ("slots", ctypes.c_uint64), ("kmin", ctypes.c_int64),
@@ -262,6 +298,22 @@ def _load():
                                ctypes.POINTER(ctypes.POINTER(_Group)),
                                ctypes.POINTER(ctypes.c_int64),
                                ctypes.POINTER(_TblLayout)]
+    lib.gx_groupby_desc.argtypes = [ctypes.c_void_p, ctypes.POINTER(_GbDesc),
+                                    ctypes.POINTER(_GbResult),
+                                    ctypes.POINTER(_GbdStats)]
+    lib.gx_test_groupby_desc.argtypes = [ctypes.c_void_p,
+                                         ctypes.POINTER(_GbDesc), ctypes.c_int,
+                                         ctypes.c_int,
+                                         ctypes.POINTER(_GbResult),
+                                         ctypes.POINTER(_GbdStats)]
+    lib.gx_gb_result_free.restype = None
+    lib.gx_gb_result_free.argtypes = [ctypes.POINTER(_GbResult)]
+    lib.gx_gb_lds_groups.restype = ctypes.c_int32
+    lib.gx_gb_lds_groups.argtypes = [ctypes.c_int]
+    lib.gx_selftest_gb_sort.restype = ctypes.c_int
+    lib.gx_selftest_gb_sort.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
+                                        ctypes.c_int64, ctypes.c_int,
+                                        ctypes.c_void_p]
     lib.gx_selftest_motion_layout.restype = ctypes.c_int
     lib.gx_selftest_motion_layout.argtypes = [
         ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
@@ -334,6 +386,28 @@ def unmatched_bound(nrows, lmin, lmax):
     only, no GPU)."""
     return int(lib().gx_selftest_unmatched_bound(
         int(nrows), int(lmin) & (2**64 - 1), int(lmax) & (2**64 - 1)))
+
+
+def gb_lds_groups(naggs):
+    """Groups one workgroup's LDS table of the descriptor GROUP BY holds for
+    a call with naggs aggregates (host only, no GPU)."""
+    return int(lib().gx_gb_lds_groups(naggs))
+
+
+def gb_sort(keys, key_null):
+    """The result order of the descriptor GROUP BY (host only, no GPU): the
+    permutation that sorts (n, nkeys) keys / key_null lexicographically by
+    column, ascending, NULLS LAST per column, stable."""
+    keys = np.ascontiguousarray(keys, np.int64)
+    key_null = np.ascontiguousarray(key_null, np.uint8)
+    assert keys.ndim == 2 and keys.shape == key_null.shape
+    n, nkeys = keys.shape
+    perm = np.zeros(n, np.int64)
+    rc = lib().gx_selftest_gb_sort(keys.ctypes.data, key_null.ctypes.data, n,
+                                   nkeys, perm.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"gx_selftest_gb_sort: bad arguments ({rc})")
+    return perm
 
 
 RLEBLK_UNFUSED, RLEBLK_NOBITMAP, RLEBLK_VARINT, RLEBLK_FIXED2 = 0, 1, 2, 3
@@ -498,6 +572,81 @@ class Context:
         if stats:
             return res, {f: getattr(st, f) for f, _ in st._fields_}
         return res
+
+    def _gb_desc(self, table, keys, aggs, quals, max_groups):
+        d = _GbDesc()
+        d.t = table._t
+        d.nkeys = len(keys)
+        for i, c in enumerate(keys[:GB_MAX_KEYS]):
+            d.key_cols[i] = c
+        d.naggs = len(aggs)
+        for i, spec in enumerate(aggs[:GB_MAX_AGGS]):
+            fn, col = spec[0], spec[1]
+            d.aggs[i] = _Agg(fn if isinstance(fn, int) else _AGG_FNS[fn],
+                             -1 if col is None else col,
+                             1 if len(spec) > 2 and spec[2] else 0, 0)
+        d.nquals = len(quals)
+        for i, (col, op, lit) in enumerate(quals[:MAX_EXTRA_QUALS]):
+            d.quals[i] = _Filter(col, _opcode(op), int(lit))
+        d.max_groups = max_groups
+        return d
+
+    def _gb_result(self, res, aggs):
+        """gx_gb_result -> numpy; frees the native arrays."""
+        n, nk, na = res.ngroups, res.nkeys, res.naggs
+
+        def grab(ptr, count, dtype):
+            if not count:
+                return np.zeros(0, dtype)
+            raw = ctypes.string_at(ptr, count * np.dtype(dtype).itemsize)
+            return np.frombuffer(raw, dtype).copy()
+        keys = grab(res.keys, n * nk, np.int64).reshape(n, nk)
+        key_null = grab(res.key_null, n * nk, np.uint8).reshape(n, nk)
+        words = grab(res.aggs, n * na, np.uint64).reshape(n, na)
+        agg_null = grab(res.agg_null, n * na, np.uint8).reshape(n, na)
+        self._lib.gx_gb_result_free(ctypes.byref(res))
+        cols = [np.ascontiguousarray(words[:, j]).view(
+                    np.float64 if len(spec) > 2 and spec[2] else np.int64)
+                for j, spec in enumerate(aggs)]
+        return {"ngroups": n, "keys": keys, "key_null": key_null.astype(np.bool_),
+                "aggs": cols, "agg_null": agg_null.astype(np.bool_)}
+
+    def groupby_desc(self, table, keys, aggs, quals=(), max_groups=0,
+                     stats=False):
+        """Descriptor-form GROUP BY (gx_groupby_desc).  keys: up to 4 integer
+        column indexes (none = a plain aggregate); aggs: 1..8 tuples (fn,
+        col[, is_f64]) with fn in 'count*', 'count', 'sum', 'min', 'max' (col
+        None for 'count*'); quals: AND-ed (col, op, literal) triples.
+        Returns a dict: keys (ngroups, nkeys) int64, key_null bool, aggs = one
+        array per aggregate (float64 where is_f64, else int64), agg_null
+        (ngroups, naggs) bool; groups sorted by key, NULLS LAST per column.
+        With stats=True returns (result, gx_gbd_stats as a dict)."""
+        return self._groupby_desc(table, keys, aggs, quals, max_groups, stats,
+                                  None)
+
+    def test_groupby_desc(self, table, keys, aggs, quals=(), max_groups=0,
+                          stats=False, grid=0, wide_rowid=False):
+        """groupby_desc through the test seam: grid workgroups scan the input
+        (0 = production) and wide_rowid forces the 8-byte slot word."""
+        return self._groupby_desc(table, keys, aggs, quals, max_groups, stats,
+                                  (grid, 1 if wide_rowid else 0))
+
+    def _groupby_desc(self, table, keys, aggs, quals, max_groups, stats, seam):
+        keys, aggs, quals = list(keys), list(aggs), list(quals)
+        d = self._gb_desc(table, keys, aggs, quals, max_groups)
+        res, st = _GbResult(), _GbdStats()
+        if seam is None:
+            rc = self._lib.gx_groupby_desc(self._h, ctypes.byref(d),
+                                           ctypes.byref(res), ctypes.byref(st))
+        else:
+            rc = self._lib.gx_test_groupby_desc(
+                self._h, ctypes.byref(d), seam[0], seam[1], ctypes.byref(res),
+                ctypes.byref(st))
+        self._chk(rc)
+        out = self._gb_result(res, aggs)
+        if stats:
+            return out, {f: getattr(st, f) for f, _ in st._fields_}
+        return out
 
     def test_gb_partial(self, table, key_col, val_col, nsegs):
         """Partial agg + partition kernels on one GPU: returns (counts,

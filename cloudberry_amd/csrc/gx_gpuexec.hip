@@ -2600,6 +2600,379 @@ k_topn(const int64_t *okey, const int32_t *odate,
     }
 }
 
+/* ================= descriptor-form GROUP BY ================= */
+/* gx_groupby_desc (include/gpuexec.h): several integer key columns, a list of
+ * aggregates, AND-ed quals; one scan kernel.
+ *
+ * GROUP IDENTITY IS A REPRESENTATIVE ROW.  A table slot holds row + 1 of the
+ * first row that claimed it (CAS from 0; u32 or u64 word, template ST).  A
+ * thread that meets an occupied slot compares its own key columns and
+ * validity with those of the slot's row and walks on if they differ.  The
+ * input is immutable, so a claimed slot's key is visible the moment the claim
+ * is: no key value is reserved and key columns cost no table bytes.
+ *
+ * ACCUMULATORS are 8-byte words, aword[j] the first word of aggregate j;
+ * SUM, MIN and MAX carry a second word counting their non-NULL inputs (the
+ * result is NULL when it is 0).  Every word's identity is the all-zero word,
+ * so a memset (global) or a zero fill (LDS) BEFORE the scan initialises a
+ * table: counts and integer sums add from 0, a float8 sum from +0.0, and MIN
+ * and MAX are both an unsigned atomic max over an order-preserving image of
+ * the value (MIN: of its complement), which starts at 0 = below every image.
+ * Claim-time initialisation would be wrong: a second thread can match a slot
+ * before the claimer's stores land.
+ *
+ * LDS STAGE (template LDS).  Each workgroup keeps a table of the same shape
+ * in LDS (lds_slots slots), inserts and accumulates there with LDS atomics,
+ * and merges every occupied slot into the global table when its rows are
+ * done: one insert plus one atomic per non-identity word per group per
+ * workgroup, instead of one set per row on the group's global address.  A
+ * row that finds neither its group nor a free slot within GBD_LDS_PROBE
+ * steps accumulates directly in the global table, and a workgroup that has
+ * seen giveup_rows rows (GBD_GIVEUP_ROWS) with more than 3 of 4 missing stops
+ * consulting its LDS table (high cardinality: it is full of other groups). */
+
+struct gbd_col {
+    const uint8_t *s;          /* Orig stream, or the flat materialization */
+    const uint8_t *val;        /* validity bytes (1 = non-null), or nullptr */
+    gx_colmeta m;
+};
+
+/* per-aggregate row ops (aop) and per-word merge ops (wop) */
+enum { GBD_COUNT_STAR = 0, GBD_COUNT, GBD_SUM_INT, GBD_SUM_F64,
+       GBD_MAX_INT, GBD_MIN_INT, GBD_MAX_F64, GBD_MIN_F64 };
+enum { GBD_W_ADD = 0, GBD_W_FADD = 1, GBD_W_MAX = 2 };
+
+static constexpr int GBD_MAX_WORDS = 2 * GX_GB_MAX_AGGS;
+static constexpr int GBD_LDS_PROBE = 8;
+static constexpr unsigned GBD_GIVEUP_ROWS = 4096;   /* GX_GB_GIVEUP_ROWS */
+static constexpr int GBD_LDS_BYTES = 40960;   /* 3 workgroups per 160-KiB CU */
+
+struct gbd_args {
+    gbd_col key[GX_GB_MAX_KEYS];
+    gbd_col agg[GX_GB_MAX_AGGS];
+    gbd_col qual[GX_MAX_EXTRA_QUALS];
+    int64_t qlit[GX_MAX_EXTRA_QUALS];
+    int32_t qop[GX_MAX_EXTRA_QUALS];
+    int32_t aop[GX_GB_MAX_AGGS];
+    int32_t aword[GX_GB_MAX_AGGS];
+    int32_t wop[GBD_MAX_WORDS];
+    int32_t nkeys, naggs, nquals, awords;
+    int64_t nrows;
+    const uint8_t *vmap;
+    uint32_t lds_slots;        /* power of two */
+    uint32_t giveup_rows;      /* rows a workgroup tries before it may stop */
+};
+
+/* sign-extended integer datum of any supported width */
+__device__ __forceinline__ int64_t gbd_load(const gbd_col &c, int64_t row)
+{
+    switch (c.m.width)
+    {
+        case 1: return gx_col_get<int8_t>(c.s, c.m, row);
+        case 2: return gx_col_get<int16_t>(c.s, c.m, row);
+        case 4: return gx_col_get<int32_t>(c.s, c.m, row);
+        default: return gx_col_get<int64_t>(c.s, c.m, row);
+    }
+}
+
+__device__ __forceinline__ bool gbd_isnull(const gbd_col &c, int64_t row)
+{
+    return c.val != nullptr && !c.val[row];
+}
+
+/* Order-preserving u64 image of a float8 under float8_cmp_internal: NaNs
+ * canonicalised to one value above +inf, negative values reversed.  -0 and
+ * +0 keep distinct images (-0 below +0); they compare equal in the reference,
+ * so either is a right answer. */
+GX_HD uint64_t gbd_f64_image(uint64_t bits)
+{
+    if ((bits & 0x7FFFFFFFFFFFFFFFULL) > 0x7FF0000000000000ULL)
+        bits = 0x7FF8000000000000ULL;
+    return (bits >> 63) ? ~bits : bits | (1ULL << 63);
+}
+
+GX_HD uint64_t gbd_f64_unimage(uint64_t img)
+{
+    return (img >> 63) ? img ^ (1ULL << 63) : ~img;
+}
+
+/* key values (0 where NULL), null bits and hash of one row */
+__device__ __forceinline__ uint64_t gbd_row_keys(const gbd_args &a, int64_t row,
+                                                 int64_t (&kv)[GX_GB_MAX_KEYS],
+                                                 unsigned &kn)
+{
+    uint64_t h = 0x9E3779B97F4A7C15ULL;
+    kn = 0;
+#pragma unroll
+    for (int k = 0; k < GX_GB_MAX_KEYS; k++)
+    {
+        kv[k] = 0;
+        if (k < a.nkeys)
+        {
+            bool isnull = gbd_isnull(a.key[k], row);
+            kv[k] = isnull ? 0 : gbd_load(a.key[k], row);
+            kn |= (unsigned) isnull << k;
+            h = gx_hmix64((h ^ (uint64_t) kv[k]) +
+                          (isnull ? 0xD6E8FEB86659FD93ULL : 0ULL));
+        }
+    }
+    return h;
+}
+
+/* NOT DISTINCT equality, column by column, with the keys of row r */
+__device__ __forceinline__ bool gbd_keys_eq(const gbd_args &a,
+                                            const int64_t (&kv)[GX_GB_MAX_KEYS],
+                                            unsigned kn, int64_t r)
+{
+    bool eq = true;
+#pragma unroll
+    for (int k = 0; k < GX_GB_MAX_KEYS; k++)
+        if (k < a.nkeys)
+        {
+            bool rnull = gbd_isnull(a.key[k], r);
+            eq = eq && rnull == (bool) ((kn >> k) & 1) &&
+                 (rnull || gbd_load(a.key[k], r) == kv[k]);
+        }
+    return eq;
+}
+
+/* find or claim the global slot of the group of row i (keys kv/kn, hash h);
+ * ~0 and the error bit when the bounded walk runs out (more groups than the
+ * table was sized for) */
+template <typename ST>
+__device__ __forceinline__ uint64_t gbd_ginsert(const gbd_args &a, ST *trow,
+                                                uint64_t tmask, uint64_t h,
+                                                const int64_t (&kv)[GX_GB_MAX_KEYS],
+                                                unsigned kn, int64_t i, int *err)
+{
+    uint64_t slot = h & tmask;
+    for (uint64_t n = 0; n <= tmask; n++)
+    {
+        /* a slot only ever goes 0 -> row + 1: a non-zero read is final, a
+         * zero one is settled by the CAS */
+        ST cur = trow[slot];
+        if (cur == (ST) 0)
+        {
+            cur = atomicCAS(&trow[slot], (ST) 0, (ST) (i + 1));
+            if (cur == (ST) 0) return slot;
+        }
+        if (gbd_keys_eq(a, kv, kn, (int64_t) cur - 1)) return slot;
+        slot = (slot + 1) & tmask;
+    }
+    atomicOr(err, 1);
+    return ~0ULL;
+}
+
+/* row i's transitions on the accumulator words w of its group; w is an LDS
+ * or a global pointer at the two call sites, so each gets its own atomics */
+__device__ __forceinline__ void gbd_accum(const gbd_args &a, int64_t i,
+                                          unsigned long long *w)
+{
+#pragma unroll
+    for (int j = 0; j < GX_GB_MAX_AGGS; j++)
+    {
+        if (j >= a.naggs) continue;
+        const gbd_col &c = a.agg[j];
+        const int op = a.aop[j];
+        unsigned long long *p = w + a.aword[j];
+        if (op == GBD_COUNT_STAR) { atomicAdd(p, 1ULL); continue; }
+        if (gbd_isnull(c, i)) continue;              /* strict transitions */
+        if (op == GBD_COUNT) { atomicAdd(p, 1ULL); continue; }
+        switch (op)
+        {
+            case GBD_SUM_INT:
+                atomicAdd(p, (unsigned long long) gbd_load(c, i));
+                break;
+            case GBD_SUM_F64:
+                atomicAdd((double *) p, gx_col_get<double>(c.s, c.m, i));
+                break;
+            case GBD_MAX_INT:
+                atomicMax(p, (unsigned long long) gbd_load(c, i) ^ (1ULL << 63));
+                break;
+            case GBD_MIN_INT:
+                atomicMax(p, ~((unsigned long long) gbd_load(c, i) ^ (1ULL << 63)));
+                break;
+            case GBD_MAX_F64:
+                atomicMax(p, (unsigned long long) gbd_f64_image(
+                                 gx_col_get<uint64_t>(c.s, c.m, i)));
+                break;
+            default:
+                atomicMax(p, (unsigned long long) ~gbd_f64_image(
+                                 gx_col_get<uint64_t>(c.s, c.m, i)));
+                break;
+        }
+        atomicAdd(p + 1, 1ULL);
+    }
+}
+
+/* stats: [0] rows passing visimap + quals, [1] rows accumulated in LDS */
+template <typename ST, bool LDS>
+__global__ void __launch_bounds__(TPB)
+k_groupby_desc(const gbd_args a, ST *trow, unsigned long long *tacc,
+               uint64_t tmask, unsigned long long *stats, int *err)
+{
+    extern __shared__ unsigned long long gbd_smem[];
+    __shared__ unsigned int s_seen, s_miss;
+    const uint32_t L = a.lds_slots;
+    unsigned long long *lacc = gbd_smem;
+    ST *lrow = (ST *) (gbd_smem + (size_t) L * a.awords);
+    if (LDS)
+    {
+        for (uint32_t s = threadIdx.x; s < L * (uint32_t) a.awords; s += TPB)
+            lacc[s] = 0ULL;
+        for (uint32_t s = threadIdx.x; s < L; s += TPB) lrow[s] = (ST) 0;
+        if (threadIdx.x == 0) { s_seen = 0; s_miss = 0; }
+        __syncthreads();
+    }
+    unsigned long long n_pass = 0, n_lds = 0;
+    int64_t i = blockIdx.x * (int64_t) blockDim.x + threadIdx.x;
+    const int64_t stride = gridDim.x * (int64_t) blockDim.x;
+    for (; i < a.nrows; i += stride)
+    {
+        if (gx_vm_hidden(a.vmap, i)) continue;
+        /* the key loads go out with the qual loads, not behind their
+         * outcome: one memory round trip per row instead of two */
+        int64_t kv[GX_GB_MAX_KEYS];
+        unsigned kn;
+        const uint64_t h = gbd_row_keys(a, i, kv, kn);
+        bool pass = true;
+#pragma unroll
+        for (int q = 0; q < GX_MAX_EXTRA_QUALS; q++)
+            if (q < a.nquals)
+                pass = pass && !gbd_isnull(a.qual[q], i) &&   /* NULL fails */
+                       gx_cmp<int64_t>(a.qop[q], gbd_load(a.qual[q], i),
+                                       a.qlit[q]);
+        if (!pass) continue;
+        n_pass++;
+        bool done = false;
+        if (LDS)
+        {
+            /* racy read on purpose: either answer is correct */
+            const unsigned seen = s_seen, miss = s_miss;
+            if (!(seen >= a.giveup_rows && miss > seen - (seen >> 2)))
+            {
+                uint32_t ls = (uint32_t) (h >> 32) & (L - 1);
+                for (int p = 0; p < GBD_LDS_PROBE; p++)
+                {
+                    ST cur = __hip_atomic_load(&lrow[ls], __ATOMIC_RELAXED,
+                                               __HIP_MEMORY_SCOPE_WORKGROUP);
+                    if (cur == (ST) 0)
+                    {
+                        cur = atomicCAS(&lrow[ls], (ST) 0, (ST) (i + 1));
+                        if (cur == (ST) 0) { done = true; break; }
+                    }
+                    if (gbd_keys_eq(a, kv, kn, (int64_t) cur - 1))
+                    { done = true; break; }
+                    ls = (ls + 1) & (L - 1);
+                }
+                if (done)
+                {
+                    gbd_accum(a, i, lacc + (size_t) ls * a.awords);
+                    n_lds++;
+                }
+                /* one pair of counter updates per wave and iteration */
+                const unsigned long long act = __ballot(1);
+                const unsigned long long mis = __ballot(!done);
+                if ((int) (threadIdx.x & 63) == __ffsll((long long) act) - 1)
+                {
+                    atomicAdd(&s_seen, (unsigned) __popcll(act));
+                    if (mis) atomicAdd(&s_miss, (unsigned) __popcll(mis));
+                }
+            }
+        }
+        if (!done)
+        {
+            uint64_t slot = gbd_ginsert<ST>(a, trow, tmask, h, kv, kn, i, err);
+            if (slot != ~0ULL) gbd_accum(a, i, tacc + slot * a.awords);
+        }
+    }
+    if (LDS)
+    {
+        __syncthreads();
+        for (uint32_t s = threadIdx.x; s < L; s += TPB)
+        {
+            const ST r1 = lrow[s];
+            if (r1 == (ST) 0) continue;
+            const int64_t r = (int64_t) r1 - 1;
+            int64_t kv[GX_GB_MAX_KEYS];
+            unsigned kn;
+            const uint64_t h = gbd_row_keys(a, r, kv, kn);
+            uint64_t slot = gbd_ginsert<ST>(a, trow, tmask, h, kv, kn, r, err);
+            if (slot == ~0ULL) continue;
+            unsigned long long *g = tacc + slot * a.awords;
+            const unsigned long long *l = lacc + (size_t) s * a.awords;
+#pragma unroll
+            for (int w = 0; w < GBD_MAX_WORDS; w++)
+            {
+                if (w >= a.awords) continue;
+                const unsigned long long v = l[w];
+                if (v == 0ULL) continue;              /* still the identity */
+                if (a.wop[w] == GBD_W_ADD) atomicAdd(&g[w], v);
+                else if (a.wop[w] == GBD_W_FADD)
+                    atomicAdd((double *) &g[w], __longlong_as_double((long long) v));
+                else atomicMax(&g[w], v);
+            }
+        }
+    }
+    gx_wave_count_add(stats + 0, n_pass);
+    gx_wave_count_add(stats + 1, n_lds);
+}
+
+/* Compact the occupied slots: representative row -> sign-extended keys and
+ * null flags, accumulator words copied.  Each workgroup counts the keeps of
+ * its 256-slot tile and claims its output region with ONE cursor atomic
+ * (k_extract's way).  Groups past cap are counted, not written; the host
+ * turns cursor > cap into an error. */
+template <typename ST>
+__global__ void __launch_bounds__(TPB)
+k_gbd_extract(const gbd_args a, const ST *trow, const unsigned long long *tacc,
+              uint64_t tslots, int64_t *okeys, uint8_t *oknull,
+              unsigned long long *oacc, unsigned long long *cursor, int64_t cap)
+{
+    constexpr int NW = TPB / 64;
+    __shared__ unsigned long long s_off[NW];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long below = (lane == 0) ? 0ULL : (~0ULL >> (64 - lane));
+    for (uint64_t base = (uint64_t) blockIdx.x * TPB; base < tslots;
+         base += (uint64_t) gridDim.x * TPB)
+    {
+        const uint64_t i = base + threadIdx.x;
+        const ST r1 = (i < tslots) ? trow[i] : (ST) 0;
+        const unsigned long long m = __ballot(r1 != (ST) 0);
+        if (lane == 0) s_off[wave] = (unsigned long long) __popcll(m);
+        __syncthreads();
+        if (threadIdx.x == 0)
+        {
+            unsigned long long tot = 0;
+            for (int w = 0; w < NW; w++) tot += s_off[w];
+            unsigned long long b = tot ? atomicAdd(cursor, tot) : 0ULL;
+            for (int w = 0; w < NW; w++)
+            {
+                unsigned long long c = s_off[w];
+                s_off[w] = b;
+                b += c;
+            }
+        }
+        __syncthreads();
+        const unsigned long long w = s_off[wave] + __popcll(m & below);
+        if (r1 != (ST) 0 && w < (unsigned long long) cap)
+        {
+            const int64_t r = (int64_t) r1 - 1;
+#pragma unroll
+            for (int k = 0; k < GX_GB_MAX_KEYS; k++)
+                if (k < a.nkeys)
+                {
+                    bool isnull = gbd_isnull(a.key[k], r);
+                    okeys[w * a.nkeys + k] = isnull ? 0 : gbd_load(a.key[k], r);
+                    oknull[w * a.nkeys + k] = (uint8_t) isnull;
+                }
+            for (int x = 0; x < a.awords; x++)
+                oacc[w * a.awords + x] = tacc[i * a.awords + x];
+        }
+        __syncthreads();
+    }
+}
+
 /* ================= host-side structures ================= */
 
 struct gx_col {
@@ -3989,6 +4362,10 @@ static gx_status gb_flat(gx_ctx *ctx, const gx_col &c, devbuf &flat,
         hipLaunchKernelGGL(k_decode_dense<int32_t>, dim3(GRID), dim3(64), 0,
                            ctx->stream, c.dstream, c.ddir, c.nblocks, n,
                            (int32_t *) dv, val.as<uint8_t>(), errb.as<int>());
+    else if (c.m.width == 2)
+        hipLaunchKernelGGL(k_decode_dense<int16_t>, dim3(GRID), dim3(64), 0,
+                           ctx->stream, c.dstream, c.ddir, c.nblocks, n,
+                           (int16_t *) dv, val.as<uint8_t>(), errb.as<int>());
     else
         hipLaunchKernelGGL(k_decode_dense<int8_t>, dim3(GRID), dim3(64), 0,
                            ctx->stream, c.dstream, c.ddir, c.nblocks, n,
@@ -6252,10 +6629,359 @@ extern "C" gx_status gx_q3_free(gx_q3 *q)
 
 extern "C" void gx_free(void *p) { free(p); }
 
+/* ---- descriptor-form GROUP BY: host side (kernels: k_groupby_desc) ---- */
+
+/* LDS table slots of one workgroup, a power of two: sized for the worst
+ * slot of naggs aggregates (two words each and an 8-byte row word) within
+ * GBD_LDS_BYTES, whatever the aggregates' functions, so the capacity depends
+ * on naggs alone. */
+static uint32_t gbd_lds_slots(int naggs)
+{
+    uint32_t slots = 1024;
+    while (slots > 1 && (size_t) slots * (16 * (size_t) naggs + 8) > GBD_LDS_BYTES)
+        slots >>= 1;
+    return slots;
+}
+
+extern "C" int32_t gx_gb_lds_groups(int naggs)
+{
+    if (naggs < 1 || naggs > GX_GB_MAX_AGGS) return 0;
+    return (int32_t) gbd_lds_slots(naggs);
+}
+
+/* the result order: (key_null, key) pairs column by column, ascending =
+ * lexicographic by key with NULLS LAST per column; stable */
+static void gbd_sort_perm(const int64_t *keys, const uint8_t *key_null,
+                          int64_t n, int nkeys, int64_t *perm)
+{
+    for (int64_t i = 0; i < n; i++) perm[i] = i;
+    std::stable_sort(perm, perm + n, [&](int64_t x, int64_t y) {
+        for (int k = 0; k < nkeys; k++)
+        {
+            uint8_t nx = key_null[x * nkeys + k], ny = key_null[y * nkeys + k];
+            if (nx != ny) return nx < ny;
+            int64_t kx = keys[x * nkeys + k], ky = keys[y * nkeys + k];
+            if (kx != ky) return kx < ky;
+        }
+        return false;
+    });
+}
+
+extern "C" int gx_selftest_gb_sort(const int64_t *keys, const uint8_t *key_null,
+                                   int64_t n, int nkeys, int64_t *perm)
+{
+    if (n < 0 || nkeys < 1 || nkeys > GX_GB_MAX_KEYS || !perm ||
+        (n > 0 && (!keys || !key_null)))
+        return 1;
+    gbd_sort_perm(keys, key_null, n, nkeys, perm);
+    return 0;
+}
+
+extern "C" void gx_gb_result_free(gx_gb_result *r)
+{
+    if (!r) return;
+    free(r->keys); free(r->key_null); free(r->aggs); free(r->agg_null);
+    memset(r, 0, sizeof *r);
+}
+
+static gx_status gbd_invalid(gx_ctx *ctx, const char *fmt, long a, long b = 0)
+{
+    char buf[200];
+    snprintf(buf, sizeof buf, fmt, a, b);
+    set_err(ctx, "groupby_desc: %s", buf);
+    return GX_ERR_INVALID;
+}
+
+/* flattened inputs of one call; a table column used in several roles is
+ * materialized once */
+struct gbd_inputs {
+    devbuf flat[GX_GB_MAX_KEYS + GX_GB_MAX_AGGS + GX_MAX_EXTRA_QUALS];
+    devbuf val[GX_GB_MAX_KEYS + GX_GB_MAX_AGGS + GX_MAX_EXTRA_QUALS];
+    int nflat = 0;
+    std::map<int, gbd_col> done;
+};
+
+static gx_status gbd_bind_col(gx_ctx *ctx, const gx_table *t, int col,
+                              gbd_inputs &in, gbd_col *out)
+{
+    auto it = in.done.find(col);
+    if (it != in.done.end()) { *out = it->second; return GX_OK; }
+    gbd_col c{};
+    gx_status st = gb_flat(ctx, t->cols[col], in.flat[in.nflat], in.val[in.nflat],
+                           &c.s, &c.m, &c.val);
+    if (st != GX_OK) return st;
+    in.nflat++;
+    in.done[col] = c;
+    *out = c;
+    return GX_OK;
+}
+
+static bool gbd_int_width(int w) { return w == 1 || w == 2 || w == 4 || w == 8; }
+
+/* Validate, flatten, size, scan, extract, sort.  grid and wide come from the
+ * caller (production: GRID, nrows >= 2^32 - 1), lds from GX_GB_LDS, so the
+ * public call and the test entry run the same launches. */
+static gx_status gbd_run(gx_ctx *ctx, const gx_gb_desc *d, int grid, bool wide,
+                         bool lds, gx_gb_result *out, gx_gbd_stats *stats)
+{
+    if (!ctx || !d || !out) return GX_ERR_INVALID;
+    memset(out, 0, sizeof *out);
+    if (stats) memset(stats, 0, sizeof *stats);
+    const gx_table *t = d->t;
+    if (!t) { set_err(ctx, "groupby_desc: no table%s", ""); return GX_ERR_INVALID; }
+    const int ncols = (int) t->cols.size();
+    if (d->nkeys < 0 || d->nkeys > GX_GB_MAX_KEYS)
+        return gbd_invalid(ctx, "nkeys %ld outside 0..%ld", d->nkeys, GX_GB_MAX_KEYS);
+    if (d->naggs < 1 || d->naggs > GX_GB_MAX_AGGS)
+        return gbd_invalid(ctx, "naggs %ld outside 1..%ld", d->naggs, GX_GB_MAX_AGGS);
+    if (d->nquals < 0 || d->nquals > GX_MAX_EXTRA_QUALS)
+        return gbd_invalid(ctx, "nquals %ld outside 0..%ld", d->nquals, GX_MAX_EXTRA_QUALS);
+    if (d->max_groups < 0)
+        return gbd_invalid(ctx, "max_groups %ld is negative", (long) d->max_groups);
+    if (grid < 1) return gbd_invalid(ctx, "grid %ld", grid);
+
+    gbd_args a{};
+    a.nkeys = d->nkeys; a.naggs = d->naggs; a.nquals = d->nquals;
+    a.nrows = t->nrows;
+    a.vmap = t->dvmap;
+    /* validate everything before the first flatten launches */
+    for (int k = 0; k < d->nkeys; k++)
+    {
+        int c = d->key_cols[k];
+        if (c < 0 || c >= ncols)
+            return gbd_invalid(ctx, "key %ld: column %ld out of range", k, c);
+        if (!gbd_int_width(t->cols[c].m.width))
+            return gbd_invalid(ctx, "key %ld: column width %ld is not 1, 2, 4 or 8",
+                               k, t->cols[c].m.width);
+    }
+    int words = 0;
+    for (int j = 0; j < d->naggs; j++)
+    {
+        const gx_agg &g = d->aggs[j];
+        if (g.fn < GX_AGG_COUNT_STAR || g.fn > GX_AGG_MAX)
+            return gbd_invalid(ctx, "aggregate %ld: unknown fn %ld", j, g.fn);
+        a.aword[j] = words;
+        if (g.fn == GX_AGG_COUNT_STAR)
+        {
+            a.aop[j] = GBD_COUNT_STAR;
+            a.wop[words++] = GBD_W_ADD;
+            continue;
+        }
+        if (g.col < 0 || g.col >= ncols)
+            return gbd_invalid(ctx, "aggregate %ld: column %ld out of range", j, g.col);
+        int w = t->cols[g.col].m.width;
+        if (g.is_f64 ? w != 8 : !gbd_int_width(w))
+            return gbd_invalid(ctx, g.is_f64
+                                   ? "aggregate %ld: is_f64 on a column of width %ld"
+                                   : "aggregate %ld: column width %ld is not 1, 2, 4 or 8",
+                               j, w);
+        if (g.fn == GX_AGG_COUNT)
+        {
+            a.aop[j] = GBD_COUNT;
+            a.wop[words++] = GBD_W_ADD;
+            continue;
+        }
+        if (g.fn == GX_AGG_SUM && !g.is_f64 && w == 8)
+            return gbd_invalid(ctx, "aggregate %ld: SUM over a width-8 integer "
+                                    "column (%ld) is numeric in the reference", j, g.col);
+        if (g.fn == GX_AGG_SUM)
+        {
+            a.aop[j] = g.is_f64 ? GBD_SUM_F64 : GBD_SUM_INT;
+            a.wop[words++] = g.is_f64 ? GBD_W_FADD : GBD_W_ADD;
+        }
+        else
+        {
+            a.aop[j] = g.fn == GX_AGG_MAX ? (g.is_f64 ? GBD_MAX_F64 : GBD_MAX_INT)
+                                          : (g.is_f64 ? GBD_MIN_F64 : GBD_MIN_INT);
+            a.wop[words++] = GBD_W_MAX;
+        }
+        a.wop[words++] = GBD_W_ADD;                  /* non-NULL input count */
+    }
+    a.awords = words;
+    for (int q = 0; q < d->nquals; q++)
+    {
+        const gx_filter &f = d->quals[q];
+        if (f.col < 0 || f.col >= ncols)
+            return gbd_invalid(ctx, "qual %ld: column %ld out of range", q, f.col);
+        int w = t->cols[f.col].m.width;
+        if (!gbd_int_width(w))
+            return gbd_invalid(ctx, "qual %ld: column width %ld is not 1, 2, 4 or 8", q, w);
+        a.qop[q] = f.op;
+        a.qlit[q] = f.literal;
+        if (!gx_fold_filter(w, &a.qop[q], &a.qlit[q]))
+            return gbd_invalid(ctx, "qual %ld: op %ld outside 0..5", q, f.op);
+    }
+
+    /* sizing: the table holds up to `bound` groups at a fill of 1/2 at most */
+    const int64_t n = t->nrows;
+    const int64_t bound = std::max<int64_t>(
+        1, d->max_groups > 0 ? std::min<int64_t>(d->max_groups, n) : n);
+    const uint64_t tslots = (uint64_t) pow2_at_least(bound * 2);
+    const size_t sw = wide ? 8 : 4;
+    if (!wide && n >= (int64_t) UINT32_MAX)
+        return gbd_invalid(ctx, "%ld rows need the 8-byte slot word", (long) n);
+    gx_status st = hbm_budget_check(
+        ctx, tslots * (sw + (uint64_t) words * 8) +
+                 (uint64_t) bound * ((uint64_t) words * 8 + (uint64_t) d->nkeys * 9) + 64,
+        "groupby_desc table");
+    if (st != GX_OK) return st;
+
+    gbd_inputs in;
+    for (int k = 0; k < d->nkeys; k++)
+        if ((st = gbd_bind_col(ctx, t, d->key_cols[k], in, &a.key[k])) != GX_OK) return st;
+    for (int j = 0; j < d->naggs; j++)
+        if (d->aggs[j].fn != GX_AGG_COUNT_STAR &&
+            (st = gbd_bind_col(ctx, t, d->aggs[j].col, in, &a.agg[j])) != GX_OK) return st;
+    for (int q = 0; q < d->nquals; q++)
+        if ((st = gbd_bind_col(ctx, t, d->quals[q].col, in, &a.qual[q])) != GX_OK) return st;
+
+    hipStream_t s = ctx->stream;
+    a.lds_slots = gbd_lds_slots(d->naggs);
+    /* measurement knob: 0 = never give up */
+    int gr = env_int("GX_GB_GIVEUP_ROWS", (int) GBD_GIVEUP_ROWS);
+    a.giveup_rows = gr > 0 ? (uint32_t) gr : UINT32_MAX;
+    const size_t lds_bytes = lds ? (size_t) a.lds_slots * ((size_t) words * 8 + sw) : 0;
+    devbuf trow, tacc, misc, okeys, oknull, oacc;
+    HIP_CHK(ctx, trow.alloc(tslots * sw));
+    HIP_CHK(ctx, tacc.alloc(tslots * (size_t) words * 8));
+    HIP_CHK(ctx, misc.alloc(32));     /* [0..1] stats, [2] cursor, [3] err */
+    HIP_CHK(ctx, okeys.alloc((size_t) bound * std::max(d->nkeys, 1) * 8));
+    HIP_CHK(ctx, oknull.alloc((size_t) bound * std::max(d->nkeys, 1)));
+    HIP_CHK(ctx, oacc.alloc((size_t) bound * words * 8));
+    HIP_CHK(ctx, hipMemsetAsync(trow.p, 0, tslots * sw, s));
+    HIP_CHK(ctx, hipMemsetAsync(tacc.p, 0, tslots * (size_t) words * 8, s));
+    HIP_CHK(ctx, hipMemsetAsync(misc.p, 0, 32, s));
+    unsigned long long *dstat = misc.as<unsigned long long>();
+    int *derr = (int *) (dstat + 3);
+    evholder e0, e1;
+    HIP_CHK(ctx, e0.create()); HIP_CHK(ctx, e1.create());
+    HIP_CHK(ctx, hipEventRecord(e0, s));
+    by_width((int) sw, trow.p, [&](auto *rows) {
+        by_flag(lds, [&](auto use_lds) {
+            hipLaunchKernelGGL((k_groupby_desc<std::decay_t<decltype(*rows)>,
+                                               decltype(use_lds)::value>),
+                               dim3(grid), dim3(TPB), lds_bytes, s, a, rows,
+                               tacc.as<unsigned long long>(), tslots - 1,
+                               dstat, derr);
+        });
+    });
+    HIP_CHK(ctx, hipEventRecord(e1, s));
+    const int xgrid = (int) std::min<uint64_t>(GRID, (tslots + TPB - 1) / TPB);
+    by_width((int) sw, (const void *) trow.p, [&](auto *rows) {
+        hipLaunchKernelGGL(k_gbd_extract<std::decay_t<decltype(*rows)>>,
+                           dim3(xgrid), dim3(TPB), 0, s, a, rows,
+                           tacc.as<unsigned long long>(), tslots,
+                           okeys.as<int64_t>(), oknull.as<uint8_t>(),
+                           oacc.as<unsigned long long>(), dstat + 2, bound);
+    });
+    unsigned long long hm[4] = {0, 0, 0, 0};
+    HIP_CHK(ctx, hipMemcpyAsync(hm, misc.p, 32, hipMemcpyDeviceToHost, s));
+    HIP_CHK(ctx, hipStreamSynchronize(s));
+    HIP_CHK(ctx, hipGetLastError());
+    const int64_t ng = (int64_t) hm[2];
+    if ((hm[3] & 1) || ng > bound || (d->max_groups > 0 && ng > d->max_groups))
+    {
+        set_err(ctx, "groupby_desc: more groups than max_groups%s", "");
+        return GX_ERR_INVALID;
+    }
+    const int nk = d->nkeys, na = d->naggs;
+    std::vector<int64_t> hk((size_t) ng * nk);
+    std::vector<uint8_t> hn((size_t) ng * nk);
+    std::vector<unsigned long long> ha((size_t) ng * words);
+    if (ng)
+    {
+        if (nk)
+        {
+            HIP_CHK(ctx, hipMemcpyAsync(hk.data(), okeys.p, hk.size() * 8, hipMemcpyDeviceToHost, s));
+            HIP_CHK(ctx, hipMemcpyAsync(hn.data(), oknull.p, hn.size(), hipMemcpyDeviceToHost, s));
+        }
+        HIP_CHK(ctx, hipMemcpyAsync(ha.data(), oacc.p, ha.size() * 8, hipMemcpyDeviceToHost, s));
+        HIP_CHK(ctx, hipStreamSynchronize(s));
+    }
+    /* a plain aggregate returns its one group over no rows as well */
+    const int64_t nres = (nk == 0) ? 1 : ng;
+    std::vector<int64_t> perm((size_t) ng);
+    if (nk) gbd_sort_perm(hk.data(), hn.data(), ng, nk, perm.data());
+    else if (ng) perm[0] = 0;
+
+    out->keys = (int64_t *) calloc(std::max<size_t>((size_t) nres * nk, 1), 8);
+    out->key_null = (uint8_t *) calloc(std::max<size_t>((size_t) nres * nk, 1), 1);
+    out->aggs = (uint64_t *) calloc(std::max<size_t>((size_t) nres * na, 1), 8);
+    out->agg_null = (uint8_t *) calloc(std::max<size_t>((size_t) nres * na, 1), 1);
+    if (!out->keys || !out->key_null || !out->aggs || !out->agg_null)
+    {
+        gx_gb_result_free(out);
+        return GX_ERR_OOM;
+    }
+    out->ngroups = nres; out->nkeys = nk; out->naggs = na;
+    for (int64_t gi = 0; gi < nres; gi++)
+    {
+        /* acc stays all-identity for the plain aggregate over no rows */
+        static const unsigned long long zero[GBD_MAX_WORDS] = {};
+        const unsigned long long *acc = ng ? &ha[(size_t) perm[gi] * words] : zero;
+        for (int k = 0; k < nk; k++)
+        {
+            out->keys[gi * nk + k] = hk[(size_t) perm[gi] * nk + k];
+            out->key_null[gi * nk + k] = hn[(size_t) perm[gi] * nk + k];
+        }
+        for (int j = 0; j < na; j++)
+        {
+            const unsigned long long v = acc[a.aword[j]];
+            uint64_t r = v;
+            bool isnull = false;
+            if (a.aop[j] >= GBD_SUM_INT)
+            {
+                isnull = acc[a.aword[j] + 1] == 0;
+                switch (a.aop[j])
+                {
+                    case GBD_MAX_INT: r = v ^ (1ULL << 63); break;
+                    case GBD_MIN_INT: r = ~v ^ (1ULL << 63); break;
+                    case GBD_MAX_F64: r = gbd_f64_unimage(v); break;
+                    case GBD_MIN_F64: r = gbd_f64_unimage(~v); break;
+                    default: break;              /* sums: the word itself */
+                }
+            }
+            out->aggs[gi * na + j] = isnull ? 0 : r;
+            out->agg_null[gi * na + j] = (uint8_t) isnull;
+        }
+    }
+    if (stats)
+    {
+        float ms = 0;
+        (void) hipEventElapsedTime(&ms, e0, e1);
+        stats->ms_kernel = (double) ms;
+        stats->rows_in = n;
+        stats->rows_pass = (int64_t) hm[0];
+        stats->rows_lds = (int64_t) hm[1];
+        stats->rows_global = (int64_t) (hm[0] - hm[1]);
+        stats->groups = nres;
+    }
+    return GX_OK;
+}
+
+static bool gbd_env_lds() { return env_int("GX_GB_LDS", 1) != 0; }
+
+extern "C" gx_status gx_groupby_desc(gx_ctx *ctx, const gx_gb_desc *d,
+                                     gx_gb_result *out, gx_gbd_stats *stats)
+{
+    bool wide = d && d->t && d->t->nrows >= (int64_t) UINT32_MAX;
+    return gbd_run(ctx, d, GRID, wide, gbd_env_lds(), out, stats);
+}
+
+extern "C" gx_status gx_test_groupby_desc(gx_ctx *ctx, const gx_gb_desc *d,
+                                          int grid, int wide_rowid,
+                                          gx_gb_result *out, gx_gbd_stats *stats)
+{
+    bool wide = wide_rowid != 0 ||
+                (d && d->t && d->t->nrows >= (int64_t) UINT32_MAX);
+    return gbd_run(ctx, d, grid == 0 ? GRID : grid, wide, gbd_env_lds(), out, stats);
+}
+
 /* ABI self-description: struct sizes for cross-checking foreign-language
  * mirrors (ctypes tests; the PG extension's abi-check compiles against the
  * real header instead).  kind: 0 stats, 1 group, 2 kv_group, 3 desc,
- * 4 coldesc, 5 filter, 6 gb_stats, 7 test_tbl_layout. */
+ * 4 coldesc, 5 filter, 6 gb_stats, 7 test_tbl_layout, 8 gb_desc,
+ * 9 gb_result, 10 agg, 11 gbd_stats. */
 extern "C" int64_t gx_abi_sizeof(int kind)
 {
     switch (kind)
@@ -6268,6 +6994,10 @@ extern "C" int64_t gx_abi_sizeof(int kind)
         case 5: return (int64_t) sizeof(gx_filter);
         case 6: return (int64_t) sizeof(gx_gb_stats);
         case 7: return (int64_t) sizeof(gx_test_tbl_layout);
+        case 8: return (int64_t) sizeof(gx_gb_desc);
+        case 9: return (int64_t) sizeof(gx_gb_result);
+        case 10: return (int64_t) sizeof(gx_agg);
+        case 11: return (int64_t) sizeof(gx_gbd_stats);
         default: return -1;
     }
 }

@@ -341,7 +341,8 @@ void gx_free(void *p);
 
 /* ABI self-description for foreign mirrors (0 stats, 1 q3_group,
  * 2 kv_group, 3 q3_desc, 4 coldesc, 5 filter, 6 gb_stats,
- * 7 test_tbl_layout); -1 for unknown kinds */
+ * 7 test_tbl_layout, 8 gb_desc, 9 gb_result, 10 agg, 11 gbd_stats);
+ * -1 for unknown kinds */
 int64_t gx_abi_sizeof(int kind);
 
 /* ---- standalone hash GROUP BY (nodeAgg.c:2288 hash strategy over one key;
@@ -383,7 +384,97 @@ gx_status gx_groupby_dist(gx_ctx *ctx, const gx_table *t, int key_col,
                           int val_col, gx_kv_group **out, int64_t *ngroups,
                           gx_gb_stats *stats);
 
+/* ---- descriptor-form hash GROUP BY: what a planner lowers an Agg node over
+ * a SeqScan to (nodeAgg.c:2288 hash strategy, execScan.c:161-263 qual scan).
+ * Several integer key columns, a list of aggregates, AND-ed WHERE quals.
+ * One-stage only: the two-stage/Motion form is gx_groupby_dist's.
+ *
+ * Keys: 0..GX_GB_MAX_KEYS integer columns of width 1, 2, 4 or 8, format 0 or
+ *   format 1 (NULL bitmaps included; width 2 binds as format 1 only).
+ *   Grouping is NOT DISTINCT per column (execGrouping.c:436-495): (NULL, 1)
+ *   and (NULL, 2) are two groups, (NULL, 1) and (0, 1) are two groups.
+ *   Every int64 value is a legal key, INT64_MIN and 0 included: a group is
+ *   identified by a representative row, no key value is reserved.  Float
+ *   key columns are not supported.
+ * nkeys == 0: a plain aggregate (nodeAgg.c:2743 AGG_PLAIN): exactly one
+ *   group, also over an empty or fully filtered input, where COUNT is 0 and
+ *   every other aggregate NULL.  With nkeys > 0 an empty input gives zero
+ *   groups (hash agg emits no row, nodeAgg.c:2288).
+ * Aggregates (1..GX_GB_MAX_AGGS; `col` is ignored by COUNT(*)):
+ *   COUNT(*) counts rows, COUNT(col) non-NULL inputs (int8inc /
+ *   int8inc_any).  SUM, MIN and MAX are strict
+ *   (nodeAgg.c:836 advance_transition_function skips NULL inputs) and NULL
+ *   for a group without a non-NULL input (agg_null = 1, word 0).
+ *   SUM over an integer column of width 1, 2 or 4 is int64 with plain
+ *   two's-complement adds (int2_sum / int4_sum); SUM over
+ *   float8 (is_f64 = 1) is float8pl (float.c:769), in the order the rows
+ *   arrive, so the last bits may differ from a serial sum; SUM over a
+ *   width-8 integer column is numeric in the reference and GX_ERR_INVALID
+ *   here.  MIN and MAX take every integer width (int2larger ... int8smaller) and float8 in the reference's total order
+ *   (float8_cmp_internal, float.c): every NaN is equal and greater
+ *   than +inf; -0 and +0 compare equal and either may come back.  AVG is
+ *   deliberately no function: divide SUM by COUNT(col), as gx_q1 documents.
+ * Quals: AND-ed gx_filters over integer/date columns of width 1, 2, 4 or 8,
+ *   each folded as gx_filter describes; a NULL qual input fails the row
+ *   (execScan.c:241, ExecQual treats NULL as false).  The visimap is
+ *   honoured.
+ * max_groups: the planner's bound on the group count; sizes the hash table
+ *   (0 = bound by nrows).  More groups than that is GX_ERR_INVALID.
+ * Output: sorted on the host, lexicographic by key columns ascending, NULLS
+ *   LAST per column (PG's default ASC).
+ * GX_ERR_INVALID names the offending item in gx_last_error: a bad column
+ *   index, width, fn or count; is_f64 on a column that is not 8 bytes wide;
+ *   a qual op outside 0..5.  The HBM budget is checked before allocating
+ *   (GX_ERR_OOM).  GX_GB_LDS=0 in the environment, read at call time, turns
+ *   the workgroup-private LDS stage off; GX_GB_GIVEUP_ROWS (default 4096,
+ *   0 = never) is the row count after which a workgroup whose LDS table
+ *   mostly misses stops consulting it (DESIGN.md "Descriptor GROUP BY").
+ * Known difference: a float8 SUM whose inputs are all -0.0 returns +0.0.
+ * Not verified: tables of 2^32 - 1 rows or more (the 8-byte slot word is
+ *   covered through gx_test_groupby_desc's wide_rowid only). ---- */
+#define GX_GB_MAX_KEYS 4
+#define GX_GB_MAX_AGGS 8
+typedef enum { GX_AGG_COUNT_STAR = 0, GX_AGG_COUNT = 1, GX_AGG_SUM = 2,
+               GX_AGG_MIN = 3, GX_AGG_MAX = 4 } gx_agg_fn;
+typedef struct gx_agg { int32_t fn; int32_t col; int32_t is_f64; int32_t _pad; } gx_agg;
+typedef struct gx_gb_desc {
+    const gx_table *t;
+    int32_t nkeys;  int32_t key_cols[GX_GB_MAX_KEYS];   /* 0..4 integer columns */
+    int32_t naggs;  gx_agg  aggs[GX_GB_MAX_AGGS];        /* 1..8 */
+    int32_t nquals; gx_filter quals[GX_MAX_EXTRA_QUALS]; /* AND-ed, integer/date cols */
+    int64_t max_groups;   /* 0 = bound by nrows; else the planner's bound */
+} gx_gb_desc;
+typedef struct gx_gb_result {
+    int64_t ngroups; int32_t nkeys, naggs;
+    int64_t  *keys;      /* ngroups x nkeys, row-major, sign-extended */
+    uint8_t  *key_null;  /* same shape, 1 = NULL (key word 0) */
+    uint64_t *aggs;      /* ngroups x naggs: int64, or the double's bits */
+    uint8_t  *agg_null;  /* same shape */
+} gx_gb_result;
+/* ms_kernel: the scan kernel alone (HIP events).  rows_pass: rows left by
+ * the visimap and the quals; rows_lds of them were accumulated in a
+ * workgroup's LDS table, rows_global directly in the global one. */
+typedef struct gx_gbd_stats { double ms_kernel; int64_t rows_in, rows_pass,
+                              rows_lds, rows_global, groups; } gx_gbd_stats;
+gx_status gx_groupby_desc(gx_ctx *, const gx_gb_desc *, gx_gb_result *out,
+                          gx_gbd_stats *stats /* may be NULL */);
+void      gx_gb_result_free(gx_gb_result *);
+/* groups one workgroup's LDS table holds for a call with naggs aggregates */
+int32_t   gx_gb_lds_groups(int naggs);
+
 /* ---- test-only entry points (parity harness; not part of the drop-in) ---- */
+/* gx_groupby_desc through the same launch helper with the scan grid and the
+ * slot word chosen by the caller: grid = 0 is production (2048 workgroups),
+ * 1 or 3 make a workgroup see enough of a test-sized input to fill and
+ * merge its LDS table; wide_rowid = 1 forces the 8-byte slot word. */
+gx_status gx_test_groupby_desc(gx_ctx *, const gx_gb_desc *, int grid,
+                               int wide_rowid, gx_gb_result *, gx_gbd_stats *);
+/* The final ordering of gx_groupby_desc alone, no GPU needed: perm[0..n)
+ * receives the row order of n rows of nkeys (1..GX_GB_MAX_KEYS) columns,
+ * row-major keys / key_null, sorted by the (key_null, key) pairs column by
+ * column, ascending and stable.  Returns 0, or 1 for bad arguments. */
+int gx_selftest_gb_sort(const int64_t *keys, const uint8_t *key_null,
+                        int64_t n, int nkeys, int64_t *perm);
 typedef struct gx_ord_row { int64_t okey, ocust; int32_t odate, oprio; } gx_ord_row;
 /* Motion-1 partition kernels on one GPU: filter orders by cutoff, route by
  * cdbhash(o_custkey), emit packed rows grouped by destination segment. */
