@@ -306,6 +306,23 @@ def _load():
                                          ctypes.c_int,
                                          ctypes.POINTER(_GbResult),
                                          ctypes.POINTER(_GbdStats)]
+    lib.gx_groupby_desc_dist.argtypes = [ctypes.c_void_p, ctypes.POINTER(_GbDesc),
+                                         ctypes.POINTER(_GbResult),
+                                         ctypes.POINTER(_GbStats)]
+    lib.gx_gbd_wire_stride.restype = ctypes.c_int64
+    lib.gx_gbd_wire_stride.argtypes = [ctypes.POINTER(_GbDesc)]
+    lib.gx_test_gbd_partial.argtypes = [ctypes.c_void_p, ctypes.POINTER(_GbDesc),
+                                        ctypes.c_int, ctypes.c_void_p,
+                                        ctypes.c_void_p, ctypes.c_int64,
+                                        ctypes.POINTER(ctypes.c_int64)]
+    lib.gx_test_gbd_combine.argtypes = [ctypes.c_void_p, ctypes.POINTER(_GbDesc),
+                                        ctypes.c_void_p, ctypes.c_int64,
+                                        ctypes.c_int, ctypes.POINTER(_GbResult)]
+    lib.gx_selftest_gbd_route.restype = ctypes.c_int
+    lib.gx_selftest_gbd_route.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_int,
+                                          ctypes.c_int64, ctypes.c_int,
+                                          ctypes.c_void_p]
     lib.gx_gb_result_free.restype = None
     lib.gx_gb_result_free.argtypes = [ctypes.POINTER(_GbResult)]
     lib.gx_gb_lds_groups.restype = ctypes.c_int32
@@ -408,6 +425,71 @@ def gb_sort(keys, key_null):
     if rc != 0:
         raise ValueError(f"gx_selftest_gb_sort: bad arguments ({rc})")
     return perm
+
+
+def _gb_desc(table, keys, aggs, quals, max_groups):
+    """gx_gb_desc from the Python argument shapes; table None leaves t NULL"""
+    d = _GbDesc()
+    d.t = None if table is None else table._t
+    d.nkeys = len(keys)
+    for i, c in enumerate(keys[:GB_MAX_KEYS]):
+        d.key_cols[i] = c
+    d.naggs = len(aggs)
+    for i, spec in enumerate(aggs[:GB_MAX_AGGS]):
+        fn, col = spec[0], spec[1]
+        d.aggs[i] = _Agg(fn if isinstance(fn, int) else _AGG_FNS[fn],
+                         -1 if col is None else col,
+                         1 if len(spec) > 2 and spec[2] else 0, 0)
+    d.nquals = len(quals)
+    for i, (col, op, lit) in enumerate(quals[:MAX_EXTRA_QUALS]):
+        d.quals[i] = _Filter(col, _opcode(op), int(lit))
+    d.max_groups = max_groups
+    return d
+
+
+def gbd_wire_stride(keys, aggs):
+    """Bytes of one wire row of the two-stage descriptor GROUP BY for these
+    keys and aggregates (gx_gbd_wire_stride; host only, no GPU), or -1."""
+    d = _gb_desc(None, list(keys), list(aggs), [], 0)
+    return int(lib().gx_gbd_wire_stride(ctypes.byref(d)))
+
+
+def gbd_wire_dtype(keys, aggs):
+    """numpy mirror of that wire row: keys (nkeys int64, 0 where NULL),
+    key_null (nkeys uint8), _pad (zero bytes up to 8), acc (the state words,
+    opaque).  keys / key_null / _pad are absent for a plain aggregate."""
+    stride = gbd_wire_stride(keys, aggs)
+    if stride < 0:
+        raise ValueError("gx_gbd_wire_stride: bad descriptor")
+    nk = len(keys)
+    head = 8 * nk + (8 if nk else 0)
+    fields = []
+    if nk:
+        fields = [("keys", np.int64, (nk,)), ("key_null", np.uint8, (nk,)),
+                  ("_pad", np.uint8, (8 - nk,))]
+    fields.append(("acc", np.uint64, ((stride - head) // 8,)))
+    dt = np.dtype(fields)
+    assert dt.itemsize == stride
+    return dt
+
+
+def gbd_route(keys, key_null, widths, nsegs):
+    """Owner segment of every (n, nkeys) key row under the two-stage
+    descriptor GROUP BY's routing (host only, no GPU): widths[k] is the byte
+    width of key column k."""
+    keys = np.ascontiguousarray(keys, np.int64)
+    key_null = np.ascontiguousarray(key_null, np.uint8)
+    widths = np.ascontiguousarray(widths, np.int32)
+    assert keys.ndim == 2 and keys.shape == key_null.shape
+    n, nkeys = keys.shape
+    assert len(widths) == nkeys
+    out = np.zeros(n, np.int32)
+    rc = lib().gx_selftest_gbd_route(keys.ctypes.data, key_null.ctypes.data,
+                                     widths.ctypes.data, nkeys, n, nsegs,
+                                     out.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"gx_selftest_gbd_route: bad arguments ({rc})")
+    return out
 
 
 RLEBLK_UNFUSED, RLEBLK_NOBITMAP, RLEBLK_VARINT, RLEBLK_FIXED2 = 0, 1, 2, 3
@@ -574,22 +656,7 @@ class Context:
         return res
 
     def _gb_desc(self, table, keys, aggs, quals, max_groups):
-        d = _GbDesc()
-        d.t = table._t
-        d.nkeys = len(keys)
-        for i, c in enumerate(keys[:GB_MAX_KEYS]):
-            d.key_cols[i] = c
-        d.naggs = len(aggs)
-        for i, spec in enumerate(aggs[:GB_MAX_AGGS]):
-            fn, col = spec[0], spec[1]
-            d.aggs[i] = _Agg(fn if isinstance(fn, int) else _AGG_FNS[fn],
-                             -1 if col is None else col,
-                             1 if len(spec) > 2 and spec[2] else 0, 0)
-        d.nquals = len(quals)
-        for i, (col, op, lit) in enumerate(quals[:MAX_EXTRA_QUALS]):
-            d.quals[i] = _Filter(col, _opcode(op), int(lit))
-        d.max_groups = max_groups
-        return d
+        return _gb_desc(table, keys, aggs, quals, max_groups)
 
     def _gb_result(self, res, aggs):
         """gx_gb_result -> numpy; frees the native arrays."""
@@ -647,6 +714,52 @@ class Context:
         if stats:
             return out, {f: getattr(st, f) for f, _ in st._fields_}
         return out
+
+    def groupby_desc_dist(self, table, keys, aggs, quals=(), max_groups=0,
+                          stats=False):
+        """Two-stage descriptor GROUP BY across all segments of this context
+        (gx_groupby_desc_dist): the arguments and the result shape of
+        groupby_desc, holding the groups THIS segment owns; with stats=True
+        returns (result, gx_gb_stats as a dict)."""
+        keys, aggs, quals = list(keys), list(aggs), list(quals)
+        d = self._gb_desc(table, keys, aggs, quals, max_groups)
+        res, st = _GbResult(), _GbStats()
+        self._chk(self._lib.gx_groupby_desc_dist(
+            self._h, ctypes.byref(d), ctypes.byref(res), ctypes.byref(st)))
+        out = self._gb_result(res, aggs)
+        if stats:
+            return out, {f: getattr(st, f) for f, _ in st._fields_}
+        return out
+
+    def test_gbd_partial(self, table, keys, aggs, nsegs, quals=(),
+                         max_groups=0):
+        """Partial agg + partition kernels of groupby_desc_dist on one GPU:
+        returns (counts, rows), rows a gbd_wire_dtype array packed by
+        destination."""
+        keys, aggs, quals = list(keys), list(aggs), list(quals)
+        d = self._gb_desc(table, keys, aggs, quals, max_groups)
+        cap = max(table.nrows, 1)
+        counts = np.zeros(max(nsegs, 1), np.int64)
+        rows = np.zeros(cap, gbd_wire_dtype(keys, aggs))
+        total = ctypes.c_int64()
+        self._chk(self._lib.gx_test_gbd_partial(
+            self._h, ctypes.byref(d), nsegs, counts.ctypes.data,
+            rows.ctypes.data, cap, ctypes.byref(total)))
+        return counts[:nsegs], rows[:total.value]
+
+    def test_gbd_combine(self, rows, keys, aggs, max_groups=0,
+                         wide_rowid=False):
+        """Combine stage of groupby_desc_dist over wire rows (a
+        gbd_wire_dtype array): the groupby_desc result shape.  keys only
+        counts: the rows carry the key values."""
+        keys, aggs = list(keys), list(aggs)
+        rows = np.ascontiguousarray(rows, gbd_wire_dtype(keys, aggs))
+        d = self._gb_desc(None, keys, aggs, [], max_groups)
+        res = _GbResult()
+        self._chk(self._lib.gx_test_gbd_combine(
+            self._h, ctypes.byref(d), rows.ctypes.data if len(rows) else None,
+            len(rows), 1 if wide_rowid else 0, ctypes.byref(res)))
+        return self._gb_result(res, aggs)
 
     def test_gb_partial(self, table, key_col, val_col, nsegs):
         """Partial agg + partition kernels on one GPU: returns (counts,

@@ -2696,8 +2696,33 @@ GX_HD uint64_t gbd_f64_unimage(uint64_t img)
     return (img >> 63) ? img ^ (1ULL << 63) : ~img;
 }
 
+/* Where a representative row's key columns come from: the input's column
+ * streams (the scan), or wire rows (gx_gbd_wire_stride: the combine stage of
+ * the two-stage plan, whose received buffer is as immutable as the input). */
+struct gbd_key_cols {
+    __device__ __forceinline__ bool isnull(const gbd_args &a, int k, int64_t r) const
+    { return gbd_isnull(a.key[k], r); }
+    __device__ __forceinline__ int64_t load(const gbd_args &a, int k, int64_t r) const
+    { return gbd_load(a.key[k], r); }
+};
+
+struct gbd_key_wire {
+    const unsigned long long *rows;
+    int64_t stride;            /* 8-byte words per row */
+    __device__ __forceinline__ bool isnull(const gbd_args &a, int k, int64_t r) const
+    { return ((rows[r * stride + a.nkeys] >> (8 * k)) & 0xFFULL) != 0ULL; }
+    __device__ __forceinline__ int64_t load(const gbd_args &a, int k, int64_t r) const
+    { (void) a; return (int64_t) rows[r * stride + k]; }
+    /* the state words of row r */
+    __device__ __forceinline__ const unsigned long long *
+    acc(const gbd_args &a, int64_t r) const
+    { return rows + r * stride + a.nkeys + (a.nkeys ? 1 : 0); }
+};
+
 /* key values (0 where NULL), null bits and hash of one row */
-__device__ __forceinline__ uint64_t gbd_row_keys(const gbd_args &a, int64_t row,
+template <typename SRC>
+__device__ __forceinline__ uint64_t gbd_row_keys(const SRC &src, const gbd_args &a,
+                                                 int64_t row,
                                                  int64_t (&kv)[GX_GB_MAX_KEYS],
                                                  unsigned &kn)
 {
@@ -2709,8 +2734,8 @@ __device__ __forceinline__ uint64_t gbd_row_keys(const gbd_args &a, int64_t row,
         kv[k] = 0;
         if (k < a.nkeys)
         {
-            bool isnull = gbd_isnull(a.key[k], row);
-            kv[k] = isnull ? 0 : gbd_load(a.key[k], row);
+            bool isnull = src.isnull(a, k, row);
+            kv[k] = isnull ? 0 : src.load(a, k, row);
             kn |= (unsigned) isnull << k;
             h = gx_hmix64((h ^ (uint64_t) kv[k]) +
                           (isnull ? 0xD6E8FEB86659FD93ULL : 0ULL));
@@ -2720,7 +2745,8 @@ __device__ __forceinline__ uint64_t gbd_row_keys(const gbd_args &a, int64_t row,
 }
 
 /* NOT DISTINCT equality, column by column, with the keys of row r */
-__device__ __forceinline__ bool gbd_keys_eq(const gbd_args &a,
+template <typename SRC>
+__device__ __forceinline__ bool gbd_keys_eq(const SRC &src, const gbd_args &a,
                                             const int64_t (&kv)[GX_GB_MAX_KEYS],
                                             unsigned kn, int64_t r)
 {
@@ -2729,9 +2755,9 @@ __device__ __forceinline__ bool gbd_keys_eq(const gbd_args &a,
     for (int k = 0; k < GX_GB_MAX_KEYS; k++)
         if (k < a.nkeys)
         {
-            bool rnull = gbd_isnull(a.key[k], r);
+            bool rnull = src.isnull(a, k, r);
             eq = eq && rnull == (bool) ((kn >> k) & 1) &&
-                 (rnull || gbd_load(a.key[k], r) == kv[k]);
+                 (rnull || src.load(a, k, r) == kv[k]);
         }
     return eq;
 }
@@ -2739,9 +2765,9 @@ __device__ __forceinline__ bool gbd_keys_eq(const gbd_args &a,
 /* find or claim the global slot of the group of row i (keys kv/kn, hash h);
  * ~0 and the error bit when the bounded walk runs out (more groups than the
  * table was sized for) */
-template <typename ST>
-__device__ __forceinline__ uint64_t gbd_ginsert(const gbd_args &a, ST *trow,
-                                                uint64_t tmask, uint64_t h,
+template <typename ST, typename SRC>
+__device__ __forceinline__ uint64_t gbd_ginsert(const SRC &src, const gbd_args &a,
+                                                ST *trow, uint64_t tmask, uint64_t h,
                                                 const int64_t (&kv)[GX_GB_MAX_KEYS],
                                                 unsigned kn, int64_t i, int *err)
 {
@@ -2756,11 +2782,31 @@ __device__ __forceinline__ uint64_t gbd_ginsert(const gbd_args &a, ST *trow,
             cur = atomicCAS(&trow[slot], (ST) 0, (ST) (i + 1));
             if (cur == (ST) 0) return slot;
         }
-        if (gbd_keys_eq(a, kv, kn, (int64_t) cur - 1)) return slot;
+        if (gbd_keys_eq(src, a, kv, kn, (int64_t) cur - 1)) return slot;
         slot = (slot + 1) & tmask;
     }
     atomicOr(err, 1);
     return ~0ULL;
+}
+
+/* merge the state words l of one group into the global words g of the same
+ * group, word by word through wop[]; a word still at its all-zero identity
+ * costs nothing.  The combine function of every aggregate (nodeAgg.c:2305). */
+__device__ __forceinline__ void d_gbd_merge_words(const gbd_args &a,
+                                                  const unsigned long long *l,
+                                                  unsigned long long *g)
+{
+#pragma unroll
+    for (int w = 0; w < GBD_MAX_WORDS; w++)
+    {
+        if (w >= a.awords) continue;
+        const unsigned long long v = l[w];
+        if (v == 0ULL) continue;              /* still the identity */
+        if (a.wop[w] == GBD_W_ADD) atomicAdd(&g[w], v);
+        else if (a.wop[w] == GBD_W_FADD)
+            atomicAdd((double *) &g[w], __longlong_as_double((long long) v));
+        else atomicMax(&g[w], v);
+    }
 }
 
 /* row i's transitions on the accumulator words w of its group; w is an LDS
@@ -2834,7 +2880,7 @@ k_groupby_desc(const gbd_args a, ST *trow, unsigned long long *tacc,
          * outcome: one memory round trip per row instead of two */
         int64_t kv[GX_GB_MAX_KEYS];
         unsigned kn;
-        const uint64_t h = gbd_row_keys(a, i, kv, kn);
+        const uint64_t h = gbd_row_keys(gbd_key_cols{}, a, i, kv, kn);
         bool pass = true;
 #pragma unroll
         for (int q = 0; q < GX_MAX_EXTRA_QUALS; q++)
@@ -2861,7 +2907,7 @@ k_groupby_desc(const gbd_args a, ST *trow, unsigned long long *tacc,
                         cur = atomicCAS(&lrow[ls], (ST) 0, (ST) (i + 1));
                         if (cur == (ST) 0) { done = true; break; }
                     }
-                    if (gbd_keys_eq(a, kv, kn, (int64_t) cur - 1))
+                    if (gbd_keys_eq(gbd_key_cols{}, a, kv, kn, (int64_t) cur - 1))
                     { done = true; break; }
                     ls = (ls + 1) & (L - 1);
                 }
@@ -2882,7 +2928,8 @@ k_groupby_desc(const gbd_args a, ST *trow, unsigned long long *tacc,
         }
         if (!done)
         {
-            uint64_t slot = gbd_ginsert<ST>(a, trow, tmask, h, kv, kn, i, err);
+            uint64_t slot = gbd_ginsert<ST>(gbd_key_cols{}, a, trow, tmask, h, kv, kn,
+                                            i, err);
             if (slot != ~0ULL) gbd_accum(a, i, tacc + slot * a.awords);
         }
     }
@@ -2896,22 +2943,12 @@ k_groupby_desc(const gbd_args a, ST *trow, unsigned long long *tacc,
             const int64_t r = (int64_t) r1 - 1;
             int64_t kv[GX_GB_MAX_KEYS];
             unsigned kn;
-            const uint64_t h = gbd_row_keys(a, r, kv, kn);
-            uint64_t slot = gbd_ginsert<ST>(a, trow, tmask, h, kv, kn, r, err);
+            const uint64_t h = gbd_row_keys(gbd_key_cols{}, a, r, kv, kn);
+            uint64_t slot = gbd_ginsert<ST>(gbd_key_cols{}, a, trow, tmask, h, kv, kn,
+                                            r, err);
             if (slot == ~0ULL) continue;
-            unsigned long long *g = tacc + slot * a.awords;
-            const unsigned long long *l = lacc + (size_t) s * a.awords;
-#pragma unroll
-            for (int w = 0; w < GBD_MAX_WORDS; w++)
-            {
-                if (w >= a.awords) continue;
-                const unsigned long long v = l[w];
-                if (v == 0ULL) continue;              /* still the identity */
-                if (a.wop[w] == GBD_W_ADD) atomicAdd(&g[w], v);
-                else if (a.wop[w] == GBD_W_FADD)
-                    atomicAdd((double *) &g[w], __longlong_as_double((long long) v));
-                else atomicMax(&g[w], v);
-            }
+            d_gbd_merge_words(a, lacc + (size_t) s * a.awords,
+                              tacc + slot * a.awords);
         }
     }
     gx_wave_count_add(stats + 0, n_pass);
@@ -2922,10 +2959,12 @@ k_groupby_desc(const gbd_args a, ST *trow, unsigned long long *tacc,
  * null flags, accumulator words copied.  Each workgroup counts the keeps of
  * its 256-slot tile and claims its output region with ONE cursor atomic
  * (k_extract's way).  Groups past cap are counted, not written; the host
- * turns cursor > cap into an error. */
-template <typename ST>
+ * turns cursor > cap into an error.  SRC says where a representative's keys
+ * are read: gbd_key_cols after the scan, gbd_key_wire after the combine. */
+template <typename ST, typename SRC>
 __global__ void __launch_bounds__(TPB)
-k_gbd_extract(const gbd_args a, const ST *trow, const unsigned long long *tacc,
+k_gbd_extract(const gbd_args a, const SRC src, const ST *trow,
+              const unsigned long long *tacc,
               uint64_t tslots, int64_t *okeys, uint8_t *oknull,
               unsigned long long *oacc, unsigned long long *cursor, int64_t cap)
 {
@@ -2962,14 +3001,175 @@ k_gbd_extract(const gbd_args a, const ST *trow, const unsigned long long *tacc,
             for (int k = 0; k < GX_GB_MAX_KEYS; k++)
                 if (k < a.nkeys)
                 {
-                    bool isnull = gbd_isnull(a.key[k], r);
-                    okeys[w * a.nkeys + k] = isnull ? 0 : gbd_load(a.key[k], r);
+                    bool isnull = src.isnull(a, k, r);
+                    okeys[w * a.nkeys + k] = isnull ? 0 : src.load(a, k, r);
                     oknull[w * a.nkeys + k] = (uint8_t) isnull;
                 }
             for (int x = 0; x < a.awords; x++)
                 oacc[w * a.awords + x] = tacc[i * a.awords + x];
         }
         __syncthreads();
+    }
+}
+
+/* ----- two-stage descriptor GROUP BY (gx_groupby_desc_dist) -----
+ * partial agg (k_groupby_desc + k_gbd_extract) -> hash Motion of the partial
+ * states by group key -> combine agg on the owning segment.  The partition
+ * kernels read the COMPACTED partial groups (okeys / oknull / oacc), not the
+ * table slots, and the group count from device memory (the extract cursor),
+ * so no host sync stands between the scan and the count all-gather. */
+
+/* owner segment of a group: the reference's cdbhash chain over the key
+ * columns, hashint8 for a width-8 column and hashint4 of the value for the
+ * narrower ones (wide bit k set = width 8), then the jump hash.  A plain
+ * aggregate (no key) is gathered on segment 0.  Host and device. */
+GX_HD int32_t gbd_owner(const int64_t (&kv)[GX_GB_MAX_KEYS], unsigned kn,
+                        unsigned wide, int nkeys, int nsegs)
+{
+    uint8_t nb[GX_GB_MAX_KEYS];
+    int32_t ty[GX_GB_MAX_KEYS];
+#pragma unroll
+    for (int k = 0; k < GX_GB_MAX_KEYS; k++)
+    {
+        nb[k] = (uint8_t) ((kn >> k) & 1);
+        ty[k] = ((wide >> k) & 1) ? 0 : 1;
+    }
+    uint32_t h;
+    /* a constant column count per call: the chain unrolls over registers */
+    switch (nkeys)
+    {
+        case 1: h = gx_cdbhash_multi(kv, nb, ty, 1); break;
+        case 2: h = gx_cdbhash_multi(kv, nb, ty, 2); break;
+        case 3: h = gx_cdbhash_multi(kv, nb, ty, 3); break;
+        case 4: h = gx_cdbhash_multi(kv, nb, ty, 4); break;
+        default: return 0;
+    }
+    return gx_jump_consistent_hash((uint64_t) h, nsegs);
+}
+
+/* groups the partial stage hands to the Motion.  misc is the partial stage's
+ * word block: [2] the extract cursor, [3] the error word.  A failed stage
+ * (error bit, or more groups than cap) ships nothing, so its peers' receives
+ * still complete; a plain aggregate ships its one state row also when no row
+ * reached it (row 0 of oacc is zeroed before the extract). */
+__device__ __forceinline__ int64_t d_gbd_part_groups(const unsigned long long *misc,
+                                                     int64_t cap, int nkeys)
+{
+    const unsigned long long ng = misc[2];
+    if ((*(const int *) (misc + 3) & 1) || ng > (unsigned long long) cap) return 0;
+    return nkeys == 0 ? 1 : (int64_t) ng;
+}
+
+/* partial groups -> destination of each (dest[], read back by the emit pass:
+ * the jump loop has an f64 divide per iteration) and the per-destination
+ * histogram.  One LDS atomic per group on cnt[dest], then one global atomic
+ * per workgroup per non-empty destination.  Dynamic LDS: nsegs u32. */
+__global__ void __launch_bounds__(TPB)
+k_gbd_part_hist(const int64_t *okeys, const uint8_t *oknull,
+                const unsigned long long *misc, int64_t cap, int nkeys,
+                unsigned wide, int nsegs, uint16_t *dest,
+                unsigned long long *hist)
+{
+    extern __shared__ unsigned int gbd_hist_lds[];
+    unsigned int *cnt = gbd_hist_lds;
+    for (int j = threadIdx.x; j < nsegs; j += TPB) cnt[j] = 0u;
+    __syncthreads();
+    const int64_t ng = d_gbd_part_groups(misc, cap, nkeys);
+    const int64_t stride = gridDim.x * (int64_t) TPB;
+    for (int64_t g = blockIdx.x * (int64_t) TPB + threadIdx.x; g < ng; g += stride)
+    {
+        int64_t kv[GX_GB_MAX_KEYS];
+        unsigned kn = 0;
+#pragma unroll
+        for (int k = 0; k < GX_GB_MAX_KEYS; k++)
+        {
+            kv[k] = 0;
+            if (k < nkeys)
+            {
+                kv[k] = okeys[g * nkeys + k];
+                kn |= (unsigned) (oknull[g * nkeys + k] != 0) << k;
+            }
+        }
+        const int32_t d = gbd_owner(kv, kn, wide, nkeys, nsegs);
+        dest[g] = (uint16_t) d;
+        atomicAdd(&cnt[d], 1u);
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < nsegs; j += TPB)
+        if (cnt[j]) atomicAdd(&hist[j], (unsigned long long) cnt[j]);
+}
+
+/* partial groups -> wire rows (gx_gbd_wire_stride) packed by destination;
+ * cursors are pre-set to the region starts.  A workgroup counts its groups
+ * per destination in LDS, claims one contiguous piece of every non-empty
+ * destination's region with one global atomic, then each group claims its
+ * row inside the piece with one returning LDS atomic.  Rows are written with
+ * 8-byte stores, the null bytes as one zero-padded word.
+ * Dynamic LDS: nsegs u64 (piece starts) + nsegs u32 (counts). */
+__global__ void __launch_bounds__(TPB)
+k_gbd_part_emit(const int64_t *okeys, const uint8_t *oknull,
+                const unsigned long long *oacc, const unsigned long long *misc,
+                int64_t cap, int nkeys, int awords, int nsegs,
+                const uint16_t *dest, unsigned long long *cursors,
+                unsigned long long *out)
+{
+    extern __shared__ unsigned long long gbd_emit_lds[];
+    unsigned long long *piece = gbd_emit_lds;
+    unsigned int *cnt = (unsigned int *) (gbd_emit_lds + nsegs);
+    for (int j = threadIdx.x; j < nsegs; j += TPB) cnt[j] = 0u;
+    __syncthreads();
+    const int64_t ng = d_gbd_part_groups(misc, cap, nkeys);
+    const int64_t stride = gridDim.x * (int64_t) TPB;
+    const int64_t g0 = blockIdx.x * (int64_t) TPB + threadIdx.x;
+    for (int64_t g = g0; g < ng; g += stride) atomicAdd(&cnt[dest[g]], 1u);
+    __syncthreads();
+    for (int j = threadIdx.x; j < nsegs; j += TPB)
+    {
+        const unsigned int c = cnt[j];
+        piece[j] = c ? atomicAdd(&cursors[j], (unsigned long long) c) : 0ULL;
+        cnt[j] = 0u;
+    }
+    __syncthreads();
+    const int64_t rw = nkeys + (nkeys ? 1 : 0) + awords;
+    for (int64_t g = g0; g < ng; g += stride)
+    {
+        const int d = dest[g];
+        const unsigned long long w = piece[d] + atomicAdd(&cnt[d], 1u);
+        unsigned long long *row = out + w * rw;
+        unsigned long long nullw = 0ULL;
+#pragma unroll
+        for (int k = 0; k < GX_GB_MAX_KEYS; k++)
+            if (k < nkeys)
+            {
+                row[k] = (unsigned long long) okeys[g * nkeys + k];
+                nullw |= (unsigned long long) (oknull[g * nkeys + k] != 0) << (8 * k);
+            }
+        if (nkeys) row[nkeys] = nullw;
+        unsigned long long *acc = row + nkeys + (nkeys ? 1 : 0);
+        for (int x = 0; x < awords; x++) acc[x] = oacc[g * awords + x];
+    }
+}
+
+/* combine agg over n received wire rows: the representative-row table of
+ * k_groupby_desc over the received buffer (a slot holds row + 1, keys are
+ * compared by reading the slot's wire row, NOT DISTINCT per column; rows
+ * hash as gbd_row_keys hashes input rows), the state merged word by word
+ * with the aggregates' combine ops.  No LDS stage: at low cardinality the
+ * input is nsegs x groups rows, at high cardinality nearly distinct. */
+template <typename ST>
+__global__ void __launch_bounds__(TPB)
+k_gbd_combine(const gbd_args a, const gbd_key_wire src, int64_t n, ST *trow,
+              unsigned long long *tacc, uint64_t tmask, int *err)
+{
+    const int64_t stride = gridDim.x * (int64_t) TPB;
+    for (int64_t i = blockIdx.x * (int64_t) TPB + threadIdx.x; i < n; i += stride)
+    {
+        int64_t kv[GX_GB_MAX_KEYS];
+        unsigned kn;
+        const uint64_t h = gbd_row_keys(src, a, i, kv, kn);
+        const uint64_t slot = gbd_ginsert<ST>(src, a, trow, tmask, h, kv, kn, i, err);
+        if (slot != ~0ULL)
+            d_gbd_merge_words(a, src.acc(a, i), tacc + slot * a.awords);
     }
 }
 
@@ -6718,34 +6918,32 @@ static gx_status gbd_bind_col(gx_ctx *ctx, const gx_table *t, int col,
 
 static bool gbd_int_width(int w) { return w == 1 || w == 2 || w == 4 || w == 8; }
 
-/* Validate, flatten, size, scan, extract, sort.  grid and wide come from the
- * caller (production: GRID, nrows >= 2^32 - 1), lds from GX_GB_LDS, so the
- * public call and the test entry run the same launches. */
-static gx_status gbd_run(gx_ctx *ctx, const gx_gb_desc *d, int grid, bool wide,
-                         bool lds, gx_gb_result *out, gx_gbd_stats *stats)
+/* state words of one aggregate: COUNTs one, SUM / MIN / MAX a second one
+ * counting their non-NULL inputs */
+static int gbd_fn_words(int fn) { return fn <= GX_AGG_COUNT ? 1 : 2; }
+
+/* PLAN: validate the descriptor and fill everything of gbd_args that needs
+ * no device memory.  t == nullptr (the combine stage over wire rows) checks
+ * and reads nkeys, the aggregates' fn / is_f64 and max_groups only. */
+static gx_status gbd_plan(gx_ctx *ctx, const gx_gb_desc *d, const gx_table *t,
+                          gbd_args &a)
 {
-    if (!ctx || !d || !out) return GX_ERR_INVALID;
-    memset(out, 0, sizeof *out);
-    if (stats) memset(stats, 0, sizeof *stats);
-    const gx_table *t = d->t;
-    if (!t) { set_err(ctx, "groupby_desc: no table%s", ""); return GX_ERR_INVALID; }
-    const int ncols = (int) t->cols.size();
+    const int ncols = t ? (int) t->cols.size() : 0;
     if (d->nkeys < 0 || d->nkeys > GX_GB_MAX_KEYS)
         return gbd_invalid(ctx, "nkeys %ld outside 0..%ld", d->nkeys, GX_GB_MAX_KEYS);
     if (d->naggs < 1 || d->naggs > GX_GB_MAX_AGGS)
         return gbd_invalid(ctx, "naggs %ld outside 1..%ld", d->naggs, GX_GB_MAX_AGGS);
-    if (d->nquals < 0 || d->nquals > GX_MAX_EXTRA_QUALS)
+    if (t && (d->nquals < 0 || d->nquals > GX_MAX_EXTRA_QUALS))
         return gbd_invalid(ctx, "nquals %ld outside 0..%ld", d->nquals, GX_MAX_EXTRA_QUALS);
     if (d->max_groups < 0)
         return gbd_invalid(ctx, "max_groups %ld is negative", (long) d->max_groups);
-    if (grid < 1) return gbd_invalid(ctx, "grid %ld", grid);
 
-    gbd_args a{};
-    a.nkeys = d->nkeys; a.naggs = d->naggs; a.nquals = d->nquals;
-    a.nrows = t->nrows;
-    a.vmap = t->dvmap;
+    a = gbd_args{};
+    a.nkeys = d->nkeys; a.naggs = d->naggs; a.nquals = t ? d->nquals : 0;
+    a.nrows = t ? t->nrows : 0;
+    a.vmap = t ? t->dvmap : nullptr;
     /* validate everything before the first flatten launches */
-    for (int k = 0; k < d->nkeys; k++)
+    for (int k = 0; t && k < d->nkeys; k++)
     {
         int c = d->key_cols[k];
         if (c < 0 || c >= ncols)
@@ -6767,14 +6965,18 @@ static gx_status gbd_run(gx_ctx *ctx, const gx_gb_desc *d, int grid, bool wide,
             a.wop[words++] = GBD_W_ADD;
             continue;
         }
-        if (g.col < 0 || g.col >= ncols)
-            return gbd_invalid(ctx, "aggregate %ld: column %ld out of range", j, g.col);
-        int w = t->cols[g.col].m.width;
-        if (g.is_f64 ? w != 8 : !gbd_int_width(w))
-            return gbd_invalid(ctx, g.is_f64
-                                   ? "aggregate %ld: is_f64 on a column of width %ld"
-                                   : "aggregate %ld: column width %ld is not 1, 2, 4 or 8",
-                               j, w);
+        int w = 0;
+        if (t)
+        {
+            if (g.col < 0 || g.col >= ncols)
+                return gbd_invalid(ctx, "aggregate %ld: column %ld out of range", j, g.col);
+            w = t->cols[g.col].m.width;
+            if (g.is_f64 ? w != 8 : !gbd_int_width(w))
+                return gbd_invalid(ctx, g.is_f64
+                                       ? "aggregate %ld: is_f64 on a column of width %ld"
+                                       : "aggregate %ld: column width %ld is not 1, 2, 4 or 8",
+                                   j, w);
+        }
         if (g.fn == GX_AGG_COUNT)
         {
             a.aop[j] = GBD_COUNT;
@@ -6798,7 +7000,7 @@ static gx_status gbd_run(gx_ctx *ctx, const gx_gb_desc *d, int grid, bool wide,
         a.wop[words++] = GBD_W_ADD;                  /* non-NULL input count */
     }
     a.awords = words;
-    for (int q = 0; q < d->nquals; q++)
+    for (int q = 0; t && q < d->nquals; q++)
     {
         const gx_filter &f = d->quals[q];
         if (f.col < 0 || f.col >= ncols)
@@ -6811,22 +7013,33 @@ static gx_status gbd_run(gx_ctx *ctx, const gx_gb_desc *d, int grid, bool wide,
         if (!gx_fold_filter(w, &a.qop[q], &a.qlit[q]))
             return gbd_invalid(ctx, "qual %ld: op %ld outside 0..5", q, f.op);
     }
+    a.lds_slots = gbd_lds_slots(d->naggs);
+    /* measurement knob: 0 = never give up */
+    int gr = env_int("GX_GB_GIVEUP_ROWS", (int) GBD_GIVEUP_ROWS);
+    a.giveup_rows = gr > 0 ? (uint32_t) gr : UINT32_MAX;
+    return GX_OK;
+}
 
-    /* sizing: the table holds up to `bound` groups at a fill of 1/2 at most */
-    const int64_t n = t->nrows;
-    const int64_t bound = std::max<int64_t>(
-        1, d->max_groups > 0 ? std::min<int64_t>(d->max_groups, n) : n);
-    const uint64_t tslots = (uint64_t) pow2_at_least(bound * 2);
-    const size_t sw = wide ? 8 : 4;
-    if (!wide && n >= (int64_t) UINT32_MAX)
-        return gbd_invalid(ctx, "%ld rows need the 8-byte slot word", (long) n);
-    gx_status st = hbm_budget_check(
-        ctx, tslots * (sw + (uint64_t) words * 8) +
-                 (uint64_t) bound * ((uint64_t) words * 8 + (uint64_t) d->nkeys * 9) + 64,
-        "groupby_desc table");
-    if (st != GX_OK) return st;
+extern "C" int64_t gx_gbd_wire_stride(const gx_gb_desc *d)
+{
+    if (!d || d->nkeys < 0 || d->nkeys > GX_GB_MAX_KEYS || d->naggs < 1 ||
+        d->naggs > GX_GB_MAX_AGGS)
+        return -1;
+    int words = 0;
+    for (int j = 0; j < d->naggs; j++)
+    {
+        if (d->aggs[j].fn < GX_AGG_COUNT_STAR || d->aggs[j].fn > GX_AGG_MAX) return -1;
+        words += gbd_fn_words(d->aggs[j].fn);
+    }
+    return 8 * (int64_t) (d->nkeys + (d->nkeys ? 1 : 0) + words);
+}
 
-    gbd_inputs in;
+/* BIND: flatten every column the plan reads */
+static gx_status gbd_bind(gx_ctx *ctx, const gx_gb_desc *d, gbd_inputs &in,
+                          gbd_args &a)
+{
+    const gx_table *t = d->t;
+    gx_status st;
     for (int k = 0; k < d->nkeys; k++)
         if ((st = gbd_bind_col(ctx, t, d->key_cols[k], in, &a.key[k])) != GX_OK) return st;
     for (int j = 0; j < d->naggs; j++)
@@ -6834,75 +7047,166 @@ static gx_status gbd_run(gx_ctx *ctx, const gx_gb_desc *d, int grid, bool wide,
             (st = gbd_bind_col(ctx, t, d->aggs[j].col, in, &a.agg[j])) != GX_OK) return st;
     for (int q = 0; q < d->nquals; q++)
         if ((st = gbd_bind_col(ctx, t, d->quals[q].col, in, &a.qual[q])) != GX_OK) return st;
+    return GX_OK;
+}
 
+/* one aggregation table on the device and its compacted groups: the scan's
+ * over input rows, or the combine stage's over wire rows */
+struct gbd_table {
+    devbuf trow, tacc, misc;       /* misc: [0..1] stats, [2] cursor, [3] err */
+    devbuf okeys, oknull, oacc;    /* compacted groups, SoA, up to bound */
+    uint64_t tslots = 0;
+    int64_t bound = 0;
+    size_t sw = 4;                 /* bytes of the slot word */
+    unsigned long long *stat() const { return misc.as<unsigned long long>(); }
+    unsigned long long *cursor() const { return stat() + 2; }
+    int *err() const { return (int *) (stat() + 3); }
+};
+
+/* HBM budget of a table for up to `bound` groups at a fill of 1/2 at most,
+ * plus `extra` bytes the caller allocates beside it */
+static gx_status gbd_table_budget(gx_ctx *ctx, const gbd_args &a, int64_t bound,
+                                  bool wide, uint64_t extra, const char *what)
+{
+    const uint64_t tslots = (uint64_t) pow2_at_least(bound * 2);
+    return hbm_budget_check(
+        ctx, tslots * ((wide ? 8 : 4) + (uint64_t) a.awords * 8) +
+                 (uint64_t) bound * ((uint64_t) a.awords * 8 + (uint64_t) a.nkeys * 9) +
+                 64 + extra,
+        what);
+}
+
+/* allocate and clear (enqueue only) */
+static gx_status gbd_table_alloc(gx_ctx *ctx, gbd_table &T, const gbd_args &a,
+                                 int64_t bound, bool wide)
+{
     hipStream_t s = ctx->stream;
-    a.lds_slots = gbd_lds_slots(d->naggs);
-    /* measurement knob: 0 = never give up */
-    int gr = env_int("GX_GB_GIVEUP_ROWS", (int) GBD_GIVEUP_ROWS);
-    a.giveup_rows = gr > 0 ? (uint32_t) gr : UINT32_MAX;
-    const size_t lds_bytes = lds ? (size_t) a.lds_slots * ((size_t) words * 8 + sw) : 0;
-    devbuf trow, tacc, misc, okeys, oknull, oacc;
-    HIP_CHK(ctx, trow.alloc(tslots * sw));
-    HIP_CHK(ctx, tacc.alloc(tslots * (size_t) words * 8));
-    HIP_CHK(ctx, misc.alloc(32));     /* [0..1] stats, [2] cursor, [3] err */
-    HIP_CHK(ctx, okeys.alloc((size_t) bound * std::max(d->nkeys, 1) * 8));
-    HIP_CHK(ctx, oknull.alloc((size_t) bound * std::max(d->nkeys, 1)));
-    HIP_CHK(ctx, oacc.alloc((size_t) bound * words * 8));
-    HIP_CHK(ctx, hipMemsetAsync(trow.p, 0, tslots * sw, s));
-    HIP_CHK(ctx, hipMemsetAsync(tacc.p, 0, tslots * (size_t) words * 8, s));
-    HIP_CHK(ctx, hipMemsetAsync(misc.p, 0, 32, s));
-    unsigned long long *dstat = misc.as<unsigned long long>();
-    int *derr = (int *) (dstat + 3);
-    evholder e0, e1;
-    HIP_CHK(ctx, e0.create()); HIP_CHK(ctx, e1.create());
-    HIP_CHK(ctx, hipEventRecord(e0, s));
-    by_width((int) sw, trow.p, [&](auto *rows) {
+    const int words = a.awords, nk = a.nkeys;
+    T.bound = bound;
+    T.tslots = (uint64_t) pow2_at_least(bound * 2);
+    T.sw = wide ? 8 : 4;
+    HIP_CHK(ctx, T.trow.alloc(T.tslots * T.sw));
+    HIP_CHK(ctx, T.tacc.alloc(T.tslots * (size_t) words * 8));
+    HIP_CHK(ctx, T.misc.alloc(32));
+    HIP_CHK(ctx, T.okeys.alloc((size_t) bound * std::max(nk, 1) * 8));
+    HIP_CHK(ctx, T.oknull.alloc((size_t) bound * std::max(nk, 1)));
+    HIP_CHK(ctx, T.oacc.alloc((size_t) bound * words * 8));
+    HIP_CHK(ctx, hipMemsetAsync(T.trow.p, 0, T.tslots * T.sw, s));
+    HIP_CHK(ctx, hipMemsetAsync(T.tacc.p, 0, T.tslots * (size_t) words * 8, s));
+    HIP_CHK(ctx, hipMemsetAsync(T.misc.p, 0, 32, s));
+    /* a plain aggregate's one group is all-identity until the extract writes
+     * it: the state row the two-stage plan ships for an empty shard */
+    if (nk == 0)
+        HIP_CHK(ctx, hipMemsetAsync(T.oacc.p, 0, (size_t) words * 8, s));
+    return GX_OK;
+}
+
+/* EXTRACT: the table's groups into okeys / oknull / oacc, their count into
+ * the cursor (enqueue only); src reads a representative row's keys */
+template <typename SRC>
+static void gbd_extract(gx_ctx *ctx, const gbd_args &a, const SRC &src, gbd_table &T)
+{
+    const int xgrid = (int) std::min<uint64_t>(GRID, (T.tslots + TPB - 1) / TPB);
+    by_width((int) T.sw, (const void *) T.trow.p, [&](auto *rows) {
+        hipLaunchKernelGGL((k_gbd_extract<std::decay_t<decltype(*rows)>, SRC>),
+                           dim3(xgrid), dim3(TPB), 0, ctx->stream, a, src, rows,
+                           T.tacc.as<unsigned long long>(), T.tslots,
+                           T.okeys.as<int64_t>(), T.oknull.as<uint8_t>(),
+                           T.oacc.as<unsigned long long>(), T.cursor(), T.bound);
+    });
+}
+
+/* SCAN stage of a planned call: budget, bind, table, k_groupby_desc (between
+ * e0 and e1 when given), extract.  Enqueue only: the group count and the
+ * error word stay on the device (T.misc) until the caller syncs.  extra:
+ * bytes the caller allocates beside the table. */
+static gx_status gbd_scan_stage(gx_ctx *ctx, const gx_gb_desc *d, gbd_args &a,
+                                gbd_inputs &in, gbd_table &T, int grid, bool wide,
+                                bool lds, uint64_t extra, hipEvent_t e0,
+                                hipEvent_t e1)
+{
+    if (grid < 1) return gbd_invalid(ctx, "grid %ld", grid);
+    /* sizing: the table holds up to `bound` groups */
+    const int64_t n = d->t->nrows;
+    const int64_t bound = std::max<int64_t>(
+        1, d->max_groups > 0 ? std::min<int64_t>(d->max_groups, n) : n);
+    if (!wide && n >= (int64_t) UINT32_MAX)
+        return gbd_invalid(ctx, "%ld rows need the 8-byte slot word", (long) n);
+    gx_status st = gbd_table_budget(ctx, a, bound, wide, extra, "groupby_desc table");
+    if (st != GX_OK) return st;
+    if ((st = gbd_bind(ctx, d, in, a)) != GX_OK) return st;
+    if ((st = gbd_table_alloc(ctx, T, a, bound, wide)) != GX_OK) return st;
+    hipStream_t s = ctx->stream;
+    const size_t lds_bytes = lds ? (size_t) a.lds_slots * ((size_t) a.awords * 8 + T.sw) : 0;
+    if (e0) HIP_CHK(ctx, hipEventRecord(e0, s));
+    by_width((int) T.sw, T.trow.p, [&](auto *rows) {
         by_flag(lds, [&](auto use_lds) {
             hipLaunchKernelGGL((k_groupby_desc<std::decay_t<decltype(*rows)>,
                                                decltype(use_lds)::value>),
                                dim3(grid), dim3(TPB), lds_bytes, s, a, rows,
-                               tacc.as<unsigned long long>(), tslots - 1,
-                               dstat, derr);
+                               T.tacc.as<unsigned long long>(), T.tslots - 1,
+                               T.stat(), T.err());
         });
     });
-    HIP_CHK(ctx, hipEventRecord(e1, s));
-    const int xgrid = (int) std::min<uint64_t>(GRID, (tslots + TPB - 1) / TPB);
-    by_width((int) sw, (const void *) trow.p, [&](auto *rows) {
-        hipLaunchKernelGGL(k_gbd_extract<std::decay_t<decltype(*rows)>>,
-                           dim3(xgrid), dim3(TPB), 0, s, a, rows,
-                           tacc.as<unsigned long long>(), tslots,
-                           okeys.as<int64_t>(), oknull.as<uint8_t>(),
-                           oacc.as<unsigned long long>(), dstat + 2, bound);
-    });
-    unsigned long long hm[4] = {0, 0, 0, 0};
-    HIP_CHK(ctx, hipMemcpyAsync(hm, misc.p, 32, hipMemcpyDeviceToHost, s));
+    if (e1) HIP_CHK(ctx, hipEventRecord(e1, s));
+    gbd_extract(ctx, a, gbd_key_cols{}, T);
+    return GX_OK;
+}
+
+/* the groups a finished table holds, on the host */
+struct gbd_host_groups {
+    std::vector<int64_t> k;
+    std::vector<uint8_t> n;
+    std::vector<unsigned long long> a;
+    int64_t ng = 0;
+};
+
+/* the table's stat words (one sync), the overflow verdict, then its ng
+ * compacted groups */
+static gx_status gbd_fetch(gx_ctx *ctx, const gbd_args &a, const gbd_table &T,
+                           int64_t max_groups, unsigned long long (&hm)[4],
+                           gbd_host_groups &H)
+{
+    hipStream_t s = ctx->stream;
+    HIP_CHK(ctx, hipMemcpyAsync(hm, T.misc.p, 32, hipMemcpyDeviceToHost, s));
     HIP_CHK(ctx, hipStreamSynchronize(s));
     HIP_CHK(ctx, hipGetLastError());
     const int64_t ng = (int64_t) hm[2];
-    if ((hm[3] & 1) || ng > bound || (d->max_groups > 0 && ng > d->max_groups))
+    if ((hm[3] & 1) || ng > T.bound || (max_groups > 0 && ng > max_groups))
     {
         set_err(ctx, "groupby_desc: more groups than max_groups%s", "");
         return GX_ERR_INVALID;
     }
-    const int nk = d->nkeys, na = d->naggs;
-    std::vector<int64_t> hk((size_t) ng * nk);
-    std::vector<uint8_t> hn((size_t) ng * nk);
-    std::vector<unsigned long long> ha((size_t) ng * words);
+    const int nk = a.nkeys, words = a.awords;
+    H.ng = ng;
+    H.k.resize((size_t) ng * nk);
+    H.n.resize((size_t) ng * nk);
+    H.a.resize((size_t) ng * words);
     if (ng)
     {
         if (nk)
         {
-            HIP_CHK(ctx, hipMemcpyAsync(hk.data(), okeys.p, hk.size() * 8, hipMemcpyDeviceToHost, s));
-            HIP_CHK(ctx, hipMemcpyAsync(hn.data(), oknull.p, hn.size(), hipMemcpyDeviceToHost, s));
+            HIP_CHK(ctx, hipMemcpyAsync(H.k.data(), T.okeys.p, H.k.size() * 8, hipMemcpyDeviceToHost, s));
+            HIP_CHK(ctx, hipMemcpyAsync(H.n.data(), T.oknull.p, H.n.size(), hipMemcpyDeviceToHost, s));
         }
-        HIP_CHK(ctx, hipMemcpyAsync(ha.data(), oacc.p, ha.size() * 8, hipMemcpyDeviceToHost, s));
+        HIP_CHK(ctx, hipMemcpyAsync(H.a.data(), T.oacc.p, H.a.size() * 8, hipMemcpyDeviceToHost, s));
         HIP_CHK(ctx, hipStreamSynchronize(s));
     }
-    /* a plain aggregate returns its one group over no rows as well */
-    const int64_t nres = (nk == 0) ? 1 : ng;
+    return GX_OK;
+}
+
+/* FINISH (pure host): sort the groups, un-image MIN / MAX, apply the NULL
+ * rule, fill the result.  plain_one: a plain aggregate returns its one group
+ * over no rows as well. */
+static gx_status gbd_finish(const gbd_args &a, const gbd_host_groups &H,
+                            bool plain_one, gx_gb_result *out)
+{
+    const int nk = a.nkeys, na = a.naggs, words = a.awords;
+    const int64_t ng = H.ng;
+    const int64_t nres = (nk == 0 && plain_one) ? 1 : ng;
     std::vector<int64_t> perm((size_t) ng);
-    if (nk) gbd_sort_perm(hk.data(), hn.data(), ng, nk, perm.data());
-    else if (ng) perm[0] = 0;
+    if (nk) gbd_sort_perm(H.k.data(), H.n.data(), ng, nk, perm.data());
+    else for (int64_t i = 0; i < ng; i++) perm[i] = i;
 
     out->keys = (int64_t *) calloc(std::max<size_t>((size_t) nres * nk, 1), 8);
     out->key_null = (uint8_t *) calloc(std::max<size_t>((size_t) nres * nk, 1), 1);
@@ -6918,11 +7222,11 @@ static gx_status gbd_run(gx_ctx *ctx, const gx_gb_desc *d, int grid, bool wide,
     {
         /* acc stays all-identity for the plain aggregate over no rows */
         static const unsigned long long zero[GBD_MAX_WORDS] = {};
-        const unsigned long long *acc = ng ? &ha[(size_t) perm[gi] * words] : zero;
+        const unsigned long long *acc = ng ? &H.a[(size_t) perm[gi] * words] : zero;
         for (int k = 0; k < nk; k++)
         {
-            out->keys[gi * nk + k] = hk[(size_t) perm[gi] * nk + k];
-            out->key_null[gi * nk + k] = hn[(size_t) perm[gi] * nk + k];
+            out->keys[gi * nk + k] = H.k[(size_t) perm[gi] * nk + k];
+            out->key_null[gi * nk + k] = H.n[(size_t) perm[gi] * nk + k];
         }
         for (int j = 0; j < na; j++)
         {
@@ -6945,6 +7249,40 @@ static gx_status gbd_run(gx_ctx *ctx, const gx_gb_desc *d, int grid, bool wide,
             out->agg_null[gi * na + j] = (uint8_t) isnull;
         }
     }
+    return GX_OK;
+}
+
+/* the argument checks every entry point starts with */
+static gx_status gbd_check_call(gx_ctx *ctx, const gx_gb_desc *d, gx_gb_result *out)
+{
+    if (!ctx || !d || !out) return GX_ERR_INVALID;
+    memset(out, 0, sizeof *out);
+    if (!d->t) { set_err(ctx, "groupby_desc: no table%s", ""); return GX_ERR_INVALID; }
+    return GX_OK;
+}
+
+/* The one-stage plan: plan, bind, scan, extract, finish.  grid and wide come
+ * from the caller (production: GRID, nrows >= 2^32 - 1), lds from GX_GB_LDS,
+ * so the public call and the test entry run the same launches. */
+static gx_status gbd_run(gx_ctx *ctx, const gx_gb_desc *d, int grid, bool wide,
+                         bool lds, gx_gb_result *out, gx_gbd_stats *stats)
+{
+    gx_status st = gbd_check_call(ctx, d, out);
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (st != GX_OK) return st;
+    gbd_args a;
+    if ((st = gbd_plan(ctx, d, d->t, a)) != GX_OK) return st;
+    gbd_inputs in;
+    gbd_table T;
+    evholder e0, e1;
+    HIP_CHK(ctx, e0.create()); HIP_CHK(ctx, e1.create());
+    st = gbd_scan_stage(ctx, d, a, in, T, grid, wide, lds, 0, e0, e1);
+    if (st != GX_OK) return st;
+    const int64_t n = d->t->nrows;
+    unsigned long long hm[4] = {0, 0, 0, 0};
+    gbd_host_groups H;
+    if ((st = gbd_fetch(ctx, a, T, d->max_groups, hm, H)) != GX_OK) return st;
+    if ((st = gbd_finish(a, H, true, out)) != GX_OK) return st;
     if (stats)
     {
         float ms = 0;
@@ -6954,7 +7292,7 @@ static gx_status gbd_run(gx_ctx *ctx, const gx_gb_desc *d, int grid, bool wide,
         stats->rows_pass = (int64_t) hm[0];
         stats->rows_lds = (int64_t) hm[1];
         stats->rows_global = (int64_t) (hm[0] - hm[1]);
-        stats->groups = nres;
+        stats->groups = out->ngroups;
     }
     return GX_OK;
 }
@@ -6975,6 +7313,324 @@ extern "C" gx_status gx_test_groupby_desc(gx_ctx *ctx, const gx_gb_desc *d,
     bool wide = wide_rowid != 0 ||
                 (d && d->t && d->t->nrows >= (int64_t) UINT32_MAX);
     return gbd_run(ctx, d, grid == 0 ? GRID : grid, wide, gbd_env_lds(), out, stats);
+}
+
+/* ---- two-stage descriptor GROUP BY: host side ----
+ * (kernels: k_gbd_part_hist, k_gbd_part_emit, k_gbd_combine) */
+
+/* bit k set: key column k is 8 bytes wide (hashint8; the others hashint4) */
+static unsigned gbd_wide_mask(const gx_gb_desc *d)
+{
+    unsigned m = 0;
+    for (int k = 0; k < d->nkeys; k++)
+        if (d->t->cols[d->key_cols[k]].m.width == 8) m |= 1u << k;
+    return m;
+}
+
+static int64_t gbd_wire_words(const gbd_args &a)
+{
+    return a.nkeys + (a.nkeys ? 1 : 0) + a.awords;
+}
+
+/* grid of the partition kernels: they walk at most T.bound groups */
+static int gbd_part_grid(const gbd_table &T)
+{
+    return (int) std::min<int64_t>(GRID, (T.bound + TPB - 1) / TPB);
+}
+
+static void gbd_part_hist(gx_ctx *ctx, const gbd_args &a, const gbd_table &T,
+                          unsigned wide, int nsegs, uint16_t *ddest,
+                          unsigned long long *dhist)
+{
+    hipLaunchKernelGGL(k_gbd_part_hist, dim3(gbd_part_grid(T)), dim3(TPB),
+                       (size_t) nsegs * 4, ctx->stream, T.okeys.as<int64_t>(),
+                       T.oknull.as<uint8_t>(), T.stat(), T.bound, a.nkeys, wide,
+                       nsegs, ddest, dhist);
+}
+
+static void gbd_part_emit(gx_ctx *ctx, const gbd_args &a, const gbd_table &T,
+                          int nsegs, const uint16_t *ddest,
+                          unsigned long long *dcur, void *dsend)
+{
+    hipLaunchKernelGGL(k_gbd_part_emit, dim3(gbd_part_grid(T)), dim3(TPB),
+                       (size_t) nsegs * 12, ctx->stream, T.okeys.as<int64_t>(),
+                       T.oknull.as<uint8_t>(), T.oacc.as<unsigned long long>(),
+                       T.stat(), T.bound, a.nkeys, a.awords, nsegs, ddest, dcur,
+                       (unsigned long long *) dsend);
+}
+
+/* COMBINE stage over n device-resident wire rows: budget, table, merge,
+ * extract, finish.  ev_done (optional) is recorded after the last kernel. */
+static gx_status gbd_combine(gx_ctx *ctx, const gbd_args &a, int64_t max_groups,
+                             const void *drows, int64_t n, bool wide,
+                             hipEvent_t ev_done, gx_gb_result *out)
+{
+    if (!wide && n >= (int64_t) UINT32_MAX)
+        return gbd_invalid(ctx, "%ld rows need the 8-byte slot word", (long) n);
+    /* the table is pow2 >= 2 * recv_rows; the groups are bounded by the
+     * rows and by the planner's bound */
+    gbd_table T;
+    const int64_t rows_bound = std::max<int64_t>(n, 1);
+    gx_status st = gbd_table_budget(ctx, a, rows_bound, wide, 0,
+                                    "groupby_desc combine table");
+    if (st != GX_OK) return st;
+    if ((st = gbd_table_alloc(ctx, T, a, rows_bound, wide)) != GX_OK) return st;
+    if (max_groups > 0) T.bound = std::min<int64_t>(T.bound, max_groups);
+    const gbd_key_wire src{(const unsigned long long *) drows, gbd_wire_words(a)};
+    if (n)
+    {
+        const int grid = (int) std::min<int64_t>(GRID, (n + TPB - 1) / TPB);
+        by_width((int) T.sw, T.trow.p, [&](auto *rows) {
+            hipLaunchKernelGGL(k_gbd_combine<std::decay_t<decltype(*rows)>>,
+                               dim3(grid), dim3(TPB), 0, ctx->stream, a, src, n,
+                               rows, T.tacc.as<unsigned long long>(),
+                               T.tslots - 1, T.err());
+        });
+        gbd_extract(ctx, a, src, T);
+    }
+    if (ev_done) HIP_CHK(ctx, hipEventRecord(ev_done, ctx->stream));
+    unsigned long long hm[4] = {0, 0, 0, 0};
+    gbd_host_groups H;
+    if ((st = gbd_fetch(ctx, a, T, max_groups, hm, H)) != GX_OK) return st;
+    return gbd_finish(a, H, false, out);
+}
+
+static gx_status gbd_partial_failed(gx_ctx *ctx)
+{
+    set_err(ctx, "groupby_desc: more groups than max_groups%s", "");
+    return GX_ERR_INVALID;
+}
+
+extern "C" gx_status gx_groupby_desc_dist(gx_ctx *ctx, const gx_gb_desc *d,
+                                          gx_gb_result *out, gx_gb_stats *stats)
+{
+    gx_status st = gbd_check_call(ctx, d, out);
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (st != GX_OK) return st;
+    const gx_table *t = d->t;
+    const bool wide = t->nrows >= (int64_t) UINT32_MAX;
+    gx_gb_stats S{};
+    S.rows_in = t->nrows;
+    /* one-stage plan: nothing to redistribute on a single segment.
+     * GX_FORCE_MOTION=1 routes a single-segment run through the full
+     * exchange branch, as in gx_groupby_dist. */
+    if (ctx->nsegs == 1 && env_int("GX_FORCE_MOTION", 0) == 0)
+    {
+        gx_gbd_stats one{};
+        st = gbd_run(ctx, d, GRID, wide, gbd_env_lds(), out, &one);
+        if (st != GX_OK) return st;
+        S.ms_partial = one.ms_kernel;
+        S.partial_groups = S.final_groups = out->ngroups;
+        if (stats) *stats = S;
+        return GX_OK;
+    }
+    gbd_args a;
+    if ((st = gbd_plan(ctx, d, t, a)) != GX_OK) return st;
+    if (!ctx->comm)
+    { set_err(ctx, "nsegs>1 but gx_comm_init not called%s", ""); return GX_ERR_STATE; }
+    const int n = ctx->nsegs;
+    if (n > GB_MAX_SEGS)
+    { set_err(ctx, "groupby_desc_dist: more segments than the partition kernels' LDS histogram holds%s", ""); return GX_ERR_INVALID; }
+
+    hipStream_t s = ctx->stream;
+    evholder ev[7];
+    for (auto &e : ev) HIP_CHK(ctx, e.create());
+    auto ms_between = [](hipEvent_t x, hipEvent_t y) {
+        float ms = 0;
+        (void) hipEventElapsedTime(&ms, x, y);
+        return (double) ms;
+    };
+
+    /* stage 1: partial agg; the groups, their count and the error word stay
+     * on the device */
+    gbd_inputs in;
+    gbd_table T;
+    const uint64_t side = (uint64_t) std::max<int64_t>(t->nrows, 1) * 2 +
+                          (uint64_t) n * (n + 2) * 8;
+    st = gbd_scan_stage(ctx, d, a, in, T, GRID, wide, gbd_env_lds(), side, ev[0],
+                        nullptr);
+    if (st != GX_OK) return st;
+    HIP_CHK(ctx, hipEventRecord(ev[1], s));
+
+    /* stage 2: partition.  The per-destination histogram goes straight into
+     * the all-gather, so ONE host sync yields this rank's send layout, every
+     * peer's counts, the partial group count and the error word. */
+    devbuf hist_b, cur_b, all_b, dest_b;
+    HIP_CHK(ctx, hist_b.alloc((size_t) n * 8));
+    HIP_CHK(ctx, cur_b.alloc((size_t) n * 8));
+    HIP_CHK(ctx, all_b.alloc((size_t) n * n * 8));
+    HIP_CHK(ctx, dest_b.alloc((size_t) T.bound * 2));
+    unsigned long long *dhist = hist_b.as<unsigned long long>();
+    HIP_CHK(ctx, hipMemsetAsync(dhist, 0, (size_t) n * 8, s));
+    gbd_part_hist(ctx, a, T, gbd_wide_mask(d), n, dest_b.as<uint16_t>(), dhist);
+    HIP_CHK(ctx, hipEventRecord(ev[2], s));
+    RCCL_CHK(ctx, ncclAllGather(dhist, all_b.p, n, ncclUint64, ctx->comm, s));
+    std::vector<unsigned long long> cnts_all((size_t) n * n);
+    unsigned long long hm[4] = {0, 0, 0, 0};
+    HIP_CHK(ctx, hipMemcpyAsync(cnts_all.data(), all_b.p, (size_t) n * n * 8,
+                                hipMemcpyDeviceToHost, s));
+    HIP_CHK(ctx, hipMemcpyAsync(hm, T.misc.p, 32, hipMemcpyDeviceToHost, s));
+    HIP_CHK(ctx, hipStreamSynchronize(s));
+    HIP_CHK(ctx, hipGetLastError());
+    const bool failed = (hm[3] & 1) || (int64_t) hm[2] > T.bound;
+    const gx_mlayout L = m_exchange_layout(cnts_all.data(), n, ctx->seg);
+    const unsigned long long send_n = L.send_n, recv_n = L.recv_n;
+    const size_t stride = (size_t) gbd_wire_words(a) * 8;
+    st = hbm_budget_check(ctx, (send_n + recv_n) * stride + 64,
+                          "groupby_desc exchange buffers");
+    if (st != GX_OK) return st;
+    devbuf send_b, recv_b;
+    HIP_CHK(ctx, send_b.alloc(send_n * stride));
+    HIP_CHK(ctx, recv_b.alloc(recv_n * stride));
+    HIP_CHK(ctx, hipMemcpyAsync(cur_b.p, L.soff.data(), (size_t) n * 8,
+                                hipMemcpyHostToDevice, s));
+    HIP_CHK(ctx, hipEventRecord(ev[3], s));
+    gbd_part_emit(ctx, a, T, n, dest_b.as<uint16_t>(),
+                  cur_b.as<unsigned long long>(), send_b.p);
+    HIP_CHK(ctx, hipEventRecord(ev[4], s));
+
+    /* stage 3: exchange */
+    st = m_exchange_payload(ctx, s, send_b.p, recv_b.p, L, stride);
+    if (st != GX_OK) return st;
+    HIP_CHK(ctx, hipEventRecord(ev[5], s));
+    /* a failed partial stage sent no rows and is reported only now, after
+     * this rank's sends and receives are enqueued, so the peers' matching
+     * calls still complete */
+    if (failed)
+    {
+        HIP_CHK(ctx, hipStreamSynchronize(s));
+        return gbd_partial_failed(ctx);
+    }
+
+    /* stage 4: combine agg over the received partial states */
+    st = gbd_combine(ctx, a, d->max_groups, recv_b.p, (int64_t) recv_n,
+                     recv_n >= (unsigned long long) UINT32_MAX, ev[6], out);
+    if (st != GX_OK) return st;
+
+    S.ms_partial = ms_between(ev[0], ev[1]);
+    S.ms_partition = ms_between(ev[1], ev[2]) + ms_between(ev[3], ev[4]);
+    S.ms_exchange = ms_between(ev[2], ev[3]) + ms_between(ev[4], ev[5]);
+    S.ms_combine = ms_between(ev[5], ev[6]);
+    S.partial_groups = S.sent_rows = (int64_t) send_n;
+    S.recv_rows = (int64_t) recv_n;
+    S.final_groups = out->ngroups;
+    if (stats) *stats = S;
+    return GX_OK;
+}
+
+/* Test ABI: partial agg + partition kernels on one GPU for a given nsegs,
+ * through the launch helpers of gx_groupby_desc_dist */
+extern "C" gx_status gx_test_gbd_partial(gx_ctx *ctx, const gx_gb_desc *d,
+                                         int nsegs, int64_t *out_counts,
+                                         void *out_rows, int64_t cap_rows,
+                                         int64_t *out_total)
+{
+    if (!ctx || !d || !out_counts || !out_total || cap_rows < 0 ||
+        (cap_rows > 0 && !out_rows))
+        return GX_ERR_INVALID;
+    if (!d->t) { set_err(ctx, "groupby_desc: no table%s", ""); return GX_ERR_INVALID; }
+    if (nsegs < 1 || nsegs > GB_MAX_SEGS)
+        return gbd_invalid(ctx, "nsegs %ld outside 1..%ld", nsegs, GB_MAX_SEGS);
+    gbd_args a;
+    gx_status st = gbd_plan(ctx, d, d->t, a);
+    if (st != GX_OK) return st;
+    hipStream_t s = ctx->stream;
+    const bool wide = d->t->nrows >= (int64_t) UINT32_MAX;
+    gbd_inputs in;
+    gbd_table T;
+    const uint64_t side = (uint64_t) std::max<int64_t>(d->t->nrows, 1) * 2 +
+                          (uint64_t) nsegs * 16;
+    st = gbd_scan_stage(ctx, d, a, in, T, GRID, wide, gbd_env_lds(), side, nullptr,
+                        nullptr);
+    if (st != GX_OK) return st;
+    devbuf hist_b, cur_b, dest_b, send_b;
+    HIP_CHK(ctx, hist_b.alloc((size_t) nsegs * 8));
+    HIP_CHK(ctx, cur_b.alloc((size_t) nsegs * 8));
+    HIP_CHK(ctx, dest_b.alloc((size_t) T.bound * 2));
+    HIP_CHK(ctx, hipMemsetAsync(hist_b.p, 0, (size_t) nsegs * 8, s));
+    gbd_part_hist(ctx, a, T, gbd_wide_mask(d), nsegs, dest_b.as<uint16_t>(),
+                  hist_b.as<unsigned long long>());
+    std::vector<unsigned long long> h(nsegs), off(nsegs + 1, 0);
+    unsigned long long hm[4] = {0, 0, 0, 0};
+    HIP_CHK(ctx, hipMemcpyAsync(h.data(), hist_b.p, (size_t) nsegs * 8,
+                                hipMemcpyDeviceToHost, s));
+    HIP_CHK(ctx, hipMemcpyAsync(hm, T.misc.p, 32, hipMemcpyDeviceToHost, s));
+    HIP_CHK(ctx, hipStreamSynchronize(s));
+    HIP_CHK(ctx, hipGetLastError());
+    if ((hm[3] & 1) || (int64_t) hm[2] > T.bound) return gbd_partial_failed(ctx);
+    for (int i = 0; i < nsegs; i++) off[i + 1] = off[i] + h[i];
+    const int64_t total = (int64_t) off[nsegs];
+    if (total > cap_rows)
+    { set_err(ctx, "gbd_partial: output capacity too small%s", ""); return GX_ERR_INVALID; }
+    const size_t stride = (size_t) gbd_wire_words(a) * 8;
+    st = hbm_budget_check(ctx, (uint64_t) total * stride + 64,
+                          "groupby_desc exchange buffers");
+    if (st != GX_OK) return st;
+    HIP_CHK(ctx, send_b.alloc((size_t) total * stride));
+    HIP_CHK(ctx, hipMemcpyAsync(cur_b.p, off.data(), (size_t) nsegs * 8,
+                                hipMemcpyHostToDevice, s));
+    gbd_part_emit(ctx, a, T, nsegs, dest_b.as<uint16_t>(),
+                  cur_b.as<unsigned long long>(), send_b.p);
+    if (total)
+        HIP_CHK(ctx, hipMemcpyAsync(out_rows, send_b.p, (size_t) total * stride,
+                                    hipMemcpyDeviceToHost, s));
+    HIP_CHK(ctx, hipStreamSynchronize(s));
+    HIP_CHK(ctx, hipGetLastError());
+    for (int i = 0; i < nsegs; i++) out_counts[i] = (int64_t) h[i];
+    *out_total = total;
+    return GX_OK;
+}
+
+/* Test ABI: the combine stage over host-supplied wire rows */
+extern "C" gx_status gx_test_gbd_combine(gx_ctx *ctx, const gx_gb_desc *d,
+                                         const void *rows, int64_t n,
+                                         int wide_rowid, gx_gb_result *out)
+{
+    if (!ctx || !d || !out || n < 0 || (n > 0 && !rows)) return GX_ERR_INVALID;
+    memset(out, 0, sizeof *out);
+    gbd_args a;
+    gx_status st = gbd_plan(ctx, d, nullptr, a);
+    if (st != GX_OK) return st;
+    const size_t stride = (size_t) gbd_wire_words(a) * 8;
+    st = hbm_budget_check(ctx, (uint64_t) n * stride + 64,
+                          "groupby_desc exchange buffers");
+    if (st != GX_OK) return st;
+    devbuf rows_b;
+    HIP_CHK(ctx, rows_b.alloc((size_t) n * stride));
+    if (n)
+        HIP_CHK(ctx, hipMemcpyAsync(rows_b.p, rows, (size_t) n * stride,
+                                    hipMemcpyHostToDevice, ctx->stream));
+    return gbd_combine(ctx, a, d->max_groups, rows_b.p, n,
+                       wide_rowid != 0 || n >= (int64_t) UINT32_MAX, nullptr, out);
+}
+
+extern "C" int gx_selftest_gbd_route(const int64_t *keys, const uint8_t *key_null,
+                                     const int32_t *widths, int nkeys, int64_t n,
+                                     int nsegs, int32_t *out)
+{
+    if (n < 0 || nkeys < 0 || nkeys > GX_GB_MAX_KEYS || nsegs < 1 ||
+        (n > 0 && !out) || (nkeys > 0 && !widths) ||
+        (n > 0 && nkeys > 0 && (!keys || !key_null)))
+        return 1;
+    unsigned wide = 0;
+    for (int k = 0; k < nkeys; k++)
+    {
+        if (!gbd_int_width(widths[k])) return 1;
+        if (widths[k] == 8) wide |= 1u << k;
+    }
+    for (int64_t i = 0; i < n; i++)
+    {
+        int64_t kv[GX_GB_MAX_KEYS] = {0, 0, 0, 0};
+        unsigned kn = 0;
+        for (int k = 0; k < nkeys; k++)
+        {
+            const bool isnull = key_null[i * nkeys + k] != 0;
+            kv[k] = isnull ? 0 : keys[i * nkeys + k];
+            kn |= (unsigned) isnull << k;
+        }
+        out[i] = gbd_owner(kv, kn, wide, nkeys, nsegs);
+    }
+    return 0;
 }
 
 /* ABI self-description: struct sizes for cross-checking foreign-language

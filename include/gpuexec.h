@@ -387,7 +387,9 @@ gx_status gx_groupby_dist(gx_ctx *ctx, const gx_table *t, int key_col,
 /* ---- descriptor-form hash GROUP BY: what a planner lowers an Agg node over
  * a SeqScan to (nodeAgg.c:2288 hash strategy, execScan.c:161-263 qual scan).
  * Several integer key columns, a list of aggregates, AND-ed WHERE quals.
- * One-stage only: the two-stage/Motion form is gx_groupby_dist's.
+ * gx_groupby_desc runs the one-stage plan over this segment's rows;
+ * gx_groupby_desc_dist below is the two-stage/Motion form of the same
+ * descriptor.
  *
  * Keys: 0..GX_GB_MAX_KEYS integer columns of width 1, 2, 4 or 8, format 0 or
  *   format 1 (NULL bitmaps included; width 2 binds as format 1 only).
@@ -462,6 +464,48 @@ void      gx_gb_result_free(gx_gb_result *);
 /* groups one workgroup's LDS table holds for a call with naggs aggregates */
 int32_t   gx_gb_lds_groups(int naggs);
 
+/* ---- two-stage descriptor GROUP BY through Motion: partial agg per segment
+ * (the one-stage scan, its accumulator words are the transition state), hash
+ * redistribution of the partial states by group key, combine agg on the
+ * owning segment (cdbgroupingpaths.c:251; combine step nodeAgg.c:2305,2321).
+ * Same descriptor, validation, error texts, result struct and result order as
+ * gx_groupby_desc; returns the groups THIS segment owns:
+ *   owner = jump_consistent_hash(cdbhash over the key columns, nsegs), a
+ *   width-8 column hashed with hashint8, widths 1, 2 and 4 with hashint4 of
+ *   the sign-extended value (hashchar / hashint2 / hashint4, hashfunc.c), a
+ *   NULL column contributing the rotation only (cdbhash.c:189-247): (NULL, 1)
+ *   and (0, 1) may live on different segments and never merge.
+ * nkeys == 0 is a Gather: every segment's partial stage ships exactly one
+ *   state row, also over an empty or fully filtered shard; segment 0 returns
+ *   the one group, every other segment ngroups == 0.
+ * nsegs == 1 without GX_FORCE_MOTION runs the one-stage plan (same output as
+ *   gx_groupby_desc, motion stats zero); otherwise gx_comm_init must have been
+ *   called (GX_ERR_STATE).  More than 2048 segments is GX_ERR_INVALID.
+ * max_groups bounds each segment's partial table and the combine result
+ *   (the combine table itself is pow2 >= 2 * recv_rows); either stage
+ *   exceeding it is GX_ERR_INVALID "more groups than max_groups".  A rank
+ *   whose partial stage failed still takes part in the count all-gather and
+ *   the payload exchange, sending no rows, and reports afterwards.  The HBM
+ *   budget is checked before the partial table, the exchange buffers and the
+ *   combine table are allocated (GX_ERR_OOM).
+ * One host sync per Motion: the partial group count and the error word
+ *   reach the host with the all-gathered counts.
+ * stats: gx_gb_stats as gx_groupby_dist fills it; rows_in = nrows.
+ *
+ * Wire row of the exchange (fixed stride, 8-byte aligned, deterministic
+ * bytes; also the row format of the two test entry points below):
+ *   int64  keys[nkeys]       sign-extended; 0 where NULL
+ *   uint8  key_null[nkeys]   zero-padded to 8 bytes; absent when nkeys == 0
+ *   uint64 acc[awords]       the state words exactly as the table holds them
+ * acc[] is opaque: order-preserving images for MIN / MAX, and the non-NULL
+ * input count word behind SUM / MIN / MAX.  COUNTs take one word, the others
+ * two; the stride is 8 * (nkeys + (nkeys ? 1 : 0) + awords) <= 168 bytes.
+ * gx_gbd_wire_stride returns it from nkeys and the aggregates' fn / is_f64
+ * alone (host only, t is never read), or -1 for a bad nkeys, naggs or fn. ---- */
+gx_status gx_groupby_desc_dist(gx_ctx *, const gx_gb_desc *, gx_gb_result *out,
+                               gx_gb_stats *stats /* may be NULL */);
+int64_t   gx_gbd_wire_stride(const gx_gb_desc *);
+
 /* ---- test-only entry points (parity harness; not part of the drop-in) ---- */
 /* gx_groupby_desc through the same launch helper with the scan grid and the
  * slot word chosen by the caller: grid = 0 is production (2048 workgroups),
@@ -475,6 +519,24 @@ gx_status gx_test_groupby_desc(gx_ctx *, const gx_gb_desc *, int grid,
  * column, ascending and stable.  Returns 0, or 1 for bad arguments. */
 int gx_selftest_gb_sort(const int64_t *keys, const uint8_t *key_null,
                         int64_t n, int nkeys, int64_t *perm);
+/* partial agg + partition for a given nsegs on one GPU: wire rows packed by
+ * destination in destination order (order inside one unspecified);
+ * GX_ERR_INVALID if the total exceeds cap_rows */
+gx_status gx_test_gbd_partial(gx_ctx *, const gx_gb_desc *, int nsegs,
+                              int64_t *out_counts /* nsegs */, void *out_rows,
+                              int64_t cap_rows, int64_t *out_total);
+/* combine over host wire rows; desc->t may be NULL (reads nkeys, aggs,
+ * max_groups); wide_rowid = 1 forces the 8-byte slot word; n == 0 returns
+ * zero groups for every nkeys */
+gx_status gx_test_gbd_combine(gx_ctx *, const gx_gb_desc *, const void *rows,
+                              int64_t n, int wide_rowid, gx_gb_result *out);
+/* host restatement of the routing through the same GX_HD functions, no GPU:
+ * out[i] = owner of row i of n rows of nkeys (0..GX_GB_MAX_KEYS) columns,
+ * row-major keys / key_null, widths[k] in 1, 2, 4, 8.  Returns 0, or 1 for
+ * bad arguments. */
+int gx_selftest_gbd_route(const int64_t *keys, const uint8_t *key_null,
+                          const int32_t *widths, int nkeys, int64_t n,
+                          int nsegs, int32_t *out);
 typedef struct gx_ord_row { int64_t okey, ocust; int32_t odate, oprio; } gx_ord_row;
 /* Motion-1 partition kernels on one GPU: filter orders by cutoff, route by
  * cdbhash(o_custkey), emit packed rows grouped by destination segment. */
