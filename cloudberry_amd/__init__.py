@@ -259,6 +259,12 @@ def _load():
     lib.gx_q3_run.argtypes = [ctypes.c_void_p]
     lib.gx_q3_stats_get.argtypes = [ctypes.c_void_p, ctypes.POINTER(_Stats)]
     lib.gx_q3_dim_mode.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
+    lib.gx_q3_table_mode.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
+    lib.gx_selftest_rank_eligible.restype = ctypes.c_int
+    lib.gx_selftest_rank_eligible.argtypes = [ctypes.c_int64, ctypes.c_uint64,
+                                              ctypes.c_uint64, ctypes.c_int]
+    lib.gx_rank_scan_block_keys.restype = ctypes.c_int64
+    lib.gx_rank_scan_block_keys.argtypes = []
     lib.gx_q3_result.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.POINTER(_Group)),
                                  ctypes.POINTER(ctypes.c_int64)]
     lib.gx_q3_topn.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
@@ -403,6 +409,20 @@ def unmatched_bound(nrows, lmin, lmax):
     only, no GPU)."""
     return int(lib().gx_selftest_unmatched_bound(
         int(nrows), int(lmin) & (2**64 - 1), int(lmax) & (2**64 - 1)))
+
+
+def rank_eligible(qual, kmin, kmax, enabled=True):
+    """Sizing's rule for the rank form of the Q3 join/agg table: qual
+    qualifying mid rows whose keys span [kmin, kmax] as unsigned 64-bit words
+    (host only, no GPU)."""
+    return bool(lib().gx_selftest_rank_eligible(
+        int(qual), int(kmin) & (2**64 - 1), int(kmax) & (2**64 - 1),
+        1 if enabled else 0))
+
+
+def rank_scan_block_keys():
+    """Keys one block of the rank table's prefix-popcount scan covers."""
+    return int(lib().gx_rank_scan_block_keys())
 
 
 def gb_lds_groups(naggs):
@@ -1145,6 +1165,18 @@ class Q3:
         1 = exact bitmap (dense keys, local path)."""
         m = ctypes.c_int()
         self.ctx._chk(self.ctx._lib.gx_q3_dim_mode(self._q, ctypes.byref(m)))
+        return m.value
+
+    def set_numeric(self, on=True):
+        """Switch numeric(15,2) mode (scaled-int64 measures) for later runs."""
+        self.ctx._chk(self.ctx._lib.gx_q3_set_numeric(self._q, 1 if on else 0))
+        return self
+
+    def table_mode(self):
+        """Join/agg table form the last run used: 0 = open-addressing hash
+        table, 1 = rank table (dense mid keys, local f64 path)."""
+        m = ctypes.c_int()
+        self.ctx._chk(self.ctx._lib.gx_q3_table_mode(self._q, ctypes.byref(m)))
         return m.value
 
     def result(self):

@@ -814,7 +814,10 @@ struct gx_dimbits {
  * just issues its own atomic).  Every lane of the wave must call this.
  * Measured at SF100: customer stage 0.08 ms, against 0.15 ms with one plain
  * atomicOr per key and 0.30 ms for bloom + CAS inserts
- * (profiles/dimbitmap_kernels.txt). */
+ * (profiles/dimbitmap_kernels.txt).
+ * STRIDE is the distance between bit words in 8-byte units: 1 for a plain
+ * bitmap, 2 for the rank table's interleaved {bits, base} entries. */
+template <int STRIDE = 1>
 __device__ __forceinline__ void d_dimbits_set_wave(unsigned long long *bits,
                                                    uint64_t kmin, uint64_t range,
                                                    bool act, uint64_t k)
@@ -836,9 +839,41 @@ __device__ __forceinline__ void d_dimbits_set_wave(unsigned long long *bits,
             for (int o = 32; o; o >>= 1)
                 v |= __shfl_xor(v, o, 64);
         if (lane == lead)
-            atomicOr(&bits[w0], v);
+            atomicOr(&bits[w0 * STRIDE], v);
         todo &= ~grp;
     }
+}
+
+/* Rank-addressed join/agg table for dense mid keys (the local f64 path):
+ * one bit per key of [kmin, kmin+range) and, per 64-bit word, the number of
+ * set bits in all words before it.  rank(k) = base[word] + popcount of the
+ * word's bits below k's is then a dense, collision-free group index in
+ * [0, distinct keys): a lookup is one load and no walk, and the payload
+ * arrays hold `qual` slots instead of 3 x qual hashed ones.
+ * The two sit interleaved in 16-byte entries {u64 bits; u64 base}, one load;
+ * separate bits[] and u32 base[] arrays (two independent loads, 12 B per
+ * word) measured 0.01-0.02 ms slower in the probe
+ * (profiles/rank_table_kernels.txt).
+ * qual is the number of payload slots: an index at or past it is a miss, so
+ * input that changed after sizing can drop rows but never leaves an
+ * allocation. */
+struct gx_rankview {
+    const ulonglong2 *ent;             /* ceil(range/64) x {bits, base} */
+    uint64_t kmin, range, qual;
+};
+
+/* words of one block of the prefix-popcount scan (k_rank_*), 8 per thread */
+static constexpr int GX_RANK_SCAN_WORDS = 8 * TPB;
+
+/* dense index of key k, or ~0ULL when k is not in the table */
+__device__ __forceinline__ uint64_t d_rank_find(const gx_rankview &rv, uint64_t k)
+{
+    uint64_t d = k - rv.kmin;          /* k < kmin wraps to d >= range */
+    if (d >= rv.range) return ~0ULL;
+    ulonglong2 e = rv.ent[d >> 6];
+    int sh = (int) (d & 63);
+    uint64_t idx = e.y + (uint64_t) __popcll(e.x & ((1ULL << sh) - 1ULL));
+    return (((e.x >> sh) & 1ULL) && idx < rv.qual) ? idx : ~0ULL;
 }
 
 /* the bloom half of the HASH form */
@@ -1498,6 +1533,147 @@ __global__ void k_orders_build(const uint8_t *ok_s, gx_colmeta ok_m,
     }
 }
 
+/* ---- orders stage in rank form (gx_rankview): mark, prefix popcounts, fill.
+ * Replaces k_orders_build when the run uses the rank table. ---- */
+
+/* Mark: k_orders_build's filters and dim test; a qualifying row sets its
+ * key's bit (d_dimbits_set_wave, so whole waves iterate together: no
+ * `continue`, wave-uniform bounds) and the wave's qualifying mask goes to
+ * rowmask[row / 64] with one plain store — every word of the mask is
+ * rewritten each run.  The fill kernel selects rows by that mask, not by the
+ * key's bit, so a key on two rows of which one fails the filter keeps the
+ * qualifying row's attrs.  blockDim.x must be a multiple of 64. */
+template <typename KS, bool VM = false, bool ANTI = false, bool BM = false>
+__global__ void k_orders_mark(const uint8_t *ok_s, gx_colmeta ok_m,
+                              const uint8_t *oc_s, gx_colmeta oc_m,
+                              const uint8_t *od_s, gx_colmeta od_m,
+                              const uint8_t *vmap, int oop, int32_t olit,
+                              const KS *cset, uint64_t cmask,
+                              const unsigned long long *bloom, uint64_t bwmask,
+                              gx_dimbits bm,
+                              ulonglong2 *rent, uint64_t kmin,
+                              uint64_t range, unsigned long long *rowmask)
+{
+    const int lane = (int) (threadIdx.x & 63);
+    int64_t base = blockIdx.x * (int64_t) blockDim.x + threadIdx.x - lane;
+    int64_t stride = gridDim.x * (int64_t) blockDim.x;
+    for (; base < ok_m.nrows; base += stride)
+    {
+        int64_t r = base + lane;
+        bool act = r < ok_m.nrows;
+        if constexpr (VM)
+            act = act && !gx_vm_hidden(vmap, r);
+        uint64_t ck = 0, k = 0;
+        if constexpr (BM)
+        {
+            /* early fk load, non-temporal streams: see k_orders_build */
+            int32_t od = 0;
+            if (act)
+            {
+                od = gx_col_get_nt<int32_t>(od_s, od_m, r);
+                ck = (uint64_t) gx_col_get_nt<int64_t>(oc_s, oc_m, r);
+            }
+            act = act && gx_cmp(oop, od, olit);
+        }
+        else
+        {
+            act = act && gx_cmp(oop, gx_col_get<int32_t>(od_s, od_m, r), olit);
+            if (act) ck = (uint64_t) gx_col_get<int64_t>(oc_s, oc_m, r);
+        }
+        if (act)
+            act = d_dim_contains<BM>(cset, cmask, bloom, bwmask, bm, ck) != ANTI;
+        if (act)
+        {
+            if constexpr (BM)
+                k = (uint64_t) gx_col_get_nt<int64_t>(ok_s, ok_m, r);
+            else
+                k = (uint64_t) gx_col_get<int64_t>(ok_s, ok_m, r);
+        }
+        act = act && (k - kmin) < range;
+        d_dimbits_set_wave<2>(reinterpret_cast<unsigned long long *>(rent),
+                              kmin, range, act, k);
+        unsigned long long m = __ballot(act);
+        if (lane == 0) rowmask[base >> 6] = m;
+    }
+}
+
+/* Prefix popcounts, three launches and no workgroup waits on another:
+ * k_rank_blocksum (set bits of each block of GX_RANK_SCAN_WORDS words),
+ * k_rank_topscan (one block: exclusive scan of the block sums in place),
+ * k_rank_localscan (per block: exclusive scan of its words + block base). */
+__global__ void __launch_bounds__(TPB)
+k_rank_blocksum(const ulonglong2 *rent, uint64_t nwords, uint32_t *blk)
+{
+    __shared__ uint32_t s_w[TPB / 64];
+    uint64_t w0 = (uint64_t) blockIdx.x * GX_RANK_SCAN_WORDS;
+    uint32_t acc = 0;
+    for (int j = threadIdx.x; j < GX_RANK_SCAN_WORDS; j += TPB)
+    {
+        uint64_t w = w0 + (uint64_t) j;
+        if (w < nwords)
+            acc += (uint32_t) __popcll(rent[w].x);
+    }
+    for (int o = 32; o; o >>= 1)
+        acc += __shfl_down(acc, o, 64);
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0)
+    {
+        uint32_t t = 0;
+        for (int i = 0; i < TPB / 64; i++) t += s_w[i];
+        blk[blockIdx.x] = t;
+    }
+}
+
+__global__ void __launch_bounds__(TPB)
+k_rank_topscan(uint32_t *blk, int nblk)
+{
+    __shared__ uint32_t s_part[TPB];
+    d_block_excl_scan(blk, nblk, s_part, nullptr, [&](int i) { return blk[i]; });
+}
+
+__global__ void __launch_bounds__(TPB)
+k_rank_localscan(ulonglong2 *rent, uint64_t nwords, const uint32_t *blk)
+{
+    __shared__ uint32_t s_scan[GX_RANK_SCAN_WORDS];
+    __shared__ uint32_t s_part[TPB];
+    uint64_t w0 = (uint64_t) blockIdx.x * GX_RANK_SCAN_WORDS;
+    int n = (nwords - w0 < (uint64_t) GX_RANK_SCAN_WORDS)
+                ? (int) (nwords - w0) : GX_RANK_SCAN_WORDS;
+    d_block_excl_scan(s_scan, n, s_part, nullptr, [&](int i) {
+        return (uint32_t) __popcll(rent[w0 + (uint64_t) i].x);
+    });
+    uint32_t b0 = blk[blockIdx.x];
+    for (int j = threadIdx.x; j < n; j += TPB)
+        rent[w0 + (uint64_t) j].y = (unsigned long long) (b0 + s_scan[j]);
+}
+
+/* Fill: for the rows the mark kernel kept, store key and attr pair at the
+ * key's rank and zero its agg slot (the d_slot_claim idea: no per-run clear
+ * of the aggregation array).  Mid rows in key order give consecutive ranks,
+ * so a wave's stores are dense.  A duplicate key stores twice to one slot. */
+template <typename KT>
+__global__ void k_orders_fill(const uint8_t *ok_s, gx_colmeta ok_m,
+                              const uint8_t *od_s, gx_colmeta od_m,
+                              const uint8_t *op_s, gx_colmeta op_m,
+                              const unsigned long long *rowmask, gx_rankview rv,
+                              KT *dkey, gx_attrpair *dattr, gx_aggslot *dagg)
+{
+    int64_t i = blockIdx.x * (int64_t) blockDim.x + threadIdx.x;
+    int64_t stride = gridDim.x * (int64_t) blockDim.x;
+    for (; i < ok_m.nrows; i += stride)
+    {
+        if (!((rowmask[i >> 6] >> (i & 63)) & 1ULL)) continue;
+        uint64_t k = (uint64_t) gx_col_get<int64_t>(ok_s, ok_m, i);
+        int32_t a1 = gx_col_get<int32_t>(od_s, od_m, i);
+        int32_t a2 = gx_col_get<int32_t>(op_s, op_m, i);
+        uint64_t idx = d_rank_find(rv, k);
+        if (idx == ~0ULL) continue;
+        dkey[idx] = (KT) k;
+        d_slot_claim(dattr, dagg, idx, a1, a2);
+    }
+}
+
 /* lineitem probe + aggregate — THE dominant kernel.
  * scan (aocsam.c:1131 semantics) + probe (nodeHashjoin.c:553-652) +
  * SUM transition (nodeAgg.c:836 + float.c:769) fused; build slots ARE the
@@ -1505,8 +1681,14 @@ __global__ void k_orders_build(const uint8_t *ok_s, gx_colmeta ok_m,
  * One row per thread per grid-stride iteration.  The kernel is latency-bound
  * at full occupancy (PMC: 85% WAIT_ANY, ~300M L3 probe round-trips); every
  * batched, tiled and LDS-staged form measured slower and was removed
- * (DESIGN.md "Measured bandwidth ceiling"). */
-template <typename KT, bool VM = false, bool OUTER = false>
+ * (DESIGN.md "Measured bandwidth ceiling").
+ * The table lookup has two compile-time forms: the open-addressing walk over
+ * tkey[] (slot0, then d_table_find), and RANK, one 16-byte load from the rank
+ * table (d_rank_find) whose result indexes the dense agg array — what dense
+ * mid keys run on the local path.  At SF100 the kernel takes 4.39-4.43 ms in
+ * the hash form and 3.79-3.86 ms in the rank form
+ * (profiles/rank_table_kernels.txt). */
+template <typename KT, bool VM = false, bool OUTER = false, bool RANK = false>
 __global__ void k_li_probe_agg_t(const uint8_t *lk_s, gx_colmeta lk_m,
                                  const uint8_t *pr_s, gx_colmeta pr_m,
                                  const uint8_t *di_s, gx_colmeta di_m,
@@ -1523,7 +1705,12 @@ __global__ void k_li_probe_agg_t(const uint8_t *lk_s, gx_colmeta lk_m,
                                  unsigned long long *ukey = nullptr,
                                  double *urev = nullptr,
                                  unsigned long long *ucnt = nullptr,
-                                 uint64_t umask = 0)
+                                 uint64_t umask = 0,
+                                 /* RANK: the group index is the key's rank in rv and
+                                  * tagg the dense agg array; tkey and smap
+                                  * are not read.  Trailing, so the hash
+                                  * forms never load it. */
+                                 gx_rankview rv = {})
 {
     uint64_t tmask = smap.mask;
     unsigned long long local_hits = 0;
@@ -1569,8 +1756,14 @@ __global__ void k_li_probe_agg_t(const uint8_t *lk_s, gx_colmeta lk_m,
             if (gx_vm_hidden(vmap, i)) continue;
         if (!gx_cmp(fop, gx_col_get<int32_t>(sh_s, sh_m, i), flit)) continue;
         uint64_t k = (uint64_t) gx_col_get<int64_t>(lk_s, lk_m, i);
-        uint64_t slot = smap.slot0(k);
-        uint64_t r = d_table_find(tkey, tmask, slot, tkey[slot], k);
+        uint64_t r;
+        if constexpr (RANK)
+            r = d_rank_find(rv, k);            /* one load, no walk */
+        else
+        {
+            uint64_t slot = smap.slot0(k);
+            r = d_table_find(tkey, tmask, slot, tkey[slot], k);
+        }
         if (r != ~0ULL) hit(r, i);
         else umiss(k, i);
     }
@@ -3219,6 +3412,22 @@ struct gx_q3 {
     gx_attrpair *tattr = nullptr;    /* claimed slots only — see gx_aggslot */
     gx_aggslot *tagg = nullptr;      /* claimed slots only, never memset */
     uint64_t tmask = 0;
+    uint64_t hash_tslots = 0;        /* local path: slots sizing wants; the
+                                        hash table itself is allocated by the
+                                        first run that needs it */
+    int64_t local_qual = 0;          /* sizing's qualifying mid rows (local) */
+    /* rank form of the join/agg table (gx_rankview): chosen per run when
+     * sizing found the qualifying mid keys dense (rank_ok); its storage is
+     * allocated by the first run that takes it */
+    int rank_ok = 0, rank_kw = 8;
+    int table_mode = 0;              /* form the last run used: 0 hash, 1 rank */
+    uint64_t rank_kmin = 0, rank_range = 0;
+    ulonglong2 *rent = nullptr;            /* {bits, base} per 64 keys */
+    uint32_t *rblk = nullptr;              /* per-scan-block popcounts */
+    unsigned long long *rowmask = nullptr; /* per mid row: qualifies this run */
+    void *dkey = nullptr;                  /* dense arrays, local_qual slots */
+    gx_attrpair *dattr = nullptr;
+    gx_aggslot *dagg = nullptr;
     unsigned long long *dcount = nullptr, *dhits = nullptr, *dmin = nullptr;
     /* motion-path exchange state (nsegs>1), cached across steps */
     unsigned long long *m_hist = nullptr, *m_cur = nullptr;
@@ -5474,6 +5683,8 @@ static void q3_free_runstate(gx_q3 *q)
 {
     auto fr = [](auto *&p) { if (p) { (void) hipFree(p); p = nullptr; } };
     fr(q->cset); fr(q->bloom); fr(q->dbits); fr(q->tkey); fr(q->tattr); fr(q->tagg);
+    fr(q->rent); fr(q->rblk); fr(q->rowmask);
+    fr(q->dkey); fr(q->dattr); fr(q->dagg);
     fr(q->r_okey); fr(q->r_odate); fr(q->r_oprio); fr(q->r_rev); fr(q->r_cnt);
     fr(q->r_flags);
     fr(q->ukey); fr(q->ucnt_u); fr(q->urev);
@@ -5611,34 +5822,106 @@ static uint64_t q3_unmatched_bound(int64_t nrows, uint64_t lmin, uint64_t lmax)
     return std::min<uint64_t>((uint64_t) nrows, span) + 1;
 }
 
-/* (Re)allocate the join/agg table of tslots slots of q->key_width-byte keys
- * and the result arrays for qual groups plus the LEFT-OUTER bound, freeing
- * what was there.  Sizing calls it once; the Motion path again whenever a
- * run's exchanged counts outgrow the cached table. */
+/* (Re)allocate the hash-form join/agg table of tslots slots of
+ * q->key_width-byte keys and the result arrays for qual groups plus the
+ * LEFT-OUTER bound, freeing what was there.  The Motion path calls it at its
+ * first run and whenever a run's exchanged counts outgrow the cached table;
+ * the local path allocates the two halves separately (results at sizing, the
+ * table at the first hash-form run). */
+static gx_status q3_alloc_results(gx_q3 *q, int64_t qual);
+static gx_status q3_alloc_hash(gx_q3 *q, uint64_t tslots);
+
 static gx_status q3_alloc_table(gx_q3 *q, uint64_t tslots, int64_t qual)
+{
+    gx_status st = q3_alloc_hash(q, tslots);
+    if (st != GX_OK) return st;
+    return q3_alloc_results(q, qual);
+}
+
+/* The result arrays are shared by both table forms and both paths: they
+ * never hold fewer than the local path's sizing asked for (local_qual), so a
+ * re-allocation by the Motion path leaves a later local run valid. */
+static gx_status q3_alloc_results(gx_q3 *q, int64_t qual)
 {
     gx_ctx *ctx = q->ctx;
     auto fr = [](auto *&p) { if (p) { (void) hipFree(p); p = nullptr; } };
-    fr(q->tkey); fr(q->tattr); fr(q->tagg);
     fr(q->r_okey); fr(q->r_odate); fr(q->r_oprio); fr(q->r_rev); fr(q->r_cnt);
     fr(q->r_flags);
-    HIP_CHK(ctx, hipMalloc(&q->tkey, tslots * q->key_width));
-    HIP_CHK(ctx, hipMalloc(&q->tattr, tslots * sizeof(gx_attrpair)));
-    HIP_CHK(ctx, hipMalloc(&q->tagg, tslots * sizeof(gx_aggslot)));
-    q->rescap = std::max<int64_t>(qual + q->u_cap, 1);
+    q->rescap = std::max<int64_t>(std::max(qual, q->local_qual) + q->u_cap, 1);
     HIP_CHK(ctx, hipMalloc(&q->r_okey, q->rescap * 8));
     HIP_CHK(ctx, hipMalloc(&q->r_odate, q->rescap * 4));
     HIP_CHK(ctx, hipMalloc(&q->r_oprio, q->rescap * 4));
     HIP_CHK(ctx, hipMalloc(&q->r_rev, q->rescap * 8));
     HIP_CHK(ctx, hipMalloc(&q->r_cnt, q->rescap * 8));
     HIP_CHK(ctx, hipMalloc(&q->r_flags, q->rescap));
+    return GX_OK;
+}
+
+/* the hash form's storage: tslots slots of q->key_width-byte keys */
+static gx_status q3_alloc_hash(gx_q3 *q, uint64_t tslots)
+{
+    gx_ctx *ctx = q->ctx;
+    auto fr = [](auto *&p) { if (p) { (void) hipFree(p); p = nullptr; } };
+    fr(q->tkey); fr(q->tattr); fr(q->tagg);
+    gx_status st = hbm_budget_check(
+        ctx, tslots * (q->key_width + sizeof(gx_attrpair) + sizeof(gx_aggslot)),
+        "join/agg table");
+    if (st != GX_OK) return st;
+    HIP_CHK(ctx, hipMalloc(&q->tkey, tslots * q->key_width));
+    HIP_CHK(ctx, hipMalloc(&q->tattr, tslots * sizeof(gx_attrpair)));
+    HIP_CHK(ctx, hipMalloc(&q->tagg, tslots * sizeof(gx_aggslot)));
     q->tmask = tslots - 1;
     return GX_OK;
 }
 
+/* Whether sizing may pick the rank form (gx_rankview) for qual qualifying
+ * mid rows whose keys span [kmin, kmax]: at least one row, a range of at
+ * most 64 keys per row (the density rule of the interpolation layout and of
+ * the dim bitmap: bits, prefix counts and dense payload then cost at most
+ * 16 B more per row than the payload alone), fewer than 2^32 rows (u32
+ * prefix counts) and the switch not off.  Pure host function;
+ * gx_selftest_rank_eligible. */
+static bool q3_rank_eligible(int64_t qual, uint64_t kmin, uint64_t kmax,
+                             int enabled)
+{
+    if (!enabled || qual <= 0 || kmax < kmin) return false;
+    if ((uint64_t) qual >= (1ULL << 32)) return false;
+    uint64_t span = kmax - kmin;       /* range - 1: cannot wrap */
+    return span < 64 * (uint64_t) qual;
+}
+
+/* first rank-form run of a q: allocate the rank storage */
+static gx_status q3_alloc_rank(gx_q3 *q)
+{
+    gx_ctx *ctx = q->ctx;
+    uint64_t nwords = (q->rank_range + 63) / 64;
+    uint64_t nblk = (nwords + GX_RANK_SCAN_WORDS - 1) / GX_RANK_SCAN_WORDS;
+    uint64_t qual = (uint64_t) q->local_qual;
+    uint64_t mwords = ((uint64_t) q->ord->nrows + 63) / 64;
+    auto fr = [](auto *&p) { if (p) { (void) hipFree(p); p = nullptr; } };
+    fr(q->rent); fr(q->rblk); fr(q->rowmask);   /* a failed earlier try */
+    fr(q->dkey); fr(q->dattr); fr(q->dagg);
+    gx_status st = hbm_budget_check(
+        ctx,
+        nwords * 16 + nblk * 4 + mwords * 8 +
+            qual * (q->rank_kw + sizeof(gx_attrpair) + sizeof(gx_aggslot)),
+        "rank join/agg table");
+    if (st != GX_OK) return st;
+    HIP_CHK(ctx, hipMalloc(&q->rent, nwords * sizeof(ulonglong2)));
+    HIP_CHK(ctx, hipMalloc(&q->rblk, nblk * 4));
+    HIP_CHK(ctx, hipMalloc(&q->rowmask, std::max<uint64_t>(mwords, 1) * 8));
+    HIP_CHK(ctx, hipMalloc(&q->dkey, qual * q->rank_kw));
+    HIP_CHK(ctx, hipMalloc(&q->dattr, qual * sizeof(gx_attrpair)));
+    HIP_CHK(ctx, hipMalloc(&q->dagg, qual * sizeof(gx_aggslot)));
+    return GX_OK;
+}
+
 /* first run only: size the dimension membership structures and join/agg
- * table from counting passes, allocate everything once (reused across bench
- * steps) */
+ * table from counting passes; allocate the dimension structures and the
+ * result arrays (reused across bench steps).  The join/agg table has two
+ * forms, hash and rank (gx_rankview); sizing decides whether the rank form
+ * is allowed and records both forms' dimensions, and the first run that
+ * uses a form allocates its storage. */
 static gx_status q3_size_and_alloc(gx_q3 *q)
 {
     gx_ctx *ctx = q->ctx;
@@ -5857,6 +6140,30 @@ static gx_status q3_size_and_alloc(gx_q3 *q)
          * tf=300 — 300 stays. */
         int tf = env_int("GX_TABLE_FACTOR_PCT", 300);
         uint64_t tslots = (uint64_t) pow2_at_least(qual * tf / 100 + 1);
+        /* Dense keys also get the rank form (gx_rankview): a run on the
+         * local f64 path over a plain fact key then resolves a key with one
+         * load instead of the open-addressing walk, into qual dense slots
+         * instead of tslots hashed ones.  The verdict and (kmin, range, qual)
+         * hold for the life of the q, as the dim bitmap's do; every rank
+         * write is guarded by d < range and idx < qual.  GX_RANK_TABLE=0
+         * forces the hash form (A/B in one binary).  Only the result arrays
+         * are allocated here: each form's table is allocated, and
+         * budget-checked, by the first run that uses it (q3_orders_local,
+         * q3_orders_rank, q3_orders_motion), so a rank-form q never holds
+         * the hash table. */
+        q->rank_ok = q3_rank_eligible(qual, kmin, kmax,
+                                      env_int("GX_RANK_TABLE", 1) != 0);
+        q->rank_kmin = q->rank_ok ? kmin : 0;
+        q->rank_range = q->rank_ok ? kmax - kmin + 1 : 0;
+        q->rank_kw = q->key_width;
+        q->local_qual = qual;
+        q->hash_tslots = tslots;
+        /* Admission stays what it was: the q is refused here unless the
+         * hash form (the larger one) and the result arrays fit the budget,
+         * even when its first run will take the rank form — set_numeric or
+         * a forced Motion may move a later run of the same q to the hash
+         * form, and a q that ran must not start failing for memory.  The
+         * allocations themselves are checked again where they happen. */
         {
             gx_status st = hbm_budget_check(
                 ctx,
@@ -5878,7 +6185,7 @@ static gx_status q3_size_and_alloc(gx_q3 *q)
                 q->smap.scale = (double) tslots / range;
         }
         {
-            gx_status st = q3_alloc_table(q, tslots, qual);
+            gx_status st = q3_alloc_results(q, qual);
             if (st != GX_OK) return st;
         }
     }
@@ -6047,6 +6354,31 @@ static void q3_launch_probe(hipStream_t s,
     });
 }
 
+/* The same stage over the rank form: the key's rank in rv indexes the dense
+ * agg array; compiled per visimap x LEFT OUTER */
+static void q3_launch_probe_rank(hipStream_t s,
+                                 const gx_col &lk, const gx_col &lp,
+                                 const gx_col &ld, const gx_col &ls,
+                                 const uint8_t *lvm, int32_t fop, int32_t flit,
+                                 gx_rankview rv, gx_aggslot *dagg,
+                                 unsigned long long *dhits, bool outer,
+                                 unsigned long long *ukey, double *urev,
+                                 unsigned long long *ucnt_u, uint64_t umask)
+{
+    by_flag(lvm != nullptr, [&](auto vm) {
+        by_flag(outer, [&](auto ou) {
+            hipLaunchKernelGGL((k_li_probe_agg_t<uint32_t, decltype(vm)::value,
+                                                 decltype(ou)::value, true>),
+                               dim3(GRID), dim3(TPB), 0, s,
+                               lk.dstream, lk.m, lp.dstream, lp.m,
+                               ld.dstream, ld.m, ls.dstream, ls.m, lvm,
+                               fop, flit, (const uint32_t *) nullptr, dagg,
+                               gx_slotmap{}, dhits,
+                               ukey, urev, ucnt_u, umask, rv);
+        });
+    });
+}
+
 /* Stage 4: one block per fixed tile of the table, block-ordered extract */
 static gx_status q3_launch_extract(gx_ctx *ctx, hipStream_t s, int key_width,
                                    const void *tkey, const gx_attrpair *tattr,
@@ -6095,6 +6427,14 @@ extern "C" gx_status gx_q3_dim_mode(gx_q3 *q, int *mode)
     return GX_OK;
 }
 
+extern "C" gx_status gx_q3_table_mode(gx_q3 *q, int *mode)
+{
+    if (!q || !mode) return GX_ERR_INVALID;
+    if (!q->ran) return GX_ERR_STATE;
+    *mode = q->table_mode;
+    return GX_OK;
+}
+
 /* the columns and effective visibility masks one Q3 run reads (extra-qual
  * masks fold the visimap in) */
 struct q3_runcols {
@@ -6111,6 +6451,11 @@ static gx_status q3_orders_local(gx_q3 *q, const q3_runcols &C, bool use_bitmap)
     hipStream_t s = ctx->stream;
     const gx_q3_desc &D = q->desc;
     const gx_col &ok = C.ok, &oc = C.oc, &od = C.od, &op = C.op;
+    if (q->tkey == nullptr)     /* first hash-form run of this q */
+    {
+        gx_status st = q3_alloc_hash(q, q->hash_tslots);
+        if (st != GX_OK) return st;
+    }
     uint64_t tslots = q->tmask + 1;
     /* keys only: agg/attr slots are initialised at claim (gx_aggslot) */
     HIP_CHK(ctx, hipMemsetAsync(q->tkey, 0, tslots * q->key_width, s));
@@ -6145,6 +6490,85 @@ static gx_status q3_orders_local(gx_q3 *q, const q3_runcols &C, bool use_bitmap)
             by_width(q->cset_width, (const void *) q->cset, [&](auto *cs) {
                 launch_build(tk, cs, std::false_type{});
             });
+    });
+    return GX_OK;
+}
+
+static inline gx_rankview q3_rankview(const gx_q3 *q)
+{
+    return {q->rent, q->rank_kmin, q->rank_range, (uint64_t) q->local_qual};
+}
+
+/* Stage 2, single segment, rank form: mark the qualifying keys' bits and the
+ * qualifying rows, turn the bit words into ranks (prefix popcounts), then
+ * store each qualifying row's key and attrs at its key's rank */
+static gx_status q3_orders_rank(gx_q3 *q, const q3_runcols &C, bool use_bitmap)
+{
+    gx_ctx *ctx = q->ctx;
+    hipStream_t s = ctx->stream;
+    const gx_q3_desc &D = q->desc;
+    const gx_col &ok = C.ok, &oc = C.oc, &od = C.od, &op = C.op;
+    if (q->dagg == nullptr)     /* first rank-form run of this q */
+    {
+        gx_status st = q3_alloc_rank(q);
+        if (st != GX_OK) return st;
+    }
+    uint64_t nwords = (q->rank_range + 63) / 64;
+    uint64_t nblk = (nwords + GX_RANK_SCAN_WORDS - 1) / GX_RANK_SCAN_WORDS;
+    if (nblk > 0x7FFFFFFFULL)
+    {
+        set_err(ctx, "rank table too large for the scan grid%s", "");
+        return GX_ERR_INVALID;
+    }
+    /* the entries (their bit words), and the dense keys so that extract emits no slot past
+     * this run's distinct qualifying keys; dattr/dagg are initialised by the
+     * fill kernel where a key lands (gx_aggslot) */
+    HIP_CHK(ctx, hipMemsetAsync(q->rent, 0, nwords * sizeof(ulonglong2), s));
+    HIP_CHK(ctx, hipMemsetAsync(q->dkey, 0,
+                                (uint64_t) q->local_qual * q->rank_kw, s));
+    if (D.fact_join == 1)
+    {
+        HIP_CHK(ctx, hipMemsetAsync(q->ukey, 0, (q->umask + 1) * 8, s));
+        HIP_CHK(ctx, hipMemsetAsync(q->urev, 0, (q->umask + 1) * 8, s));
+        HIP_CHK(ctx, hipMemsetAsync(q->ucnt_u, 0, (q->umask + 1) * 8, s));
+    }
+    gx_dimbits dbm = {q->dbits, q->dim_kmin, q->dim_range};
+    const gx_rankview rv = q3_rankview(q);
+    auto launch_mark = [&](auto *cs, auto bmode) {
+        by_flag(C.ovm != nullptr, [&](auto vm) {
+            by_flag(D.dim_join != 0, [&](auto anti) {
+                hipLaunchKernelGGL((k_orders_mark<std::decay_t<decltype(*cs)>,
+                                                  decltype(vm)::value,
+                                                  decltype(anti)::value,
+                                                  decltype(bmode)::value>),
+                                   dim3(ORDERS_GRID), dim3(TPB), 0, s,
+                                   ok.dstream, ok.m, oc.dstream, oc.m,
+                                   od.dstream, od.m, C.ovm, D.mid_filter.op,
+                                   (int32_t) D.mid_filter.literal, cs, q->cmask,
+                                   q->bloom, q->bwmask, dbm,
+                                   q->rent, q->rank_kmin, q->rank_range,
+                                   q->rowmask);
+            });
+        });
+    };
+    if (use_bitmap)     /* no key set: one set-width instantiation */
+        launch_mark((const unsigned int *) nullptr, std::true_type{});
+    else
+        by_width(q->cset_width, (const void *) q->cset, [&](auto *cs) {
+            launch_mark(cs, std::false_type{});
+        });
+    hipLaunchKernelGGL(k_rank_blocksum, dim3((unsigned) nblk), dim3(TPB), 0, s,
+                       q->rent, nwords, q->rblk);
+    hipLaunchKernelGGL(k_rank_topscan, dim3(1), dim3(TPB), 0, s,
+                       q->rblk, (int) nblk);
+    hipLaunchKernelGGL(k_rank_localscan, dim3((unsigned) nblk), dim3(TPB), 0, s,
+                       q->rent, nwords, q->rblk);
+    by_width(q->rank_kw, q->dkey, [&](auto *dk) {
+        hipLaunchKernelGGL(k_orders_fill<std::decay_t<decltype(*dk)>>,
+                           dim3(ORDERS_GRID), dim3(TPB), 0, s,
+                           ok.dstream, ok.m, od.dstream, od.m,
+                           op.dstream, op.m, q->rowmask, rv, dk,
+                           q->dattr, q->dagg);
     });
     return GX_OK;
 }
@@ -6401,6 +6825,12 @@ static gx_status q3_probe_agg(gx_q3 *q, const q3_runcols &C)
         HIP_CHK(ctx, hipStreamSynchronize(s));
         if (herr) { set_err(ctx, "numeric overflow in aggregation%s", ""); return GX_ERR_INVALID; }
     }
+    else if (q->table_mode == 1)
+        q3_launch_probe_rank(
+            s, lk, lp, ld, ls, C.lvm, D.fact_filter.op,
+            (int32_t) D.fact_filter.literal, q3_rankview(q),
+            q->dagg, dhits, D.fact_join == 1, q->ukey, q->urev, q->ucnt_u,
+            q->umask);
     else
         q3_launch_probe(
             s, lk, lp, ld, ls, C.lvm, D.fact_filter.op,
@@ -6423,10 +6853,17 @@ static gx_status q3_extract(gx_q3 *q)
     /* one block per fixed tile of the table; k_extract_u keeps its own grid */
     const int egrid = 32768;
     {
-        gx_status est = q3_launch_extract(ctx, s, q->key_width, q->tkey, q->tattr,
-                                          q->tagg, q->tmask + 1, q->numeric,
-                                          q->r_okey, q->r_odate, q->r_oprio,
-                                          q->r_rev, q->r_cnt, dcount);
+        /* rank form: the same kernel over the dense arrays, whose slots at
+         * or past this run's distinct keys hold key 0 (cleared per run) */
+        gx_status est = q->table_mode == 1
+            ? q3_launch_extract(ctx, s, q->rank_kw, q->dkey, q->dattr, q->dagg,
+                                (uint64_t) q->local_qual, q->numeric,
+                                q->r_okey, q->r_odate, q->r_oprio,
+                                q->r_rev, q->r_cnt, dcount)
+            : q3_launch_extract(ctx, s, q->key_width, q->tkey, q->tattr,
+                                q->tagg, q->tmask + 1, q->numeric,
+                                q->r_okey, q->r_odate, q->r_oprio,
+                                q->r_rev, q->r_cnt, dcount);
         if (est != GX_OK) return est;
     }
     if (q->desc.fact_join == 1)
@@ -6490,9 +6927,14 @@ extern "C" gx_status gx_q3_run(gx_q3 *q)
      * multi-GPU scale bench executes, testable on one GPU. */
     int64_t qual = 0;
     double ms_motion = 0.0;
+    /* table form of this run: rank for dense keys on the local path under
+     * the plain f64 probe over a flat fact key; hash for everything else */
+    q->table_mode = (q->rank_ok && local_path && !q->numeric &&
+                     C.lk.format == 0) ? 1 : 0;
     if (local_path)
     {
-        gx_status st = q3_orders_local(q, C, use_bitmap);
+        gx_status st = q->table_mode == 1 ? q3_orders_rank(q, C, use_bitmap)
+                                          : q3_orders_local(q, C, use_bitmap);
         if (st != GX_OK) return st;
         qual = q->rescap;
     }
@@ -8120,6 +8562,20 @@ extern "C" uint64_t gx_selftest_unmatched_bound(int64_t nrows, uint64_t lmin,
                                                 uint64_t lmax)
 {
     return q3_unmatched_bound(nrows, lmin, lmax);
+}
+
+/* sizing's rank-form rule (q3_rank_eligible) on caller-supplied key stats,
+ * and the keys one block of the prefix-popcount scan covers; callable without
+ * a GPU */
+extern "C" int gx_selftest_rank_eligible(int64_t qual, uint64_t kmin,
+                                         uint64_t kmax, int enabled)
+{
+    return q3_rank_eligible(qual, kmin, kmax, enabled) ? 1 : 0;
+}
+
+extern "C" int64_t gx_rank_scan_block_keys(void)
+{
+    return (int64_t) GX_RANK_SCAN_WORDS * 64;
 }
 
 /* bind's per-block routing of the fused RLE probe (parse_block_dir +

@@ -326,6 +326,15 @@ gx_status gx_q3_stats_get(const gx_q3 *q, gx_q3_stats *out);
  * GX_DIM_BITMAP is not 0; only the local (single-segment, no forced Motion)
  * path reads it.  GX_ERR_STATE before the first run. */
 gx_status gx_q3_dim_mode(gx_q3 *q, int *mode);
+/* Form of the join/agg table the LAST run used: 0 = open-addressing hash
+ * table, 1 = rank table (one bit per mid key of [min, max] plus per-word
+ * prefix popcounts; a key's rank indexes dense payload arrays).  Sizing allows
+ * the rank form when the qualifying mid keys are dense (max - min + 1 <= 64 *
+ * their row count, fewer than 2^32 rows) and GX_RANK_TABLE is not 0; a run
+ * takes it on the local (single-segment, no forced Motion) path with f64
+ * measures over a plain fact key, and the hash form otherwise.  GX_ERR_STATE
+ * before the first run. */
+gx_status gx_q3_table_mode(gx_q3 *q, int *mode);
 /* groups of THIS segment, sorted by l_orderkey asc; caller frees with gx_free */
 gx_status gx_q3_result(gx_q3 *q, gx_q3_group **out, int64_t *ngroups);
 /* top-N of this segment's groups (Q3's ORDER BY revenue DESC, o_orderdate
@@ -656,6 +665,15 @@ int gx_selftest_topn_merge(const int64_t *cidx, const int64_t *okey,
  * without wrap-around. */
 uint64_t gx_selftest_unmatched_bound(int64_t nrows, uint64_t lmin,
                                      uint64_t lmax);
+/* Sizing's rule for the rank form of the join/agg table (gx_q3_table_mode)
+ * on caller-supplied stats: qual qualifying mid rows whose keys, as unsigned
+ * words, span [kmin, kmax]; enabled = GX_RANK_TABLE is not 0.  No GPU
+ * needed.  Returns 1 or 0. */
+int gx_selftest_rank_eligible(int64_t qual, uint64_t kmin, uint64_t kmax,
+                              int enabled);
+/* Keys covered by one block of the rank table's prefix-popcount scan (ranks
+ * of keys further apart cross a block boundary of that scan). */
+int64_t gx_rank_scan_block_keys(void);
 /* How bind routes each block of a format-1 stream of 8-byte datums for the
  * fused RLE fact-key probe; no GPU needed.  cls[b]: 0 = not fused (Orig,
  * DELTA, NULL bitmap, more than 4096 physical datums: one such block and
