@@ -116,6 +116,32 @@ class _GbDesc(ctypes.Structure):
                 ("max_groups", ctypes.c_int64)]
 
 
+GB_MAX_FACTORS, GB_MAX_FQUALS, GB_MAX_OPERANDS = 3, 4, 8
+FACTOR_COL, FACTOR_ONE_MINUS, FACTOR_ONE_PLUS = 0, 1, 2
+_FACTOR_FORMS = {"": FACTOR_COL, "1-": FACTOR_ONE_MINUS, "1+": FACTOR_ONE_PLUS}
+
+
+class _Factor(ctypes.Structure):
+    _fields_ = [("col", ctypes.c_int32), ("form", ctypes.c_int32)]
+
+
+class _Expr(ctypes.Structure):
+    _fields_ = [("nfactors", ctypes.c_int32), ("_pad", ctypes.c_int32),
+                ("f", _Factor * GB_MAX_FACTORS)]
+
+
+class _FQual(ctypes.Structure):
+    _fields_ = [("col", ctypes.c_int32), ("op", ctypes.c_int32),
+                ("literal", ctypes.c_double)]
+
+
+class _GbExt(ctypes.Structure):
+    _fields_ = [("nexprs", ctypes.c_int32), ("nfquals", ctypes.c_int32),
+                ("exprs", _Expr * GB_MAX_AGGS),
+                ("agg_expr", ctypes.c_int32 * GB_MAX_AGGS),
+                ("fquals", _FQual * GB_MAX_FQUALS)]
+
+
 class _GbResult(ctypes.Structure):
     _fields_ = [("ngroups", ctypes.c_int64),
                 ("nkeys", ctypes.c_int32), ("naggs", ctypes.c_int32),
@@ -315,6 +341,28 @@ def _load():
     lib.gx_groupby_desc_dist.argtypes = [ctypes.c_void_p, ctypes.POINTER(_GbDesc),
                                          ctypes.POINTER(_GbResult),
                                          ctypes.POINTER(_GbStats)]
+    lib.gx_groupby_expr.argtypes = [ctypes.c_void_p, ctypes.POINTER(_GbDesc),
+                                    ctypes.POINTER(_GbExt),
+                                    ctypes.POINTER(_GbResult),
+                                    ctypes.POINTER(_GbdStats)]
+    lib.gx_test_groupby_expr.argtypes = [ctypes.c_void_p,
+                                         ctypes.POINTER(_GbDesc),
+                                         ctypes.POINTER(_GbExt), ctypes.c_int,
+                                         ctypes.c_int,
+                                         ctypes.POINTER(_GbResult),
+                                         ctypes.POINTER(_GbdStats)]
+    lib.gx_groupby_expr_dist.argtypes = [ctypes.c_void_p, ctypes.POINTER(_GbDesc),
+                                         ctypes.POINTER(_GbExt),
+                                         ctypes.POINTER(_GbResult),
+                                         ctypes.POINTER(_GbStats)]
+    lib.gx_selftest_expr_eval.restype = ctypes.c_int
+    lib.gx_selftest_expr_eval.argtypes = [ctypes.POINTER(_Expr), ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_int64,
+                                          ctypes.c_int, ctypes.c_void_p,
+                                          ctypes.c_void_p]
+    lib.gx_selftest_fqual.restype = ctypes.c_int
+    lib.gx_selftest_fqual.argtypes = [ctypes.c_int, ctypes.c_double,
+                                      ctypes.c_double]
     lib.gx_gbd_wire_stride.restype = ctypes.c_int64
     lib.gx_gbd_wire_stride.argtypes = [ctypes.POINTER(_GbDesc)]
     lib.gx_test_gbd_partial.argtypes = [ctypes.c_void_p, ctypes.POINTER(_GbDesc),
@@ -465,6 +513,80 @@ def _gb_desc(table, keys, aggs, quals, max_groups):
         d.quals[i] = _Filter(col, _opcode(op), int(lit))
     d.max_groups = max_groups
     return d
+
+
+def _factor(f):
+    """one factor: a column index, or (form, col) with form '1-' / '1+' / ''
+    or a raw gx_factor_form code"""
+    if isinstance(f, (tuple, list)):
+        form, col = f
+        return _Factor(col, form if isinstance(form, int) else _FACTOR_FORMS[form])
+    return _Factor(f, FACTOR_COL)
+
+
+def _expr(factors):
+    """gx_expr from a list of factors; the count goes through unclipped so
+    that the library's own range check answers"""
+    e = _Expr()
+    e.nfactors = len(factors)
+    for i, f in enumerate(factors[:GB_MAX_FACTORS]):
+        e.f[i] = _factor(f)
+    return e
+
+
+def _gb_expr_desc(table, keys, aggs, quals, fquals, max_groups):
+    """(gx_gb_desc, gx_gb_ext, aggs as groupby_desc specs) from the
+    groupby_expr argument shapes: an aggregate whose col is a list of factors
+    becomes an expression aggregate (one gx_expr per distinct factor list)"""
+    ext = _GbExt()
+    plain, exprs = [], []
+    for j in range(GB_MAX_AGGS):
+        ext.agg_expr[j] = -1
+    for j, spec in enumerate(aggs):
+        if isinstance(spec[1], (list, tuple)):
+            fac = [tuple(f) if isinstance(f, (list, tuple)) else f for f in spec[1]]
+            if fac not in exprs:
+                exprs.append(fac)
+            if j < GB_MAX_AGGS:
+                ext.agg_expr[j] = exprs.index(fac)
+            # float8 values; COUNT(expr) stays the int64 count
+            plain.append((spec[0], -1, spec[0] not in ("count", AGG_COUNT)))
+        else:
+            plain.append(tuple(spec))
+    ext.nexprs = len(exprs)
+    for e, fac in enumerate(exprs[:GB_MAX_AGGS]):
+        ext.exprs[e] = _expr(fac)
+    ext.nfquals = len(fquals)
+    for q, (col, op, lit) in enumerate(fquals[:GB_MAX_FQUALS]):
+        ext.fquals[q] = _FQual(col, _opcode(op), float(lit))
+    return _gb_desc(table, keys, plain, quals, max_groups), ext, plain
+
+
+def selftest_expr_eval(factors, vals, isnull=None):
+    """The value of one expression over the rows of vals (n, ncols) float64
+    through the functions the scan kernel calls (host only, no GPU):
+    (values, nulls).  factors as in Context.groupby_expr."""
+    vals = np.ascontiguousarray(vals, np.float64)
+    n, ncols = vals.shape
+    nl = None
+    if isnull is not None:
+        nl = np.ascontiguousarray(isnull, np.uint8)
+        assert nl.shape == vals.shape
+    out, out_null = np.zeros(n, np.float64), np.zeros(n, np.uint8)
+    e = _expr(list(factors))
+    rc = lib().gx_selftest_expr_eval(ctypes.byref(e), vals.ctypes.data,
+                                     None if nl is None else nl.ctypes.data,
+                                     n, ncols, out.ctypes.data,
+                                     out_null.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"gx_selftest_expr_eval: bad arguments ({rc})")
+    return out, out_null.astype(np.bool_)
+
+
+def selftest_fqual(op, x, literal):
+    """`x op literal` under float8_cmp_internal as the scan kernel evaluates
+    a float8 qual (host only, no GPU): 1 pass, 0 fail, -1 for a bad op."""
+    return int(lib().gx_selftest_fqual(_opcode(op), float(x), float(literal)))
 
 
 def gbd_wire_stride(keys, aggs):
@@ -747,6 +869,66 @@ class Context:
         self._chk(self._lib.gx_groupby_desc_dist(
             self._h, ctypes.byref(d), ctypes.byref(res), ctypes.byref(st)))
         out = self._gb_result(res, aggs)
+        if stats:
+            return out, {f: getattr(st, f) for f, _ in st._fields_}
+        return out
+
+    def groupby_expr(self, table, keys, aggs, quals=(), fquals=(),
+                     max_groups=0, stats=False):
+        """groupby_desc with float8 expression aggregates and float8 quals
+        (gx_groupby_expr).  An aggregate's col may be a list of up to 3
+        factors, each a float8 column index or ('1-', col) / ('1+', col):
+        ("sum", [2, ("1-", 3), ("1+", 5)]) is SUM(c2 * (1 - c3) * (1 + c5));
+        those aggregates come back as float64 arrays (COUNT as int64).  fquals: AND-ed (col,
+        op, float) triples over float8 columns, compared in the reference's
+        float8 order (NaN above +inf, -0 = +0).  Everything else as
+        groupby_desc."""
+        return self._groupby_expr(table, keys, aggs, quals, fquals, max_groups,
+                                  stats, None)
+
+    def test_groupby_expr(self, table, keys, aggs, quals=(), fquals=(),
+                          max_groups=0, stats=False, grid=0, wide_rowid=False,
+                          ext=True):
+        """groupby_expr through the test seam (grid, wide_rowid as for
+        test_groupby_desc).  ext=None passes a NULL gx_gb_ext; a callable is
+        given the filled gx_gb_ext mirror to alter before the call (raw
+        counts, forms and indexes for the error paths)."""
+        return self._groupby_expr(table, keys, aggs, quals, fquals, max_groups,
+                                  stats, (grid, 1 if wide_rowid else 0), ext)
+
+    def _groupby_expr(self, table, keys, aggs, quals, fquals, max_groups, stats,
+                      seam, ext_arg=True):
+        d, ext, plain = _gb_expr_desc(table, list(keys), list(aggs), list(quals),
+                                      list(fquals), max_groups)
+        if callable(ext_arg):
+            ext_arg(ext)
+        pext = ctypes.byref(ext) if ext_arg is not None else None
+        res, st = _GbResult(), _GbdStats()
+        if seam is None:
+            rc = self._lib.gx_groupby_expr(self._h, ctypes.byref(d), pext,
+                                           ctypes.byref(res), ctypes.byref(st))
+        else:
+            rc = self._lib.gx_test_groupby_expr(
+                self._h, ctypes.byref(d), pext, seam[0], seam[1],
+                ctypes.byref(res), ctypes.byref(st))
+        self._chk(rc)
+        out = self._gb_result(res, plain)
+        if stats:
+            return out, {f: getattr(st, f) for f, _ in st._fields_}
+        return out
+
+    def groupby_expr_dist(self, table, keys, aggs, quals=(), fquals=(),
+                          max_groups=0, stats=False):
+        """Two-stage groupby_expr across all segments of this context
+        (gx_groupby_expr_dist): the groups THIS segment owns; with stats=True
+        returns (result, gx_gb_stats as a dict)."""
+        d, ext, plain = _gb_expr_desc(table, list(keys), list(aggs), list(quals),
+                                      list(fquals), max_groups)
+        res, st = _GbResult(), _GbStats()
+        self._chk(self._lib.gx_groupby_expr_dist(
+            self._h, ctypes.byref(d), ctypes.byref(ext), ctypes.byref(res),
+            ctypes.byref(st)))
+        out = self._gb_result(res, plain)
         if stats:
             return out, {f: getattr(st, f) for f, _ in st._fields_}
         return out

@@ -2889,6 +2889,65 @@ GX_HD uint64_t gbd_f64_unimage(uint64_t img)
     return (img >> 63) ? img ^ (1ULL << 63) : ~img;
 }
 
+/* ---- float8 expression aggregates and float8 quals (gx_gb_ext) ----
+ * Only the EXPR instantiations of k_groupby_desc receive gbd_xargs; the
+ * others take the empty gbd_noexpr and compile as before.  opnd[] are the
+ * DISTINCT float8 columns over all expressions and fquals (deduplicated at
+ * plan time); factors, fquals and expression NULL masks name them by index. */
+struct gbd_xargs {
+    gbd_col  opnd[GX_GB_MAX_OPERANDS];
+    uint64_t fqimg[GX_GB_MAX_FQUALS];    /* gbd_fq_image of the literal */
+    int32_t  fqop[GX_GB_MAX_FQUALS];
+    int32_t  fqopnd[GX_GB_MAX_FQUALS];
+    int32_t  fopnd[GX_GB_MAX_AGGS][GX_GB_MAX_FACTORS];
+    int32_t  fform[GX_GB_MAX_AGGS][GX_GB_MAX_FACTORS];
+    int32_t  nfactors[GX_GB_MAX_AGGS];
+    uint32_t emask[GX_GB_MAX_AGGS];      /* operands of expression e, as bits */
+    int32_t  aexpr[GX_GB_MAX_AGGS];      /* expression of aggregate j, or -1 */
+    int32_t  nopnd, nexprs, nfquals, _pad;
+};
+struct gbd_noexpr {};
+
+/* One IEEE operation each, rounded to nearest, never contracted: hipcc
+ * contracts by default and __dmul_rn and its kin are plain operators in its
+ * headers, so the pragma is the fence.  float8mul / float8mi / float8pl of
+ * float.c without the overflow / underflow ereport. */
+GX_HD double gbd_factor(double c, int form)
+{
+#pragma clang fp contract(off)
+    if (form == GX_FACTOR_ONE_MINUS) return 1.0 - c;
+    if (form == GX_FACTOR_ONE_PLUS) return 1.0 + c;
+    return c;
+}
+
+GX_HD double gbd_fmul(double x, double y)
+{
+#pragma clang fp contract(off)
+    return x * y;
+}
+
+/* Image of a float8 for the fqual comparison: gbd_f64_image after -0.0 is
+ * made +0.0, so that unsigned order and equality of two images are
+ * float8_cmp_internal's (every NaN equal and above +inf, -0 = +0). */
+GX_HD uint64_t gbd_fq_image(uint64_t bits)
+{
+    if (bits == 0x8000000000000000ULL) bits = 0;
+    return gbd_f64_image(bits);
+}
+
+GX_HD bool gbd_fqual_pass(int op, uint64_t xbits, uint64_t litimg)
+{
+    return gx_cmp<uint64_t>(op, gbd_fq_image(xbits), litimg);
+}
+
+/* A row's operand values, and its expression values: one vector VALUE of
+ * eight doubles each, not an array.  An array indexed by the plan's tables
+ * stayed in memory (80-144 bytes of scratch per lane, or 16 KiB of LDS,
+ * when first built that way); a vector element picked by a wave-uniform
+ * index is a register-indexed move. */
+typedef double gbd_d8 __attribute__((ext_vector_type(8)));
+static_assert(GX_GB_MAX_OPERANDS == 8 && GX_GB_MAX_AGGS == 8, "gbd_d8 holds either");
+
 /* Where a representative row's key columns come from: the input's column
  * streams (the scan), or wire rows (gx_gbd_wire_stride: the combine stage of
  * the two-stage plan, whose received buffer is as immutable as the input). */
@@ -3002,6 +3061,41 @@ __device__ __forceinline__ void d_gbd_merge_words(const gbd_args &a,
     }
 }
 
+/* row i's transition on the first word p of one column aggregate j */
+__device__ __forceinline__ void gbd_accum_col(const gbd_args &a, int j, int64_t i,
+                                              unsigned long long *p)
+{
+    const gbd_col &c = a.agg[j];
+    const int op = a.aop[j];
+    if (op == GBD_COUNT_STAR) { atomicAdd(p, 1ULL); return; }
+    if (gbd_isnull(c, i)) return;                    /* strict transitions */
+    if (op == GBD_COUNT) { atomicAdd(p, 1ULL); return; }
+    switch (op)
+    {
+        case GBD_SUM_INT:
+            atomicAdd(p, (unsigned long long) gbd_load(c, i));
+            break;
+        case GBD_SUM_F64:
+            atomicAdd((double *) p, gx_col_get<double>(c.s, c.m, i));
+            break;
+        case GBD_MAX_INT:
+            atomicMax(p, (unsigned long long) gbd_load(c, i) ^ (1ULL << 63));
+            break;
+        case GBD_MIN_INT:
+            atomicMax(p, ~((unsigned long long) gbd_load(c, i) ^ (1ULL << 63)));
+            break;
+        case GBD_MAX_F64:
+            atomicMax(p, (unsigned long long) gbd_f64_image(
+                             gx_col_get<uint64_t>(c.s, c.m, i)));
+            break;
+        default:
+            atomicMax(p, (unsigned long long) ~gbd_f64_image(
+                             gx_col_get<uint64_t>(c.s, c.m, i)));
+            break;
+    }
+    atomicAdd(p + 1, 1ULL);
+}
+
 /* row i's transitions on the accumulator words w of its group; w is an LDS
  * or a global pointer at the two call sites, so each gets its own atomics */
 __device__ __forceinline__ void gbd_accum(const gbd_args &a, int64_t i,
@@ -3011,44 +3105,44 @@ __device__ __forceinline__ void gbd_accum(const gbd_args &a, int64_t i,
     for (int j = 0; j < GX_GB_MAX_AGGS; j++)
     {
         if (j >= a.naggs) continue;
-        const gbd_col &c = a.agg[j];
-        const int op = a.aop[j];
+        gbd_accum_col(a, j, i, w + a.aword[j]);
+    }
+}
+
+/* the same with expression aggregates: aggregate j with aexpr[j] >= 0 takes
+ * its float8 input from the row's expression registers ev (bit e of enull:
+ * expression e is NULL in this row), every other one from its column */
+__device__ __forceinline__ void gbd_accum_x(const gbd_args &a, const gbd_xargs &x,
+                                            int64_t i, unsigned long long *w,
+                                            const gbd_d8 &ev, unsigned enull)
+{
+#pragma unroll
+    for (int j = 0; j < GX_GB_MAX_AGGS; j++)
+    {
+        if (j >= a.naggs) continue;
         unsigned long long *p = w + a.aword[j];
-        if (op == GBD_COUNT_STAR) { atomicAdd(p, 1ULL); continue; }
-        if (gbd_isnull(c, i)) continue;              /* strict transitions */
+        const int e = x.aexpr[j];
+        if (e < 0) { gbd_accum_col(a, j, i, p); continue; }
+        if ((enull >> e) & 1u) continue;             /* strict transitions */
+        const int op = a.aop[j];
         if (op == GBD_COUNT) { atomicAdd(p, 1ULL); continue; }
-        switch (op)
-        {
-            case GBD_SUM_INT:
-                atomicAdd(p, (unsigned long long) gbd_load(c, i));
-                break;
-            case GBD_SUM_F64:
-                atomicAdd((double *) p, gx_col_get<double>(c.s, c.m, i));
-                break;
-            case GBD_MAX_INT:
-                atomicMax(p, (unsigned long long) gbd_load(c, i) ^ (1ULL << 63));
-                break;
-            case GBD_MIN_INT:
-                atomicMax(p, ~((unsigned long long) gbd_load(c, i) ^ (1ULL << 63)));
-                break;
-            case GBD_MAX_F64:
-                atomicMax(p, (unsigned long long) gbd_f64_image(
-                                 gx_col_get<uint64_t>(c.s, c.m, i)));
-                break;
-            default:
-                atomicMax(p, (unsigned long long) ~gbd_f64_image(
-                                 gx_col_get<uint64_t>(c.s, c.m, i)));
-                break;
-        }
+        const double v = ev[e];
+        const uint64_t bits = (uint64_t) __double_as_longlong(v);
+        if (op == GBD_SUM_F64) atomicAdd((double *) p, v);
+        else if (op == GBD_MAX_F64)
+            atomicMax(p, (unsigned long long) gbd_f64_image(bits));
+        else atomicMax(p, (unsigned long long) ~gbd_f64_image(bits));
         atomicAdd(p + 1, 1ULL);
     }
 }
 
 /* stats: [0] rows passing visimap + quals, [1] rows accumulated in LDS */
-template <typename ST, bool LDS>
+template <typename ST, bool LDS, bool EXPR>
 __global__ void __launch_bounds__(TPB)
-k_groupby_desc(const gbd_args a, ST *trow, unsigned long long *tacc,
-               uint64_t tmask, unsigned long long *stats, int *err)
+k_groupby_desc(const gbd_args a,
+               const std::conditional_t<EXPR, gbd_xargs, gbd_noexpr> x, ST *trow,
+               unsigned long long *tacc, uint64_t tmask,
+               unsigned long long *stats, int *err)
 {
     extern __shared__ unsigned long long gbd_smem[];
     __shared__ unsigned int s_seen, s_miss;
@@ -3074,6 +3168,22 @@ k_groupby_desc(const gbd_args a, ST *trow, unsigned long long *tacc,
         int64_t kv[GX_GB_MAX_KEYS];
         unsigned kn;
         const uint64_t h = gbd_row_keys(gbd_key_cols{}, a, i, kv, kn);
+        /* EXPR: every distinct operand column once per row, value and
+         * validity, in the same round trip */
+        gbd_d8 ov = 0.0, ev = 0.0;
+        unsigned onull = 0, enull = 0;
+        if constexpr (EXPR)
+        {
+#pragma unroll
+            for (int o = 0; o < GX_GB_MAX_OPERANDS; o++)
+            {
+                if (o < x.nopnd)
+                {
+                    onull |= (unsigned) gbd_isnull(x.opnd[o], i) << o;
+                    ov[o] = gx_col_get<double>(x.opnd[o].s, x.opnd[o].m, i);
+                }
+            }
+        }
         bool pass = true;
 #pragma unroll
         for (int q = 0; q < GX_MAX_EXTRA_QUALS; q++)
@@ -3081,8 +3191,37 @@ k_groupby_desc(const gbd_args a, ST *trow, unsigned long long *tacc,
                 pass = pass && !gbd_isnull(a.qual[q], i) &&   /* NULL fails */
                        gx_cmp<int64_t>(a.qop[q], gbd_load(a.qual[q], i),
                                        a.qlit[q]);
+        if constexpr (EXPR)
+        {
+#pragma unroll
+            for (int q = 0; q < GX_GB_MAX_FQUALS; q++)
+                if (q < x.nfquals)
+                    pass = pass && !((onull >> x.fqopnd[q]) & 1u) &&
+                           gbd_fqual_pass(x.fqop[q],
+                                          (uint64_t) __double_as_longlong(
+                                              ov[x.fqopnd[q]]),
+                                          x.fqimg[q]);
+        }
         if (!pass) continue;
         n_pass++;
+        if constexpr (EXPR)
+        {
+#pragma unroll
+            for (int e = 0; e < GX_GB_MAX_AGGS; e++)
+            {
+                if (e < x.nexprs)
+                {
+                    double v = gbd_factor(ov[x.fopnd[e][0]], x.fform[e][0]);
+#pragma unroll
+                    for (int f = 1; f < GX_GB_MAX_FACTORS; f++)
+                        if (f < x.nfactors[e])
+                            v = gbd_fmul(v, gbd_factor(ov[x.fopnd[e][f]],
+                                                       x.fform[e][f]));
+                    ev[e] = v;
+                    enull |= (unsigned) ((onull & x.emask[e]) != 0u) << e;
+                }
+            }
+        }
         bool done = false;
         if (LDS)
         {
@@ -3106,7 +3245,10 @@ k_groupby_desc(const gbd_args a, ST *trow, unsigned long long *tacc,
                 }
                 if (done)
                 {
-                    gbd_accum(a, i, lacc + (size_t) ls * a.awords);
+                    if constexpr (EXPR)
+                        gbd_accum_x(a, x, i, lacc + (size_t) ls * a.awords, ev, enull);
+                    else
+                        gbd_accum(a, i, lacc + (size_t) ls * a.awords);
                     n_lds++;
                 }
                 /* one pair of counter updates per wave and iteration */
@@ -3123,7 +3265,13 @@ k_groupby_desc(const gbd_args a, ST *trow, unsigned long long *tacc,
         {
             uint64_t slot = gbd_ginsert<ST>(gbd_key_cols{}, a, trow, tmask, h, kv, kn,
                                             i, err);
-            if (slot != ~0ULL) gbd_accum(a, i, tacc + slot * a.awords);
+            if (slot != ~0ULL)
+            {
+                if constexpr (EXPR)
+                    gbd_accum_x(a, x, i, tacc + slot * a.awords, ev, enull);
+                else
+                    gbd_accum(a, i, tacc + slot * a.awords);
+            }
         }
     }
     if (LDS)
@@ -7326,10 +7474,11 @@ extern "C" void gx_gb_result_free(gx_gb_result *r)
     memset(r, 0, sizeof *r);
 }
 
-static gx_status gbd_invalid(gx_ctx *ctx, const char *fmt, long a, long b = 0)
+static gx_status gbd_invalid(gx_ctx *ctx, const char *fmt, long a, long b = 0,
+                             long c = 0)
 {
     char buf[200];
-    snprintf(buf, sizeof buf, fmt, a, b);
+    snprintf(buf, sizeof buf, fmt, a, b, c);
     set_err(ctx, "groupby_desc: %s", buf);
     return GX_ERR_INVALID;
 }
@@ -7337,8 +7486,10 @@ static gx_status gbd_invalid(gx_ctx *ctx, const char *fmt, long a, long b = 0)
 /* flattened inputs of one call; a table column used in several roles is
  * materialized once */
 struct gbd_inputs {
-    devbuf flat[GX_GB_MAX_KEYS + GX_GB_MAX_AGGS + GX_MAX_EXTRA_QUALS];
-    devbuf val[GX_GB_MAX_KEYS + GX_GB_MAX_AGGS + GX_MAX_EXTRA_QUALS];
+    devbuf flat[GX_GB_MAX_KEYS + GX_GB_MAX_AGGS + GX_MAX_EXTRA_QUALS +
+                GX_GB_MAX_OPERANDS];
+    devbuf val[GX_GB_MAX_KEYS + GX_GB_MAX_AGGS + GX_MAX_EXTRA_QUALS +
+               GX_GB_MAX_OPERANDS];
     int nflat = 0;
     std::map<int, gbd_col> done;
 };
@@ -7364,11 +7515,97 @@ static bool gbd_int_width(int w) { return w == 1 || w == 2 || w == 4 || w == 8; 
  * counting their non-NULL inputs */
 static int gbd_fn_words(int fn) { return fn <= GX_AGG_COUNT ? 1 : 2; }
 
+/* the expression side of a planned call: on = the EXPR instantiations run
+ * (the ext names an expression or an fqual); opnd_col[o] = the table column
+ * of operand o */
+struct gbd_xplan {
+    gbd_xargs x{};
+    bool on = false;
+    int opnd_col[GX_GB_MAX_OPERANDS] = {};
+};
+
+/* index of table column c among the operands, appended when new; -1 when
+ * the table is full */
+static int gbd_operand(gbd_xplan &xp, int c)
+{
+    for (int o = 0; o < xp.x.nopnd; o++)
+        if (xp.opnd_col[o] == c) return o;
+    if (xp.x.nopnd == GX_GB_MAX_OPERANDS) return -1;
+    xp.opnd_col[xp.x.nopnd] = c;
+    return xp.x.nopnd++;
+}
+
+/* validate a gx_gb_ext against the table and fill the operand, factor and
+ * fqual tables; agg_expr is checked with the aggregates in gbd_plan */
+static gx_status gbd_plan_ext(gx_ctx *ctx, const gx_gb_ext *ext, const gx_table *t,
+                              gbd_xplan &xp)
+{
+    const int ncols = (int) t->cols.size();
+    if (ext->nexprs < 0 || ext->nexprs > GX_GB_MAX_AGGS)
+        return gbd_invalid(ctx, "nexprs %ld outside 0..%ld", ext->nexprs, GX_GB_MAX_AGGS);
+    if (ext->nfquals < 0 || ext->nfquals > GX_GB_MAX_FQUALS)
+        return gbd_invalid(ctx, "nfquals %ld outside 0..%ld", ext->nfquals, GX_GB_MAX_FQUALS);
+    gbd_xargs &x = xp.x;
+    x.nexprs = ext->nexprs;
+    x.nfquals = ext->nfquals;
+    for (int e = 0; e < ext->nexprs; e++)
+    {
+        const gx_expr &ex = ext->exprs[e];
+        if (ex.nfactors < 1 || ex.nfactors > GX_GB_MAX_FACTORS)
+            return gbd_invalid(ctx, "expr %ld: nfactors %ld outside 1..%ld", e,
+                               ex.nfactors, GX_GB_MAX_FACTORS);
+        x.nfactors[e] = ex.nfactors;
+        for (int f = 0; f < ex.nfactors; f++)
+        {
+            const int c = ex.f[f].col;
+            if (c < 0 || c >= ncols)
+                return gbd_invalid(ctx, "expr %ld factor %ld: column %ld out of range", e, f, c);
+            if (t->cols[c].m.width != 8)
+                return gbd_invalid(ctx, "expr %ld factor %ld: column width %ld is not 8",
+                                   e, f, t->cols[c].m.width);
+            if (ex.f[f].form < GX_FACTOR_COL || ex.f[f].form > GX_FACTOR_ONE_PLUS)
+                return gbd_invalid(ctx, "expr %ld factor %ld: form %ld outside 0..2", e, f,
+                                   ex.f[f].form);
+            const int o = gbd_operand(xp, c);
+            if (o < 0)
+                return gbd_invalid(ctx, "more than %ld distinct float8 operand columns",
+                                   GX_GB_MAX_OPERANDS);
+            x.fopnd[e][f] = o;
+            x.fform[e][f] = ex.f[f].form;
+            x.emask[e] |= 1u << o;
+        }
+    }
+    for (int q = 0; q < ext->nfquals; q++)
+    {
+        const gx_fqual &fq = ext->fquals[q];
+        if (fq.col < 0 || fq.col >= ncols)
+            return gbd_invalid(ctx, "fqual %ld: column %ld out of range", q, fq.col);
+        if (t->cols[fq.col].m.width != 8)
+            return gbd_invalid(ctx, "fqual %ld: column width %ld is not 8", q,
+                               t->cols[fq.col].m.width);
+        if (fq.op < 0 || fq.op > 5)
+            return gbd_invalid(ctx, "fqual %ld: op %ld outside 0..5", q, fq.op);
+        const int o = gbd_operand(xp, fq.col);
+        if (o < 0)
+            return gbd_invalid(ctx, "more than %ld distinct float8 operand columns",
+                               GX_GB_MAX_OPERANDS);
+        uint64_t bits;
+        memcpy(&bits, &fq.literal, 8);
+        x.fqopnd[q] = o;
+        x.fqop[q] = fq.op;
+        x.fqimg[q] = gbd_fq_image(bits);
+    }
+    xp.on = ext->nexprs > 0 || ext->nfquals > 0;
+    return GX_OK;
+}
+
 /* PLAN: validate the descriptor and fill everything of gbd_args that needs
  * no device memory.  t == nullptr (the combine stage over wire rows) checks
- * and reads nkeys, the aggregates' fn / is_f64 and max_groups only. */
+ * and reads nkeys, the aggregates' fn / is_f64 and max_groups only.  ext and
+ * xp (both or neither; a table is required) add the expression side. */
 static gx_status gbd_plan(gx_ctx *ctx, const gx_gb_desc *d, const gx_table *t,
-                          gbd_args &a)
+                          gbd_args &a, const gx_gb_ext *ext = nullptr,
+                          gbd_xplan *xp = nullptr)
 {
     const int ncols = t ? (int) t->cols.size() : 0;
     if (d->nkeys < 0 || d->nkeys > GX_GB_MAX_KEYS)
@@ -7380,6 +7617,11 @@ static gx_status gbd_plan(gx_ctx *ctx, const gx_gb_desc *d, const gx_table *t,
     if (d->max_groups < 0)
         return gbd_invalid(ctx, "max_groups %ld is negative", (long) d->max_groups);
 
+    if (ext)
+    {
+        gx_status st = gbd_plan_ext(ctx, ext, t, *xp);
+        if (st != GX_OK) return st;
+    }
     a = gbd_args{};
     a.nkeys = d->nkeys; a.naggs = d->naggs; a.nquals = t ? d->nquals : 0;
     a.nrows = t ? t->nrows : 0;
@@ -7397,18 +7639,30 @@ static gx_status gbd_plan(gx_ctx *ctx, const gx_gb_desc *d, const gx_table *t,
     int words = 0;
     for (int j = 0; j < d->naggs; j++)
     {
-        const gx_agg &g = d->aggs[j];
+        gx_agg g = d->aggs[j];
         if (g.fn < GX_AGG_COUNT_STAR || g.fn > GX_AGG_MAX)
             return gbd_invalid(ctx, "aggregate %ld: unknown fn %ld", j, g.fn);
         a.aword[j] = words;
+        const int ae = ext ? ext->agg_expr[j] : -1;
+        if (ext)
+        {
+            if (ae < -1 || ae >= ext->nexprs)
+                return gbd_invalid(ctx, "aggregate %ld: agg_expr %ld outside -1..%ld", j,
+                                   ae, ext->nexprs - 1);
+            if (ae >= 0 && g.fn == GX_AGG_COUNT_STAR)
+                return gbd_invalid(ctx, "aggregate %ld: agg_expr %ld on COUNT(*)", j, ae);
+            xp->x.aexpr[j] = ae;
+        }
+        /* an expression aggregate is "float8 of that fn": col is not read */
+        if (ae >= 0) g.is_f64 = 1;
         if (g.fn == GX_AGG_COUNT_STAR)
         {
             a.aop[j] = GBD_COUNT_STAR;
             a.wop[words++] = GBD_W_ADD;
             continue;
         }
-        int w = 0;
-        if (t)
+        int w = ae >= 0 ? 8 : 0;
+        if (t && ae < 0)
         {
             if (g.col < 0 || g.col >= ncols)
                 return gbd_invalid(ctx, "aggregate %ld: column %ld out of range", j, g.col);
@@ -7478,18 +7732,32 @@ extern "C" int64_t gx_gbd_wire_stride(const gx_gb_desc *d)
 
 /* BIND: flatten every column the plan reads */
 static gx_status gbd_bind(gx_ctx *ctx, const gx_gb_desc *d, gbd_inputs &in,
-                          gbd_args &a)
+                          gbd_args &a, gbd_xplan *xp)
 {
     const gx_table *t = d->t;
+    const bool ex = xp && xp->on;
     gx_status st;
     for (int k = 0; k < d->nkeys; k++)
         if ((st = gbd_bind_col(ctx, t, d->key_cols[k], in, &a.key[k])) != GX_OK) return st;
     for (int j = 0; j < d->naggs; j++)
-        if (d->aggs[j].fn != GX_AGG_COUNT_STAR &&
+        if (d->aggs[j].fn != GX_AGG_COUNT_STAR && !(ex && xp->x.aexpr[j] >= 0) &&
             (st = gbd_bind_col(ctx, t, d->aggs[j].col, in, &a.agg[j])) != GX_OK) return st;
     for (int q = 0; q < d->nquals; q++)
         if ((st = gbd_bind_col(ctx, t, d->quals[q].col, in, &a.qual[q])) != GX_OK) return st;
+    for (int o = 0; ex && o < xp->x.nopnd; o++)
+        if ((st = gbd_bind_col(ctx, t, xp->opnd_col[o], in, &xp->x.opnd[o])) != GX_OK) return st;
     return GX_OK;
+}
+
+/* bytes gbd_bind materialises for the operand columns (format 1: a flat
+ * copy and validity bytes), for the budget check before anything is bound */
+static uint64_t gbd_operand_flat_bytes(const gx_table *t, const gbd_xplan *xp)
+{
+    uint64_t b = 0;
+    for (int o = 0; xp && xp->on && o < xp->x.nopnd; o++)
+        if (t->cols[xp->opnd_col[o]].format != 0)
+            b += GX_AOCS_DATUM_OFF + (uint64_t) std::max<int64_t>(t->nrows, 1) * 9;
+    return b;
 }
 
 /* one aggregation table on the device and its compacted groups: the scan's
@@ -7565,7 +7833,7 @@ static void gbd_extract(gx_ctx *ctx, const gbd_args &a, const SRC &src, gbd_tabl
 static gx_status gbd_scan_stage(gx_ctx *ctx, const gx_gb_desc *d, gbd_args &a,
                                 gbd_inputs &in, gbd_table &T, int grid, bool wide,
                                 bool lds, uint64_t extra, hipEvent_t e0,
-                                hipEvent_t e1)
+                                hipEvent_t e1, gbd_xplan *xp = nullptr)
 {
     if (grid < 1) return gbd_invalid(ctx, "grid %ld", grid);
     /* sizing: the table holds up to `bound` groups */
@@ -7574,20 +7842,27 @@ static gx_status gbd_scan_stage(gx_ctx *ctx, const gx_gb_desc *d, gbd_args &a,
         1, d->max_groups > 0 ? std::min<int64_t>(d->max_groups, n) : n);
     if (!wide && n >= (int64_t) UINT32_MAX)
         return gbd_invalid(ctx, "%ld rows need the 8-byte slot word", (long) n);
-    gx_status st = gbd_table_budget(ctx, a, bound, wide, extra, "groupby_desc table");
+    gx_status st = gbd_table_budget(ctx, a, bound, wide,
+                                    extra + gbd_operand_flat_bytes(d->t, xp),
+                                    "groupby_desc table");
     if (st != GX_OK) return st;
-    if ((st = gbd_bind(ctx, d, in, a)) != GX_OK) return st;
+    if ((st = gbd_bind(ctx, d, in, a, xp)) != GX_OK) return st;
     if ((st = gbd_table_alloc(ctx, T, a, bound, wide)) != GX_OK) return st;
     hipStream_t s = ctx->stream;
     const size_t lds_bytes = lds ? (size_t) a.lds_slots * ((size_t) a.awords * 8 + T.sw) : 0;
     if (e0) HIP_CHK(ctx, hipEventRecord(e0, s));
     by_width((int) T.sw, T.trow.p, [&](auto *rows) {
         by_flag(lds, [&](auto use_lds) {
-            hipLaunchKernelGGL((k_groupby_desc<std::decay_t<decltype(*rows)>,
-                                               decltype(use_lds)::value>),
-                               dim3(grid), dim3(TPB), lds_bytes, s, a, rows,
-                               T.tacc.as<unsigned long long>(), T.tslots - 1,
-                               T.stat(), T.err());
+            by_flag(xp && xp->on, [&](auto use_expr) {
+                constexpr bool EX = decltype(use_expr)::value;
+                std::conditional_t<EX, gbd_xargs, gbd_noexpr> x{};
+                if constexpr (EX) x = xp->x;
+                hipLaunchKernelGGL((k_groupby_desc<std::decay_t<decltype(*rows)>,
+                                                   decltype(use_lds)::value, EX>),
+                                   dim3(grid), dim3(TPB), lds_bytes, s, a, x, rows,
+                                   T.tacc.as<unsigned long long>(), T.tslots - 1,
+                                   T.stat(), T.err());
+            });
         });
     });
     if (e1) HIP_CHK(ctx, hipEventRecord(e1, s));
@@ -7707,18 +7982,20 @@ static gx_status gbd_check_call(gx_ctx *ctx, const gx_gb_desc *d, gx_gb_result *
  * from the caller (production: GRID, nrows >= 2^32 - 1), lds from GX_GB_LDS,
  * so the public call and the test entry run the same launches. */
 static gx_status gbd_run(gx_ctx *ctx, const gx_gb_desc *d, int grid, bool wide,
-                         bool lds, gx_gb_result *out, gx_gbd_stats *stats)
+                         bool lds, gx_gb_result *out, gx_gbd_stats *stats,
+                         const gx_gb_ext *ext = nullptr)
 {
     gx_status st = gbd_check_call(ctx, d, out);
     if (stats) memset(stats, 0, sizeof *stats);
     if (st != GX_OK) return st;
     gbd_args a;
-    if ((st = gbd_plan(ctx, d, d->t, a)) != GX_OK) return st;
+    gbd_xplan xp;
+    if ((st = gbd_plan(ctx, d, d->t, a, ext, &xp)) != GX_OK) return st;
     gbd_inputs in;
     gbd_table T;
     evholder e0, e1;
     HIP_CHK(ctx, e0.create()); HIP_CHK(ctx, e1.create());
-    st = gbd_scan_stage(ctx, d, a, in, T, grid, wide, lds, 0, e0, e1);
+    st = gbd_scan_stage(ctx, d, a, in, T, grid, wide, lds, 0, e0, e1, &xp);
     if (st != GX_OK) return st;
     const int64_t n = d->t->nrows;
     unsigned long long hm[4] = {0, 0, 0, 0};
@@ -7755,6 +8032,25 @@ extern "C" gx_status gx_test_groupby_desc(gx_ctx *ctx, const gx_gb_desc *d,
     bool wide = wide_rowid != 0 ||
                 (d && d->t && d->t->nrows >= (int64_t) UINT32_MAX);
     return gbd_run(ctx, d, grid == 0 ? GRID : grid, wide, gbd_env_lds(), out, stats);
+}
+
+extern "C" gx_status gx_groupby_expr(gx_ctx *ctx, const gx_gb_desc *d,
+                                     const gx_gb_ext *ext, gx_gb_result *out,
+                                     gx_gbd_stats *stats)
+{
+    bool wide = d && d->t && d->t->nrows >= (int64_t) UINT32_MAX;
+    return gbd_run(ctx, d, GRID, wide, gbd_env_lds(), out, stats, ext);
+}
+
+extern "C" gx_status gx_test_groupby_expr(gx_ctx *ctx, const gx_gb_desc *d,
+                                          const gx_gb_ext *ext, int grid,
+                                          int wide_rowid, gx_gb_result *out,
+                                          gx_gbd_stats *stats)
+{
+    bool wide = wide_rowid != 0 ||
+                (d && d->t && d->t->nrows >= (int64_t) UINT32_MAX);
+    return gbd_run(ctx, d, grid == 0 ? GRID : grid, wide, gbd_env_lds(), out, stats,
+                   ext);
 }
 
 /* ---- two-stage descriptor GROUP BY: host side ----
@@ -7843,8 +8139,9 @@ static gx_status gbd_partial_failed(gx_ctx *ctx)
     return GX_ERR_INVALID;
 }
 
-extern "C" gx_status gx_groupby_desc_dist(gx_ctx *ctx, const gx_gb_desc *d,
-                                          gx_gb_result *out, gx_gb_stats *stats)
+static gx_status gbd_run_dist(gx_ctx *ctx, const gx_gb_desc *d,
+                              const gx_gb_ext *ext, gx_gb_result *out,
+                              gx_gb_stats *stats)
 {
     gx_status st = gbd_check_call(ctx, d, out);
     if (stats) memset(stats, 0, sizeof *stats);
@@ -7859,7 +8156,7 @@ extern "C" gx_status gx_groupby_desc_dist(gx_ctx *ctx, const gx_gb_desc *d,
     if (ctx->nsegs == 1 && env_int("GX_FORCE_MOTION", 0) == 0)
     {
         gx_gbd_stats one{};
-        st = gbd_run(ctx, d, GRID, wide, gbd_env_lds(), out, &one);
+        st = gbd_run(ctx, d, GRID, wide, gbd_env_lds(), out, &one, ext);
         if (st != GX_OK) return st;
         S.ms_partial = one.ms_kernel;
         S.partial_groups = S.final_groups = out->ngroups;
@@ -7867,7 +8164,8 @@ extern "C" gx_status gx_groupby_desc_dist(gx_ctx *ctx, const gx_gb_desc *d,
         return GX_OK;
     }
     gbd_args a;
-    if ((st = gbd_plan(ctx, d, t, a)) != GX_OK) return st;
+    gbd_xplan xp;
+    if ((st = gbd_plan(ctx, d, t, a, ext, &xp)) != GX_OK) return st;
     if (!ctx->comm)
     { set_err(ctx, "nsegs>1 but gx_comm_init not called%s", ""); return GX_ERR_STATE; }
     const int n = ctx->nsegs;
@@ -7890,7 +8188,7 @@ extern "C" gx_status gx_groupby_desc_dist(gx_ctx *ctx, const gx_gb_desc *d,
     const uint64_t side = (uint64_t) std::max<int64_t>(t->nrows, 1) * 2 +
                           (uint64_t) n * (n + 2) * 8;
     st = gbd_scan_stage(ctx, d, a, in, T, GRID, wide, gbd_env_lds(), side, ev[0],
-                        nullptr);
+                        nullptr, &xp);
     if (st != GX_OK) return st;
     HIP_CHK(ctx, hipEventRecord(ev[1], s));
 
@@ -7958,6 +8256,19 @@ extern "C" gx_status gx_groupby_desc_dist(gx_ctx *ctx, const gx_gb_desc *d,
     S.final_groups = out->ngroups;
     if (stats) *stats = S;
     return GX_OK;
+}
+
+extern "C" gx_status gx_groupby_desc_dist(gx_ctx *ctx, const gx_gb_desc *d,
+                                          gx_gb_result *out, gx_gb_stats *stats)
+{
+    return gbd_run_dist(ctx, d, nullptr, out, stats);
+}
+
+extern "C" gx_status gx_groupby_expr_dist(gx_ctx *ctx, const gx_gb_desc *d,
+                                          const gx_gb_ext *ext, gx_gb_result *out,
+                                          gx_gb_stats *stats)
+{
+    return gbd_run_dist(ctx, d, ext, out, stats);
 }
 
 /* Test ABI: partial agg + partition kernels on one GPU for a given nsegs,
@@ -8075,11 +8386,49 @@ extern "C" int gx_selftest_gbd_route(const int64_t *keys, const uint8_t *key_nul
     return 0;
 }
 
+/* host restatements of the expression value and the float8 qual through
+ * gbd_factor / gbd_fmul / gbd_fqual_pass, which the scan kernel calls */
+extern "C" int gx_selftest_expr_eval(const gx_expr *ex, const double *vals,
+                                     const uint8_t *isnull, int64_t n, int ncols,
+                                     double *out, uint8_t *out_null)
+{
+    if (!ex || n < 0 || ncols < 1 || (n > 0 && (!vals || !out || !out_null)) ||
+        ex->nfactors < 1 || ex->nfactors > GX_GB_MAX_FACTORS)
+        return 1;
+    for (int f = 0; f < ex->nfactors; f++)
+        if (ex->f[f].col < 0 || ex->f[f].col >= ncols ||
+            ex->f[f].form < GX_FACTOR_COL || ex->f[f].form > GX_FACTOR_ONE_PLUS)
+            return 1;
+    for (int64_t i = 0; i < n; i++)
+    {
+        const double *row = vals + i * ncols;
+        bool isn = false;
+        double v = gbd_factor(row[ex->f[0].col], ex->f[0].form);
+        for (int f = 1; f < ex->nfactors; f++)
+            v = gbd_fmul(v, gbd_factor(row[ex->f[f].col], ex->f[f].form));
+        for (int f = 0; f < ex->nfactors; f++)
+            isn = isn || (isnull && isnull[i * ncols + ex->f[f].col]);
+        out[i] = isn ? 0.0 : v;
+        out_null[i] = (uint8_t) isn;
+    }
+    return 0;
+}
+
+extern "C" int gx_selftest_fqual(int op, double x, double literal)
+{
+    if (op < 0 || op > 5) return -1;
+    uint64_t xb, lb;
+    memcpy(&xb, &x, 8);
+    memcpy(&lb, &literal, 8);
+    return gbd_fqual_pass(op, xb, gbd_fq_image(lb)) ? 1 : 0;
+}
+
 /* ABI self-description: struct sizes for cross-checking foreign-language
  * mirrors (ctypes tests; the PG extension's abi-check compiles against the
  * real header instead).  kind: 0 stats, 1 group, 2 kv_group, 3 desc,
  * 4 coldesc, 5 filter, 6 gb_stats, 7 test_tbl_layout, 8 gb_desc,
- * 9 gb_result, 10 agg, 11 gbd_stats. */
+ * 9 gb_result, 10 agg, 11 gbd_stats, 13 gb_ext, 14 expr, 15 fqual; 12 is
+ * unassigned and stays -1. */
 extern "C" int64_t gx_abi_sizeof(int kind)
 {
     switch (kind)
@@ -8096,6 +8445,9 @@ extern "C" int64_t gx_abi_sizeof(int kind)
         case 9: return (int64_t) sizeof(gx_gb_result);
         case 10: return (int64_t) sizeof(gx_agg);
         case 11: return (int64_t) sizeof(gx_gbd_stats);
+        case 13: return (int64_t) sizeof(gx_gb_ext);
+        case 14: return (int64_t) sizeof(gx_expr);
+        case 15: return (int64_t) sizeof(gx_fqual);
         default: return -1;
     }
 }

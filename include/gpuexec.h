@@ -350,8 +350,9 @@ void gx_free(void *p);
 
 /* ABI self-description for foreign mirrors (0 stats, 1 q3_group,
  * 2 kv_group, 3 q3_desc, 4 coldesc, 5 filter, 6 gb_stats,
- * 7 test_tbl_layout, 8 gb_desc, 9 gb_result, 10 agg, 11 gbd_stats);
- * -1 for unknown kinds */
+ * 7 test_tbl_layout, 8 gb_desc, 9 gb_result, 10 agg, 11 gbd_stats,
+ * 13 gb_ext, 14 expr, 15 fqual); -1 for unknown kinds.  Kind 12 is left
+ * unassigned on purpose and stays -1: the suite pins it as an unknown kind. */
 int64_t gx_abi_sizeof(int kind);
 
 /* ---- standalone hash GROUP BY (nodeAgg.c:2288 hash strategy over one key;
@@ -515,6 +516,64 @@ gx_status gx_groupby_desc_dist(gx_ctx *, const gx_gb_desc *, gx_gb_result *out,
                                gx_gb_stats *stats /* may be NULL */);
 int64_t   gx_gbd_wire_stride(const gx_gb_desc *);
 
+/* ---- descriptor GROUP BY: float8 expression aggregates and float8 quals.
+ * What TPC-H Q1 (SUM(price * (1 - disc) * (1 + tax))) and Q6 (SUM(price *
+ * disc) WHERE disc BETWEEN .. AND qty < ..) need on top of gx_gb_desc.  The
+ * descriptor and gx_agg keep their sizes; the new items travel in gx_gb_ext
+ * beside the descriptor.  Tagged structs, no expression trees: an expression
+ * is a product of 1..GX_GB_MAX_FACTORS factors, a factor one float8 column c
+ * as c (GX_FACTOR_COL), 1.0 - c (GX_FACTOR_ONE_MINUS) or 1.0 + c
+ * (GX_FACTOR_ONE_PLUS).
+ *
+ * ext == NULL, or an ext with nexprs == nfquals == 0 and every agg_expr of
+ *   the descriptor's aggregates -1, is exactly gx_groupby_desc /
+ *   gx_groupby_desc_dist: same kernels, result bytes and error texts.
+ * Factors: the column must be 8 bytes wide and is read as float8; format 0
+ *   and format 1 (NULL bitmaps, RLE) both bind.
+ * Value: ((f0 * f1) * f2), left to right, every step one IEEE double
+ *   operation rounded to nearest (float8mul, float8mi, float8pl of float.c),
+ *   never fused: a row's value is bit-identical to the same C expression.
+ * NULL: every operator is strict, so an expression is NULL in a row where
+ *   any of its columns is NULL; COUNT, SUM, MIN and MAX then treat it as
+ *   they treat a NULL column input, and agg_null reports a group without a
+ *   non-NULL input.
+ * Aggregates: agg_expr[j] >= 0 makes aggregate j's argument exprs[agg_expr[j]]
+ *   and the aggregate float8 (aggs[j].col and .is_f64 are ignored): SUM is
+ *   float8pl in arrival order, MIN and MAX use float8_cmp_internal's total
+ *   order as above, COUNT counts non-NULL values.  On COUNT(*) it is
+ *   GX_ERR_INVALID.  The state words, and with them gx_gbd_wire_stride,
+ *   depend on fn alone.
+ * fquals: AND-ed with the integer quals and the visimap over float8 columns
+ *   (width 8), op 0..5 as gx_filter; a NULL input fails the row.  The
+ *   comparison is float8_cmp_internal (float.c): every NaN equals every NaN
+ *   and is greater than +inf, -0.0 equals +0.0.  A NaN literal is legal.
+ * At most GX_GB_MAX_OPERANDS distinct columns over all expressions and
+ *   fquals; a column named several times is read once per row.
+ * GX_ERR_INVALID names the item in gx_last_error: nexprs, nfquals or
+ *   nfactors out of range, a factor or fqual column out of range or not 8
+ *   bytes wide, a form outside 0..2, an agg_expr outside -1..nexprs-1 or on
+ *   COUNT(*), an fqual op outside 0..5, too many distinct operand columns.
+ * Known differences: float8mul's overflow / underflow ereport is not raised
+ *   (inf and 0 come back, as gx_q1 documents for its own products); a SUM
+ *   whose inputs are all -0.0 returns +0.0, as in gx_groupby_desc. ---- */
+#define GX_GB_MAX_FACTORS  3
+#define GX_GB_MAX_FQUALS   4
+#define GX_GB_MAX_OPERANDS 8   /* distinct float8 columns over all exprs + fquals */
+typedef enum { GX_FACTOR_COL = 0, GX_FACTOR_ONE_MINUS = 1, GX_FACTOR_ONE_PLUS = 2 } gx_factor_form;
+typedef struct gx_factor { int32_t col; int32_t form; } gx_factor;
+typedef struct gx_expr   { int32_t nfactors; int32_t _pad; gx_factor f[GX_GB_MAX_FACTORS]; } gx_expr;
+typedef struct gx_fqual  { int32_t col; int32_t op; double literal; } gx_fqual;   /* op 0..5 as gx_filter */
+typedef struct gx_gb_ext {
+    int32_t  nexprs, nfquals;
+    gx_expr  exprs[GX_GB_MAX_AGGS];
+    int32_t  agg_expr[GX_GB_MAX_AGGS];  /* -1: argument is aggs[j].col as today; else index into exprs */
+    gx_fqual fquals[GX_GB_MAX_FQUALS];
+} gx_gb_ext;
+gx_status gx_groupby_expr(gx_ctx *, const gx_gb_desc *, const gx_gb_ext * /* may be NULL */,
+                          gx_gb_result *out, gx_gbd_stats *stats /* may be NULL */);
+gx_status gx_groupby_expr_dist(gx_ctx *, const gx_gb_desc *, const gx_gb_ext * /* may be NULL */,
+                               gx_gb_result *out, gx_gb_stats *stats /* may be NULL */);
+
 /* ---- test-only entry points (parity harness; not part of the drop-in) ---- */
 /* gx_groupby_desc through the same launch helper with the scan grid and the
  * slot word chosen by the caller: grid = 0 is production (2048 workgroups),
@@ -522,6 +581,22 @@ int64_t   gx_gbd_wire_stride(const gx_gb_desc *);
  * merge its LDS table; wide_rowid = 1 forces the 8-byte slot word. */
 gx_status gx_test_groupby_desc(gx_ctx *, const gx_gb_desc *, int grid,
                                int wide_rowid, gx_gb_result *, gx_gbd_stats *);
+/* gx_groupby_expr through the same seam */
+gx_status gx_test_groupby_expr(gx_ctx *, const gx_gb_desc *, const gx_gb_ext *,
+                               int grid, int wide_rowid, gx_gb_result *,
+                               gx_gbd_stats *);
+/* Host restatements of the expression value and of the float8 qual through
+ * the same host/device functions the scan kernel calls, no GPU needed.
+ * expr_eval: vals / isnull are row-major n x ncols (isnull may be NULL = no
+ * NULLs), a factor's col indexes them; out[i] receives the value (0.0 where
+ * NULL), out_null[i] 1 where any factor's column is NULL.  Returns 0, or 1
+ * for bad arguments (nfactors, form or a column out of range).
+ * fqual: 1 when `x op literal` passes under float8_cmp_internal, 0 when it
+ * fails, -1 for an op outside 0..5. */
+int gx_selftest_expr_eval(const gx_expr *, const double *vals,
+                          const uint8_t *isnull, int64_t n, int ncols,
+                          double *out, uint8_t *out_null);
+int gx_selftest_fqual(int op, double x, double literal);
 /* The final ordering of gx_groupby_desc alone, no GPU needed: perm[0..n)
  * receives the row order of n rows of nkeys (1..GX_GB_MAX_KEYS) columns,
  * row-major keys / key_null, sorted by the (key_null, key) pairs column by

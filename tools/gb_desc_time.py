@@ -15,8 +15,16 @@ timed.  Recorded, not gated.
         (gx_groupby_dist's ms_partial at nsegs == 1: table clear + k_groupby
         + extract between two HIP events; gx_groupby_desc's ms_kernel is the
         scan kernel alone, so its own clear + extract span is not in it).
+  q1rev GX_TPCH_LINEITEM_Q1 at --sf: the same GROUP BY with COUNT(*) +
+        SUM(price) + SUM(price * (1 - disc)) through gx_groupby_expr (the
+        22 B/row k_q1_agg reads), alternated with gx_q1 and with the
+        two-aggregate gx_groupby_desc call of `low`.
+  low with --parent-root DIR (a built checkout of the parent commit): `low`
+        run by one fresh process per round from DIR and from this tree,
+        alternated --rounds times, to see whether the scan kernel that takes
+        no expressions moved.
 
-    python tools/gb_desc_time.py [--cases low,lds0,high] [--runs R] [--out F]
+    python tools/gb_desc_time.py [--cases low,lds0,high,q1rev] [--runs R] [--out F]
 
 Each case updates its own key of the JSON file, so cases may run in separate
 processes."""
@@ -24,7 +32,9 @@ import argparse
 import json
 import os
 import statistics
+import subprocess
 import sys
+import tempfile
 import time
 
 import numpy as np
@@ -41,6 +51,8 @@ ap.add_argument("--rows", type=float, default=100e6)
 ap.add_argument("--keys", type=float, default=10e6)
 ap.add_argument("--runs", type=int, default=7)
 ap.add_argument("--warmup", type=int, default=2)
+ap.add_argument("--parent-root", default=None)
+ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "groupby_desc.json"))
 args = ap.parse_args()
 assert args.runs >= 5, "report the median of at least 5 runs"
@@ -115,6 +127,85 @@ def case_low(ctx, sf):
         "ratio_desc_over_q1": md / mq,
         "bytes_per_row": {"groupby_desc": 14, "q1": 22},
         "tb_per_s": {"groupby_desc": 14 * n / md / 1e9, "q1": 22 * n / mq / 1e9},
+        "stream_ceiling_tb_per_s": STREAM_TBS,
+    }
+
+
+def case_low_vs_parent(parent_root, sf, rounds):
+    """`low` in fresh processes, the parent commit's tree and this one
+    alternated; each child checks its result against gx_q1 before timing"""
+    got = {"parent": [], "this": []}
+    for r in range(rounds):
+        for name, root in (("parent", parent_root), ("this", ROOT)):
+            with tempfile.TemporaryDirectory() as tmp:
+                f = os.path.join(tmp, "low.json")
+                subprocess.run(
+                    [sys.executable, os.path.join(root, "tools", "gb_desc_time.py"),
+                     "--cases", "low", "--sf", str(sf), "--runs", str(args.runs),
+                     "--warmup", str(args.warmup), "--out", f],
+                    check=True, cwd=root, stdout=subprocess.DEVNULL, timeout=300)
+                with open(f) as fh:
+                    low = json.load(fh)["low_cardinality"]
+            got[name].append({k: low[k] for k in ("ms_groupby_desc", "ms_q1")})
+            print(f"low: round {r} {name} "
+                  f"{low['ms_groupby_desc']['median']:.3f} ms", flush=True)
+    meds = {k: [x["ms_groupby_desc"]["median"] for x in v] for k, v in got.items()}
+    return {
+        "what": "case `low` (k_groupby_desc without expressions), one fresh "
+                "process per round from the parent commit's build and from "
+                "this one, alternated; ms_kernel median of each process",
+        "sf": sf, "rounds": rounds, "runs": args.runs, "warmup": args.warmup,
+        "parent": got["parent"], "this": got["this"],
+        "ms_parent": summary(meds["parent"]), "ms_this": summary(meds["this"]),
+        "every_new_above_every_parent": min(meds["this"]) > max(meds["parent"]),
+    }
+
+
+Q1REV_AGGS = [("count*", None), ("sum", 2, True), ("sum", [2, ("1-", 3)])]
+
+
+def q1_expr(ctx, t):
+    return ctx.groupby_expr(t, [0, 1], Q1REV_AGGS,
+                            quals=[(4, "<=", gx.CUTOFF_19950315)], stats=True)
+
+
+def case_q1rev(ctx, sf):
+    t = ctx.tpch_gen(gx.TPCH_LINEITEM_Q1, sf)
+    n = t.nrows
+    q1 = ctx.q1(t, gx.CUTOFF_19950315)
+    res, st = q1_expr(ctx, t)
+    check_q1(res, q1)
+    want = np.nonzero(q1["count"])[0]
+    np.testing.assert_allclose(res["aggs"][2], q1["sum_revenue"][want], rtol=1e-6)
+    check_q1(q1_desc(ctx, t)[0], q1)
+    print(f"q1rev: sf {sf}, {n} rows, results agree with gx_q1", flush=True)
+    for _ in range(args.warmup):
+        ctx.q1(t, gx.CUTOFF_19950315)
+        q1_desc(ctx, t)
+        q1_expr(ctx, t)
+    ms_q1, ms_desc, ms_expr = [], [], []
+    for _ in range(args.runs):                  # alternated
+        ms_q1.append(ctx.q1(t, gx.CUTOFF_19950315)["ms"])
+        ms_desc.append(q1_desc(ctx, t)[1]["ms_kernel"])
+        ms_expr.append(q1_expr(ctx, t)[1]["ms_kernel"])
+    t.free()
+    me, md, mq = (statistics.median(x) for x in (ms_expr, ms_desc, ms_q1))
+    return {
+        "what": "GROUP BY (returnflag, linestatus) WHERE shipdate <= cutoff, "
+                "COUNT(*) + SUM(price) + SUM(price * (1 - disc)): "
+                "gx_groupby_expr (ms_kernel) against gx_q1's k_q1_agg (ms_out) "
+                "and against gx_groupby_desc's COUNT(*) + SUM(price), same "
+                "table, alternated",
+        "sf": sf, "rows": n, "rows_pass": st["rows_pass"],
+        "rows_lds": st["rows_lds"], "rows_global": st["rows_global"],
+        "runs": args.runs, "warmup": args.warmup,
+        "ms_groupby_expr": summary(ms_expr), "ms_groupby_desc": summary(ms_desc),
+        "ms_q1": summary(ms_q1),
+        "ratio_expr_over_q1": me / mq, "ratio_desc_over_q1": md / mq,
+        "ratio_expr_over_desc": me / md,
+        "bytes_per_row": {"groupby_expr": 22, "groupby_desc": 14, "q1": 22},
+        "tb_per_s": {"groupby_expr": 22 * n / me / 1e9,
+                     "groupby_desc": 14 * n / md / 1e9, "q1": 22 * n / mq / 1e9},
         "stream_ceiling_tb_per_s": STREAM_TBS,
     }
 
@@ -230,10 +321,19 @@ out = {}
 if os.path.exists(path):
     with open(path) as f:
         out = json.load(f)
-ctx = gx.Context(device=0, seg=0, nsegs=1)
+ctx = None
 for case in CASES:
-    if case == "low":
+    if case == "low" and args.parent_root:      # children only: no context here
+        out["low_cardinality_vs_parent"] = case_low_vs_parent(
+            os.path.abspath(args.parent_root), args.sf, args.rounds)
+    else:
+        ctx = ctx or gx.Context(device=0, seg=0, nsegs=1)
+    if case == "low" and args.parent_root:
+        pass
+    elif case == "low":
         out["low_cardinality"] = case_low(ctx, args.sf)
+    elif case == "q1rev":
+        out["q1_revenue"] = case_q1rev(ctx, args.sf)
     elif case == "lds0":
         out["low_cardinality_lds_off"] = case_lds0(ctx, args.lds0_sf)
     elif case == "high":
@@ -244,4 +344,5 @@ for case in CASES:
     with open(path, "w") as f:
         json.dump(out, f, indent=1)
     print(json.dumps(out), flush=True)
-ctx.close()
+if ctx:
+    ctx.close()
