@@ -142,6 +142,42 @@ class _GbExt(ctypes.Structure):
                 ("fquals", _FQual * GB_MAX_FQUALS)]
 
 
+GBJ_MAX_JOINS = 2
+
+
+class _GbJoin(ctypes.Structure):
+    _fields_ = [("dim", ctypes.c_void_p),
+                ("fact_col", ctypes.c_int32), ("dim_key_col", ctypes.c_int32),
+                ("nquals", ctypes.c_int32), ("_pad", ctypes.c_int32),
+                ("quals", _Filter * MAX_EXTRA_QUALS)]
+
+
+class _GbjExt(ctypes.Structure):
+    _fields_ = [("njoins", ctypes.c_int32), ("_pad", ctypes.c_int32),
+                ("joins", _GbJoin * GBJ_MAX_JOINS),
+                ("key_side", ctypes.c_int32 * GB_MAX_KEYS),
+                ("agg_side", ctypes.c_int32 * GB_MAX_AGGS)]
+
+
+class _GbjStats(ctypes.Structure):
+    _fields_ = [("ms_build", ctypes.c_double), ("ms_kernel", ctypes.c_double),
+                ("rows_in", ctypes.c_int64), ("rows_probed", ctypes.c_int64),
+                ("rows_pass", ctypes.c_int64), ("rows_lds", ctypes.c_int64),
+                ("rows_global", ctypes.c_int64), ("groups", ctypes.c_int64),
+                ("dim_rows", ctypes.c_int64 * GBJ_MAX_JOINS)]
+
+
+class DimCol:
+    """A group key, or a column aggregate's column, read from the matched row
+    of joins[j]'s dimension table (Context.groupby_join): DimCol(j, col)."""
+
+    def __init__(self, j, col):
+        self.j, self.col = j, col
+
+    def __repr__(self):
+        return f"DimCol({self.j}, {self.col})"
+
+
 class _GbResult(ctypes.Structure):
     _fields_ = [("ngroups", ctypes.c_int64),
                 ("nkeys", ctypes.c_int32), ("naggs", ctypes.c_int32),
@@ -355,6 +391,37 @@ def _load():
                                          ctypes.POINTER(_GbExt),
                                          ctypes.POINTER(_GbResult),
                                          ctypes.POINTER(_GbStats)]
+    lib.gx_groupby_join.argtypes = [ctypes.c_void_p, ctypes.POINTER(_GbDesc),
+                                    ctypes.POINTER(_GbjExt),
+                                    ctypes.POINTER(_GbExt),
+                                    ctypes.POINTER(_GbResult),
+                                    ctypes.POINTER(_GbjStats)]
+    lib.gx_test_groupby_join.argtypes = [ctypes.c_void_p,
+                                         ctypes.POINTER(_GbDesc),
+                                         ctypes.POINTER(_GbjExt),
+                                         ctypes.POINTER(_GbExt), ctypes.c_int,
+                                         ctypes.c_int,
+                                         ctypes.POINTER(_GbResult),
+                                         ctypes.POINTER(_GbjStats)]
+    lib.gx_groupby_join_dist.argtypes = [ctypes.c_void_p, ctypes.POINTER(_GbDesc),
+                                         ctypes.POINTER(_GbjExt),
+                                         ctypes.POINTER(_GbExt),
+                                         ctypes.POINTER(_GbResult),
+                                         ctypes.POINTER(_GbStats)]
+    lib.gx_test_gbj_partial.argtypes = [ctypes.c_void_p, ctypes.POINTER(_GbDesc),
+                                        ctypes.POINTER(_GbjExt), ctypes.c_int,
+                                        ctypes.c_void_p, ctypes.c_void_p,
+                                        ctypes.c_int64,
+                                        ctypes.POINTER(ctypes.c_int64)]
+    lib.gx_selftest_gbj_join.restype = ctypes.c_int64
+    lib.gx_selftest_gbj_join.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_int64, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_int64,
+                                         ctypes.c_void_p,
+                                         ctypes.POINTER(ctypes.c_int64)]
+    lib.gx_selftest_gbj_slots.restype = ctypes.c_int64
+    lib.gx_selftest_gbj_slots.argtypes = [ctypes.c_void_p, ctypes.c_int64,
+                                          ctypes.c_int64, ctypes.c_void_p]
     lib.gx_selftest_expr_eval.restype = ctypes.c_int
     lib.gx_selftest_expr_eval.argtypes = [ctypes.POINTER(_Expr), ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.c_int64,
@@ -560,6 +627,75 @@ def _gb_expr_desc(table, keys, aggs, quals, fquals, max_groups):
     for q, (col, op, lit) in enumerate(fquals[:GB_MAX_FQUALS]):
         ext.fquals[q] = _FQual(col, _opcode(op), float(lit))
     return _gb_desc(table, keys, plain, quals, max_groups), ext, plain
+
+
+def _gbj_desc(table, keys, aggs, joins, quals, fquals, max_groups):
+    """(gx_gb_desc, gx_gbj_ext, gx_gb_ext, aggs as groupby_desc specs) from the
+    groupby_join argument shapes: a DimCol key or aggregate column sets its
+    side to the join's dimension; counts go through unclipped so that the
+    library's own range checks answer"""
+    jext = _GbjExt()
+    kcols, specs = [], []
+    for k, c in enumerate(keys):
+        if isinstance(c, DimCol):
+            if k < GB_MAX_KEYS:
+                jext.key_side[k] = c.j + 1
+            c = c.col
+        kcols.append(c)
+    for j, spec in enumerate(aggs):
+        if isinstance(spec[1], DimCol):
+            if j < GB_MAX_AGGS:
+                jext.agg_side[j] = spec[1].j + 1
+            spec = (spec[0], spec[1].col) + tuple(spec[2:])
+        specs.append(tuple(spec))
+    jext.njoins = len(joins)
+    for j, jn in enumerate(joins[:GBJ_MAX_JOINS]):
+        dim, fact_col, dim_key_col = jn[:3]
+        jq = list(jn[3]) if len(jn) > 3 else []
+        jext.joins[j].dim = None if dim is None else dim._t
+        jext.joins[j].fact_col = fact_col
+        jext.joins[j].dim_key_col = dim_key_col
+        jext.joins[j].nquals = len(jq)
+        for q, (col, op, lit) in enumerate(jq[:MAX_EXTRA_QUALS]):
+            jext.joins[j].quals[q] = _Filter(col, _opcode(op), int(lit))
+    d, ext, plain = _gb_expr_desc(table, kcols, specs, quals, fquals, max_groups)
+    return d, jext, ext, plain
+
+
+def selftest_gbj_join(dim_keys, fact_keys, dim_null=None, fact_null=None):
+    """The join table of the descriptor GROUP BY over a join, restated on the
+    host through the hash, slot and compare functions the kernels call (no
+    GPU): a serial build over dim_keys (dim_null marks NULL keys, never
+    inserted) and one probe per fact key.  Returns (rows, None), rows[i] the
+    matched dimension row or -1, or (None, key) for a duplicated key."""
+    dk = np.ascontiguousarray(dim_keys, np.int64)
+    fk = np.ascontiguousarray(fact_keys, np.int64)
+    dn = None if dim_null is None else np.ascontiguousarray(dim_null, np.uint8)
+    fn = None if fact_null is None else np.ascontiguousarray(fact_null, np.uint8)
+    assert dn is None or dn.shape == dk.shape
+    assert fn is None or fn.shape == fk.shape
+    out = np.full(len(fk), -2, np.int64)
+    dup = ctypes.c_int64()
+    rc = lib().gx_selftest_gbj_join(
+        dk.ctypes.data if len(dk) else None, None if dn is None else dn.ctypes.data,
+        len(dk), fk.ctypes.data if len(fk) else None,
+        None if fn is None else fn.ctypes.data, len(fk),
+        out.ctypes.data if len(fk) else None, ctypes.byref(dup))
+    if rc < 0:
+        raise ValueError(f"gx_selftest_gbj_join: bad arguments ({rc})")
+    return (None, dup.value) if rc == 1 else (out, None)
+
+
+def selftest_gbj_slots(keys, ndim):
+    """(home slot of every key, slot count) of the join table of a dimension
+    of ndim rows (host only, no GPU)."""
+    k = np.ascontiguousarray(keys, np.int64)
+    out = np.zeros(len(k), np.uint32)
+    n = lib().gx_selftest_gbj_slots(k.ctypes.data if len(k) else None, len(k),
+                                    ndim, out.ctypes.data if len(k) else None)
+    if n < 0:
+        raise ValueError(f"gx_selftest_gbj_slots: bad arguments ({n})")
+    return out, int(n)
 
 
 def selftest_expr_eval(factors, vals, isnull=None):
@@ -932,6 +1068,91 @@ class Context:
         if stats:
             return out, {f: getattr(st, f) for f, _ in st._fields_}
         return out
+
+    def groupby_join(self, table, keys, aggs, joins, quals=(), fquals=(),
+                     max_groups=0, stats=False):
+        """groupby_expr over a join (gx_groupby_join): table is the fact side
+        of up to 2 inner equi-joins, joins = [(dim_table, fact_col,
+        dim_key_col[, quals])] with AND-ed (col, op, literal) quals over the
+        dimension.  A key, or a column aggregate's col, may be DimCol(j, col):
+        column col of joins[j]'s dimension at the matched row.  Dimension
+        keys must be unique among the rows that take part; a fact row that
+        misses any join is dropped.  Everything else, and the result, as
+        groupby_expr; with stats=True returns (result, gx_gbj_stats as a
+        dict, its dim_rows a list)."""
+        return self._groupby_join(table, keys, aggs, joins, quals, fquals,
+                                  max_groups, stats, None)
+
+    def test_groupby_join(self, table, keys, aggs, joins, quals=(), fquals=(),
+                          max_groups=0, stats=False, grid=0, wide_rowid=False,
+                          jext=None):
+        """groupby_join through the test seam (grid, wide_rowid as for
+        test_groupby_desc).  A callable jext is given the filled gx_gbj_ext
+        mirror to alter before the call (raw counts, sides and indexes for
+        the error paths)."""
+        return self._groupby_join(table, keys, aggs, joins, quals, fquals,
+                                  max_groups, stats,
+                                  (grid, 1 if wide_rowid else 0), jext)
+
+    def _groupby_join(self, table, keys, aggs, joins, quals, fquals, max_groups,
+                      stats, seam, jext_arg=None):
+        d, jext, ext, plain = _gbj_desc(table, list(keys), list(aggs), list(joins),
+                                        list(quals), list(fquals), max_groups)
+        if callable(jext_arg):
+            jext_arg(jext)
+        res, st = _GbResult(), _GbjStats()
+        if seam is None:
+            rc = self._lib.gx_groupby_join(
+                self._h, ctypes.byref(d), ctypes.byref(jext), ctypes.byref(ext),
+                ctypes.byref(res), ctypes.byref(st))
+        else:
+            rc = self._lib.gx_test_groupby_join(
+                self._h, ctypes.byref(d), ctypes.byref(jext), ctypes.byref(ext),
+                seam[0], seam[1], ctypes.byref(res), ctypes.byref(st))
+        self._chk(rc)
+        out = self._gb_result(res, plain)
+        if stats:
+            sd = {f: getattr(st, f) for f, _ in st._fields_}
+            sd["dim_rows"] = list(st.dim_rows)
+            return out, sd
+        return out
+
+    def groupby_join_dist(self, table, keys, aggs, joins, quals=(), fquals=(),
+                          max_groups=0, stats=False):
+        """Two-stage groupby_join across all segments of this context
+        (gx_groupby_join_dist): every segment holds each dimension complete;
+        returns the groups THIS segment owns; with stats=True returns
+        (result, gx_gb_stats as a dict)."""
+        d, jext, ext, plain = _gbj_desc(table, list(keys), list(aggs), list(joins),
+                                        list(quals), list(fquals), max_groups)
+        res, st = _GbResult(), _GbStats()
+        self._chk(self._lib.gx_groupby_join_dist(
+            self._h, ctypes.byref(d), ctypes.byref(jext), ctypes.byref(ext),
+            ctypes.byref(res), ctypes.byref(st)))
+        out = self._gb_result(res, plain)
+        if stats:
+            return out, {f: getattr(st, f) for f, _ in st._fields_}
+        return out
+
+    def test_gbj_partial(self, table, keys, aggs, joins, nsegs, quals=(),
+                         max_groups=0):
+        """Partial agg + partition kernels of groupby_join_dist on one GPU:
+        (counts, rows) as test_gbd_partial."""
+        d, jext, _, plain = _gbj_desc(table, list(keys), list(aggs), list(joins),
+                                      list(quals), [], max_groups)
+        cap = max(table.nrows, 1)
+        counts = np.zeros(max(nsegs, 1), np.int64)
+        rows = np.zeros(cap, gbd_wire_dtype([0] * len(keys), plain))
+        total = ctypes.c_int64()
+        self._chk(self._lib.gx_test_gbj_partial(
+            self._h, ctypes.byref(d), ctypes.byref(jext), nsegs,
+            counts.ctypes.data, rows.ctypes.data, cap, ctypes.byref(total)))
+        return counts[:nsegs], rows[:total.value]
+
+    def selftest_gbj_join(self, dim_keys, fact_keys, dim_null=None,
+                          fact_null=None):
+        """The module's selftest_gbj_join (host only; needs no GPU work)."""
+        return selftest_gbj_join(dim_keys, fact_keys, dim_null, fact_null)
 
     def test_gbd_partial(self, table, keys, aggs, nsegs, quals=(),
                          max_groups=0):

@@ -42,6 +42,7 @@ extern "C" unsigned ZSTD_isError(size_t code);
 #include <string>
 #include <vector>
 #include <map>
+#include <set>
 #include <utility>
 
 /* ================= error plumbing ================= */
@@ -2971,6 +2972,131 @@ struct gbd_key_wire {
     { return rows + r * stride + a.nkeys + (a.nkeys ? 1 : 0); }
 };
 
+/* ---- joins (gx_gbj_ext): the scanned table is the fact side of up to two
+ * inner equi-joins; a key or an aggregate's argument may be a column of the
+ * matched dimension row.  Only the JOIN instantiations of k_groupby_desc
+ * receive gbd_jargs; the others take the empty gbd_nojoin.
+ *
+ * JOIN TABLE, built like the group tables: u32 slots, a slot holds the
+ * dimension row + 1 of the row that claimed it (CAS from 0), a power-of-two
+ * slot count of at least 2 x the dimension's rows, linear probing.  A key is
+ * compared by reading the dimension's key column at the slot's row (the
+ * input is immutable, so it is visible the moment the claim is): no key value
+ * is reserved.  The scan only reads the table, after the build has finished
+ * on the same stream.  The hash, step and compare below are also what the
+ * host restatement gx_selftest_gbj_join runs. */
+GX_HD uint64_t gbj_home(int64_t key, uint64_t mask)
+{
+    return gx_hmix64((uint64_t) key + 0x9E3779B97F4A7C15ULL) & mask;
+}
+
+GX_HD uint64_t gbj_next(uint64_t slot, uint64_t mask) { return (slot + 1) & mask; }
+
+GX_HD bool gbj_key_eq(int64_t dim_key, int64_t key) { return dim_key == key; }
+
+/* the dimension row whose key equals `key`, or -1; keyat(r) is the key of
+ * dimension row r */
+template <typename KEYAT>
+GX_HD int64_t gbj_probe(const uint32_t *slots, uint64_t mask, int64_t key,
+                        const KEYAT &keyat)
+{
+    uint64_t s = gbj_home(key, mask);
+    for (uint64_t n = 0; n <= mask; n++)
+    {
+        const uint32_t cur = slots[s];
+        if (cur == 0u) return -1;
+        if (gbj_key_eq(keyat((int64_t) cur - 1), key)) return (int64_t) cur - 1;
+        s = gbj_next(s, mask);
+    }
+    return -1;
+}
+
+struct gbj_col_key {
+    const gbd_col &c;
+    __device__ __forceinline__ int64_t operator()(int64_t r) const
+    { return gbd_load(c, r); }
+};
+
+struct gbd_join1 {
+    gbd_col fact;              /* join column of the scanned table */
+    gbd_col dkey;              /* key column of the dimension */
+    const uint32_t *slots;
+    uint64_t mask;
+};
+
+/* key[k] / agg[j] of gbd_args are bound to the table their side names */
+struct gbd_jargs {
+    gbd_join1 j[GX_GBJ_MAX_JOINS];
+    int32_t njoins;
+    uint32_t key_joins;        /* bit j: some key reads joins[j].dim */
+    int32_t key_side[GX_GB_MAX_KEYS];
+    int32_t agg_side[GX_GB_MAX_AGGS];
+};
+struct gbd_nojoin {};
+static_assert(GX_GBJ_MAX_JOINS == 2, "a row's matches are the two scalars d0, d1");
+
+/* the dimension row fact row r matches in join J (J a compile-time index at
+ * every call site), or -1 */
+__device__ __forceinline__ int64_t gbj_match(const gbd_join1 &J, int64_t key)
+{
+    return gbj_probe(J.slots, J.mask, key, gbj_col_key{J.dkey});
+}
+
+/* Key source of ONE fact row whose matched dimension rows are d0 / d1: a
+ * fact-side key reads the row itself, a dim-side key the dimension's column
+ * at that row's match.  Two scalars, not an array indexed by the side: an
+ * indexed array would live in scratch. */
+struct gbd_key_joined {
+    const gbd_jargs &jx;
+    int64_t d0, d1;
+    __device__ __forceinline__ int64_t at(int k, int64_t r) const
+    {
+        const int side = jx.key_side[k];
+        return side == 0 ? r : side == 1 ? d0 : d1;
+    }
+    __device__ __forceinline__ bool isnull(const gbd_args &a, int k, int64_t r) const
+    { return gbd_isnull(a.key[k], at(k, r)); }
+    __device__ __forceinline__ int64_t load(const gbd_args &a, int k, int64_t r) const
+    { return gbd_load(a.key[k], at(k, r)); }
+};
+
+/* Key source of a REPRESENTATIVE row of a join scan: it finds the row's OWN
+ * matched dimension rows by probing again (the row passed, so the probes
+ * succeed) and never reads through the match of the row at hand.  No side
+ * array of matched rows: a store at claim time is not visible to a thread
+ * that sees the claim (header comment above), and the table the probe reads
+ * is immutable during the scan. */
+struct gbd_key_join {
+    const gbd_jargs &jx;
+    /* the source of row r with the joins its keys use probed once */
+    __device__ __forceinline__ gbd_key_joined of(int64_t r) const
+    {
+        int64_t d0 = 0, d1 = 0;
+        if (jx.key_joins & 1u) d0 = gbj_match(jx.j[0], gbd_load(jx.j[0].fact, r));
+        if (jx.key_joins & 2u) d1 = gbj_match(jx.j[1], gbd_load(jx.j[1].fact, r));
+        return gbd_key_joined{jx, d0, d1};
+    }
+    __device__ __forceinline__ bool isnull(const gbd_args &a, int k, int64_t r) const
+    { return of(r).isnull(a, k, r); }
+    __device__ __forceinline__ int64_t load(const gbd_args &a, int k, int64_t r) const
+    { return of(r).load(a, k, r); }
+};
+
+/* the same as a kernel argument (k_gbd_extract after a join scan) */
+struct gbd_key_join_args {
+    gbd_jargs jx;
+    __device__ __forceinline__ bool isnull(const gbd_args &a, int k, int64_t r) const
+    { return gbd_key_join{jx}.isnull(a, k, r); }
+    __device__ __forceinline__ int64_t load(const gbd_args &a, int k, int64_t r) const
+    { return gbd_key_join{jx}.load(a, k, r); }
+};
+
+/* the key source of the scan kernel's representatives */
+__device__ __forceinline__ gbd_key_cols gbd_scan_src(const gbd_nojoin &)
+{ return gbd_key_cols{}; }
+__device__ __forceinline__ gbd_key_join gbd_scan_src(const gbd_jargs &jx)
+{ return gbd_key_join{jx}; }
+
 /* key values (0 where NULL), null bits and hash of one row */
 template <typename SRC>
 __device__ __forceinline__ uint64_t gbd_row_keys(const SRC &src, const gbd_args &a,
@@ -3012,6 +3138,37 @@ __device__ __forceinline__ bool gbd_keys_eq(const SRC &src, const gbd_args &a,
                  (rnull || src.load(a, k, r) == kv[k]);
         }
     return eq;
+}
+
+/* a join scan's representative: probe once per row, not once per column */
+__device__ __forceinline__ uint64_t gbd_row_keys(const gbd_key_join &src,
+                                                 const gbd_args &a, int64_t row,
+                                                 int64_t (&kv)[GX_GB_MAX_KEYS],
+                                                 unsigned &kn)
+{
+    return gbd_row_keys(src.of(row), a, row, kv, kn);
+}
+
+__device__ __forceinline__ bool gbd_keys_eq(const gbd_key_join &src, const gbd_args &a,
+                                            const int64_t (&kv)[GX_GB_MAX_KEYS],
+                                            unsigned kn, int64_t r)
+{
+    return gbd_keys_eq(src.of(r), a, kv, kn, r);
+}
+
+/* gbd_row_keys' hash over key values already gathered (a join scan loads a
+ * row's fact-side keys before its probes and its dim-side keys after them) */
+__device__ __forceinline__ uint64_t gbd_keys_hash(const gbd_args &a,
+                                                  const int64_t (&kv)[GX_GB_MAX_KEYS],
+                                                  unsigned kn)
+{
+    uint64_t h = 0x9E3779B97F4A7C15ULL;
+#pragma unroll
+    for (int k = 0; k < GX_GB_MAX_KEYS; k++)
+        if (k < a.nkeys)
+            h = gx_hmix64((h ^ (uint64_t) kv[k]) +
+                          (((kn >> k) & 1u) ? 0xD6E8FEB86659FD93ULL : 0ULL));
+    return h;
 }
 
 /* find or claim the global slot of the group of row i (keys kv/kn, hash h);
@@ -3136,11 +3293,49 @@ __device__ __forceinline__ void gbd_accum_x(const gbd_args &a, const gbd_xargs &
     }
 }
 
-/* stats: [0] rows passing visimap + quals, [1] rows accumulated in LDS */
-template <typename ST, bool LDS, bool EXPR>
+/* the same for a join scan: a column aggregate reads its argument in the
+ * table its side names, at fact row i or at the row's matches d0 / d1 */
+template <bool EXPR, typename X>
+__device__ __forceinline__ void gbj_accum(const gbd_args &a, const gbd_jargs &jx,
+                                          const X &x, int64_t i, int64_t d0,
+                                          int64_t d1, unsigned long long *w,
+                                          const gbd_d8 &ev, unsigned enull)
+{
+#pragma unroll
+    for (int j = 0; j < GX_GB_MAX_AGGS; j++)
+    {
+        if (j >= a.naggs) continue;
+        unsigned long long *p = w + a.aword[j];
+        if constexpr (EXPR)
+        {
+            const int e = x.aexpr[j];
+            if (e >= 0)
+            {
+                if ((enull >> e) & 1u) continue;         /* strict transitions */
+                const int op = a.aop[j];
+                if (op == GBD_COUNT) { atomicAdd(p, 1ULL); continue; }
+                const double v = ev[e];
+                const uint64_t bits = (uint64_t) __double_as_longlong(v);
+                if (op == GBD_SUM_F64) atomicAdd((double *) p, v);
+                else if (op == GBD_MAX_F64)
+                    atomicMax(p, (unsigned long long) gbd_f64_image(bits));
+                else atomicMax(p, (unsigned long long) ~gbd_f64_image(bits));
+                atomicAdd(p + 1, 1ULL);
+                continue;
+            }
+        }
+        const int side = jx.agg_side[j];
+        gbd_accum_col(a, j, side == 0 ? i : side == 1 ? d0 : d1, p);
+    }
+}
+
+/* stats: [0] rows passing visimap + quals (JOIN: and matching every join),
+ * [1] rows accumulated in LDS, [4] JOIN: rows that reached the probes */
+template <typename ST, bool LDS, bool EXPR, bool JOIN>
 __global__ void __launch_bounds__(TPB)
 k_groupby_desc(const gbd_args a,
-               const std::conditional_t<EXPR, gbd_xargs, gbd_noexpr> x, ST *trow,
+               const std::conditional_t<EXPR, gbd_xargs, gbd_noexpr> x,
+               const std::conditional_t<JOIN, gbd_jargs, gbd_nojoin> jx, ST *trow,
                unsigned long long *tacc, uint64_t tmask,
                unsigned long long *stats, int *err)
 {
@@ -3157,7 +3352,9 @@ k_groupby_desc(const gbd_args a,
         if (threadIdx.x == 0) { s_seen = 0; s_miss = 0; }
         __syncthreads();
     }
-    unsigned long long n_pass = 0, n_lds = 0;
+    /* where a representative row's keys are read */
+    const auto src = gbd_scan_src(jx);
+    unsigned long long n_pass = 0, n_lds = 0, n_probed = 0;
     int64_t i = blockIdx.x * (int64_t) blockDim.x + threadIdx.x;
     const int64_t stride = gridDim.x * (int64_t) blockDim.x;
     for (; i < a.nrows; i += stride)
@@ -3167,7 +3364,38 @@ k_groupby_desc(const gbd_args a,
          * outcome: one memory round trip per row instead of two */
         int64_t kv[GX_GB_MAX_KEYS];
         unsigned kn;
-        const uint64_t h = gbd_row_keys(gbd_key_cols{}, a, i, kv, kn);
+        uint64_t h;
+        /* JOIN: the fact-side keys and the join columns go out here as well;
+         * the dim-side keys and the hash follow the probes */
+        int64_t jv0 = 0, jv1 = 0;
+        bool jnull = false;
+        if constexpr (JOIN)
+        {
+            kn = 0;
+#pragma unroll
+            for (int k = 0; k < GX_GB_MAX_KEYS; k++)
+            {
+                kv[k] = 0;
+                if (k < a.nkeys && jx.key_side[k] == 0)
+                {
+                    const bool isnull = gbd_isnull(a.key[k], i);
+                    kv[k] = isnull ? 0 : gbd_load(a.key[k], i);
+                    kn |= (unsigned) isnull << k;
+                }
+            }
+            if (jx.njoins > 0)
+            {
+                jnull = gbd_isnull(jx.j[0].fact, i);
+                jv0 = gbd_load(jx.j[0].fact, i);
+            }
+            if (jx.njoins > 1)
+            {
+                jnull = jnull || gbd_isnull(jx.j[1].fact, i);
+                jv1 = gbd_load(jx.j[1].fact, i);
+            }
+        }
+        else
+            h = gbd_row_keys(gbd_key_cols{}, a, i, kv, kn);
         /* EXPR: every distinct operand column once per row, value and
          * validity, in the same round trip */
         gbd_d8 ov = 0.0, ev = 0.0;
@@ -3203,6 +3431,35 @@ k_groupby_desc(const gbd_args a,
                                           x.fqimg[q]);
         }
         if (!pass) continue;
+        /* JOIN: the quals are decided; now the probes, each a chain of
+         * dependent random reads.  The join operator is strict, and a row
+         * that misses any join is dropped (inner join). */
+        int64_t d0 = 0, d1 = 0;
+        if constexpr (JOIN)
+        {
+            n_probed++;
+            if (jnull) continue;
+            if (jx.njoins > 0)
+            {
+                d0 = gbj_match(jx.j[0], jv0);
+                if (d0 < 0) continue;
+            }
+            if (jx.njoins > 1)
+            {
+                d1 = gbj_match(jx.j[1], jv1);
+                if (d1 < 0) continue;
+            }
+            const gbd_key_joined own{jx, d0, d1};
+#pragma unroll
+            for (int k = 0; k < GX_GB_MAX_KEYS; k++)
+                if (k < a.nkeys && jx.key_side[k] != 0)
+                {
+                    const bool isnull = own.isnull(a, k, i);
+                    kv[k] = isnull ? 0 : own.load(a, k, i);
+                    kn |= (unsigned) isnull << k;
+                }
+            h = gbd_keys_hash(a, kv, kn);
+        }
         n_pass++;
         if constexpr (EXPR)
         {
@@ -3239,13 +3496,16 @@ k_groupby_desc(const gbd_args a,
                         cur = atomicCAS(&lrow[ls], (ST) 0, (ST) (i + 1));
                         if (cur == (ST) 0) { done = true; break; }
                     }
-                    if (gbd_keys_eq(gbd_key_cols{}, a, kv, kn, (int64_t) cur - 1))
+                    if (gbd_keys_eq(src, a, kv, kn, (int64_t) cur - 1))
                     { done = true; break; }
                     ls = (ls + 1) & (L - 1);
                 }
                 if (done)
                 {
-                    if constexpr (EXPR)
+                    if constexpr (JOIN)
+                        gbj_accum<EXPR>(a, jx, x, i, d0, d1,
+                                        lacc + (size_t) ls * a.awords, ev, enull);
+                    else if constexpr (EXPR)
                         gbd_accum_x(a, x, i, lacc + (size_t) ls * a.awords, ev, enull);
                     else
                         gbd_accum(a, i, lacc + (size_t) ls * a.awords);
@@ -3263,11 +3523,13 @@ k_groupby_desc(const gbd_args a,
         }
         if (!done)
         {
-            uint64_t slot = gbd_ginsert<ST>(gbd_key_cols{}, a, trow, tmask, h, kv, kn,
-                                            i, err);
+            uint64_t slot = gbd_ginsert<ST>(src, a, trow, tmask, h, kv, kn, i, err);
             if (slot != ~0ULL)
             {
-                if constexpr (EXPR)
+                if constexpr (JOIN)
+                    gbj_accum<EXPR>(a, jx, x, i, d0, d1, tacc + slot * a.awords, ev,
+                                    enull);
+                else if constexpr (EXPR)
                     gbd_accum_x(a, x, i, tacc + slot * a.awords, ev, enull);
                 else
                     gbd_accum(a, i, tacc + slot * a.awords);
@@ -3284,9 +3546,8 @@ k_groupby_desc(const gbd_args a,
             const int64_t r = (int64_t) r1 - 1;
             int64_t kv[GX_GB_MAX_KEYS];
             unsigned kn;
-            const uint64_t h = gbd_row_keys(gbd_key_cols{}, a, r, kv, kn);
-            uint64_t slot = gbd_ginsert<ST>(gbd_key_cols{}, a, trow, tmask, h, kv, kn,
-                                            r, err);
+            const uint64_t h = gbd_row_keys(src, a, r, kv, kn);
+            uint64_t slot = gbd_ginsert<ST>(src, a, trow, tmask, h, kv, kn, r, err);
             if (slot == ~0ULL) continue;
             d_gbd_merge_words(a, lacc + (size_t) s * a.awords,
                               tacc + slot * a.awords);
@@ -3294,6 +3555,7 @@ k_groupby_desc(const gbd_args a,
     }
     gx_wave_count_add(stats + 0, n_pass);
     gx_wave_count_add(stats + 1, n_lds);
+    if constexpr (JOIN) gx_wave_count_add(stats + 4, n_probed);
 }
 
 /* Compact the occupied slots: representative row -> sign-extended keys and
@@ -3351,6 +3613,61 @@ k_gbd_extract(const gbd_args a, const SRC src, const ST *trow,
         }
         __syncthreads();
     }
+}
+
+/* Build one join table: every dimension row that its visimap, the join's
+ * quals (a NULL input fails) and the key's validity leave is inserted by CAS
+ * from 0.  A slot whose row carries an equal key is a duplicate among the
+ * participating rows: the error bit is set and the key recorded (any one of
+ * them).  misc: [0] rows inserted, [1] error bit, [2] a duplicated key. */
+struct gbj_build_args {
+    gbd_col key;
+    gbd_col qual[GX_MAX_EXTRA_QUALS];
+    int64_t qlit[GX_MAX_EXTRA_QUALS];
+    int32_t qop[GX_MAX_EXTRA_QUALS];
+    int32_t nquals, _pad;
+    int64_t nrows;
+    const uint8_t *vmap;
+};
+
+__global__ void __launch_bounds__(TPB)
+k_gbj_build(const gbj_build_args b, uint32_t *slots, uint64_t mask,
+            unsigned long long *misc)
+{
+    unsigned long long n_ins = 0;
+    const int64_t stride = gridDim.x * (int64_t) TPB;
+    for (int64_t i = blockIdx.x * (int64_t) TPB + threadIdx.x; i < b.nrows; i += stride)
+    {
+        if (gx_vm_hidden(b.vmap, i)) continue;
+        bool pass = !gbd_isnull(b.key, i);               /* strict operator */
+        const int64_t key = gbd_load(b.key, i);
+#pragma unroll
+        for (int q = 0; q < GX_MAX_EXTRA_QUALS; q++)
+            if (q < b.nquals)
+                pass = pass && !gbd_isnull(b.qual[q], i) &&
+                       gx_cmp<int64_t>(b.qop[q], gbd_load(b.qual[q], i), b.qlit[q]);
+        if (!pass) continue;
+        uint64_t s = gbj_home(key, mask);
+        /* at most nrows <= (mask + 1) / 2 slots are ever claimed, so a free
+         * one is met within the bound */
+        for (uint64_t n = 0; n <= mask; n++)
+        {
+            uint32_t cur = slots[s];
+            if (cur == 0u)
+            {
+                cur = atomicCAS(&slots[s], 0u, (uint32_t) (i + 1));
+                if (cur == 0u) { n_ins++; break; }
+            }
+            if (gbj_key_eq(gbd_load(b.key, (int64_t) cur - 1), key))
+            {
+                misc[2] = (unsigned long long) key;
+                atomicOr((unsigned int *) (misc + 1), 1u);
+                break;
+            }
+            s = gbj_next(s, mask);
+        }
+    }
+    gx_wave_count_add(misc + 0, n_ins);
 }
 
 /* ----- two-stage descriptor GROUP BY (gx_groupby_desc_dist) -----
@@ -7487,9 +7804,9 @@ static gx_status gbd_invalid(gx_ctx *ctx, const char *fmt, long a, long b = 0,
  * materialized once */
 struct gbd_inputs {
     devbuf flat[GX_GB_MAX_KEYS + GX_GB_MAX_AGGS + GX_MAX_EXTRA_QUALS +
-                GX_GB_MAX_OPERANDS];
+                GX_GB_MAX_OPERANDS + GX_GBJ_MAX_JOINS];
     devbuf val[GX_GB_MAX_KEYS + GX_GB_MAX_AGGS + GX_MAX_EXTRA_QUALS +
-               GX_GB_MAX_OPERANDS];
+               GX_GB_MAX_OPERANDS + GX_GBJ_MAX_JOINS];
     int nflat = 0;
     std::map<int, gbd_col> done;
 };
@@ -7599,13 +7916,115 @@ static gx_status gbd_plan_ext(gx_ctx *ctx, const gx_gb_ext *ext, const gx_table 
     return GX_OK;
 }
 
+/* the join side of a planned call: on = the JOIN instantiations run (the
+ * ext names a join); b[j] / slots[j] = join j's build arguments and table */
+struct gbj_plan {
+    gbd_jargs jx{};
+    bool on = false;
+    const gx_gbj_ext *ext = nullptr;
+    gbj_build_args b[GX_GBJ_MAX_JOINS] = {};
+    uint64_t nslots[GX_GBJ_MAX_JOINS] = {};
+    gbd_inputs din[GX_GBJ_MAX_JOINS];
+    devbuf slots[GX_GBJ_MAX_JOINS], misc;
+    int64_t dim_rows[GX_GBJ_MAX_JOINS] = {};
+    double ms_build = 0;
+    /* the table side `side` of a key or an aggregate names */
+    const gx_table *table(const gx_table *fact, int side) const
+    { return side == 0 ? fact : ext->joins[side - 1].dim; }
+};
+
+static uint64_t gbj_slots(int64_t dim_rows)
+{
+    return (uint64_t) pow2_at_least(dim_rows * 2);
+}
+
+/* validate a gx_gbj_ext against the tables: the joins, their quals and the
+ * sides; the key and aggregate columns are checked in gbd_plan against the
+ * table their side names */
+static gx_status gbj_plan_ext(gx_ctx *ctx, const gx_gb_desc *d,
+                              const gx_gbj_ext *jext, gbj_plan &jp)
+{
+    const gx_table *t = d->t;
+    if (jext->njoins < 0 || jext->njoins > GX_GBJ_MAX_JOINS)
+        return gbd_invalid(ctx, "njoins %ld outside 0..%ld", jext->njoins,
+                           GX_GBJ_MAX_JOINS);
+    jp.ext = jext;
+    jp.on = jext->njoins > 0;
+    gbd_jargs &jx = jp.jx;
+    jx.njoins = jext->njoins;
+    for (int j = 0; j < jext->njoins; j++)
+    {
+        const gx_gb_join &J = jext->joins[j];
+        if (!J.dim) return gbd_invalid(ctx, "join %ld: no dimension table", j);
+        if (J.dim->nrows >= (int64_t) UINT32_MAX)
+            return gbd_invalid(ctx, "join %ld: a dimension of %ld rows does not fit "
+                                    "the 4-byte join-table slot", j, (long) J.dim->nrows);
+        const int nf = (int) t->cols.size(), nd = (int) J.dim->cols.size();
+        if (J.fact_col < 0 || J.fact_col >= nf)
+            return gbd_invalid(ctx, "join %ld: fact column %ld out of range", j, J.fact_col);
+        if (!gbd_int_width(t->cols[J.fact_col].m.width))
+            return gbd_invalid(ctx, "join %ld: fact column width %ld is not 1, 2, 4 or 8",
+                               j, t->cols[J.fact_col].m.width);
+        if (J.dim_key_col < 0 || J.dim_key_col >= nd)
+            return gbd_invalid(ctx, "join %ld: dimension key column %ld out of range", j,
+                               J.dim_key_col);
+        if (!gbd_int_width(J.dim->cols[J.dim_key_col].m.width))
+            return gbd_invalid(ctx, "join %ld: dimension key column width %ld is not "
+                                    "1, 2, 4 or 8", j, J.dim->cols[J.dim_key_col].m.width);
+        if (J.nquals < 0 || J.nquals > GX_MAX_EXTRA_QUALS)
+            return gbd_invalid(ctx, "join %ld: nquals %ld outside 0..%ld", j, J.nquals,
+                               GX_MAX_EXTRA_QUALS);
+        gbj_build_args &b = jp.b[j];
+        b.nquals = J.nquals;
+        b.nrows = J.dim->nrows;
+        b.vmap = J.dim->dvmap;
+        for (int q = 0; q < J.nquals; q++)
+        {
+            const gx_filter &f = J.quals[q];
+            if (f.col < 0 || f.col >= nd)
+                return gbd_invalid(ctx, "join %ld qual %ld: column %ld out of range", j, q,
+                                   f.col);
+            const int w = J.dim->cols[f.col].m.width;
+            if (!gbd_int_width(w))
+                return gbd_invalid(ctx, "join %ld qual %ld: column width %ld is not "
+                                        "1, 2, 4 or 8", j, q, w);
+            b.qop[q] = f.op;
+            b.qlit[q] = f.literal;
+            if (!gx_fold_filter(w, &b.qop[q], &b.qlit[q]))
+                return gbd_invalid(ctx, "join %ld qual %ld: op %ld outside 0..5", j, q, f.op);
+        }
+        jp.nslots[j] = gbj_slots(J.dim->nrows);
+    }
+    for (int k = 0; k < d->nkeys; k++)
+    {
+        const int side = jext->key_side[k];
+        if (side < 0 || side > jext->njoins)
+            return gbd_invalid(ctx, "key %ld: side %ld outside 0..%ld", k, side,
+                               jext->njoins);
+        jx.key_side[k] = side;
+        if (side) jx.key_joins |= 1u << (side - 1);
+    }
+    for (int j = 0; j < d->naggs; j++)
+    {
+        const int side = jext->agg_side[j];
+        if (side < 0 || side > jext->njoins)
+            return gbd_invalid(ctx, "aggregate %ld: side %ld outside 0..%ld", j, side,
+                               jext->njoins);
+        jx.agg_side[j] = side;
+    }
+    return GX_OK;
+}
+
 /* PLAN: validate the descriptor and fill everything of gbd_args that needs
  * no device memory.  t == nullptr (the combine stage over wire rows) checks
  * and reads nkeys, the aggregates' fn / is_f64 and max_groups only.  ext and
- * xp (both or neither; a table is required) add the expression side. */
+ * xp (both or neither; a table is required) add the expression side, jext
+ * and jp (both or neither; a table is required) the join side: a key or a
+ * column aggregate is then checked against the table its side names. */
 static gx_status gbd_plan(gx_ctx *ctx, const gx_gb_desc *d, const gx_table *t,
                           gbd_args &a, const gx_gb_ext *ext = nullptr,
-                          gbd_xplan *xp = nullptr)
+                          gbd_xplan *xp = nullptr,
+                          const gx_gbj_ext *jext = nullptr, gbj_plan *jp = nullptr)
 {
     const int ncols = t ? (int) t->cols.size() : 0;
     if (d->nkeys < 0 || d->nkeys > GX_GB_MAX_KEYS)
@@ -7622,6 +8041,11 @@ static gx_status gbd_plan(gx_ctx *ctx, const gx_gb_desc *d, const gx_table *t,
         gx_status st = gbd_plan_ext(ctx, ext, t, *xp);
         if (st != GX_OK) return st;
     }
+    if (jext)
+    {
+        gx_status st = gbj_plan_ext(ctx, d, jext, *jp);
+        if (st != GX_OK) return st;
+    }
     a = gbd_args{};
     a.nkeys = d->nkeys; a.naggs = d->naggs; a.nquals = t ? d->nquals : 0;
     a.nrows = t ? t->nrows : 0;
@@ -7630,11 +8054,12 @@ static gx_status gbd_plan(gx_ctx *ctx, const gx_gb_desc *d, const gx_table *t,
     for (int k = 0; t && k < d->nkeys; k++)
     {
         int c = d->key_cols[k];
-        if (c < 0 || c >= ncols)
+        const gx_table *kt = jext ? jp->table(t, jext->key_side[k]) : t;
+        if (c < 0 || c >= (int) kt->cols.size())
             return gbd_invalid(ctx, "key %ld: column %ld out of range", k, c);
-        if (!gbd_int_width(t->cols[c].m.width))
+        if (!gbd_int_width(kt->cols[c].m.width))
             return gbd_invalid(ctx, "key %ld: column width %ld is not 1, 2, 4 or 8",
-                               k, t->cols[c].m.width);
+                               k, kt->cols[c].m.width);
     }
     int words = 0;
     for (int j = 0; j < d->naggs; j++)
@@ -7664,9 +8089,10 @@ static gx_status gbd_plan(gx_ctx *ctx, const gx_gb_desc *d, const gx_table *t,
         int w = ae >= 0 ? 8 : 0;
         if (t && ae < 0)
         {
-            if (g.col < 0 || g.col >= ncols)
+            const gx_table *at = jext ? jp->table(t, jext->agg_side[j]) : t;
+            if (g.col < 0 || g.col >= (int) at->cols.size())
                 return gbd_invalid(ctx, "aggregate %ld: column %ld out of range", j, g.col);
-            w = t->cols[g.col].m.width;
+            w = at->cols[g.col].m.width;
             if (g.is_f64 ? w != 8 : !gbd_int_width(w))
                 return gbd_invalid(ctx, g.is_f64
                                        ? "aggregate %ld: is_f64 on a column of width %ld"
@@ -7732,20 +8158,120 @@ extern "C" int64_t gx_gbd_wire_stride(const gx_gb_desc *d)
 
 /* BIND: flatten every column the plan reads */
 static gx_status gbd_bind(gx_ctx *ctx, const gx_gb_desc *d, gbd_inputs &in,
-                          gbd_args &a, gbd_xplan *xp)
+                          gbd_args &a, gbd_xplan *xp, gbj_plan *jp = nullptr)
 {
     const gx_table *t = d->t;
     const bool ex = xp && xp->on;
+    const bool jn = jp && jp->on;
     gx_status st;
+    /* a dim-side key or aggregate binds the dimension's column */
+    auto bind_side = [&](int side, int col, gbd_col *out) {
+        return side == 0 ? gbd_bind_col(ctx, t, col, in, out)
+                         : gbd_bind_col(ctx, jp->ext->joins[side - 1].dim, col,
+                                        jp->din[side - 1], out);
+    };
     for (int k = 0; k < d->nkeys; k++)
-        if ((st = gbd_bind_col(ctx, t, d->key_cols[k], in, &a.key[k])) != GX_OK) return st;
+        if ((st = bind_side(jn ? jp->jx.key_side[k] : 0, d->key_cols[k],
+                            &a.key[k])) != GX_OK) return st;
     for (int j = 0; j < d->naggs; j++)
         if (d->aggs[j].fn != GX_AGG_COUNT_STAR && !(ex && xp->x.aexpr[j] >= 0) &&
-            (st = gbd_bind_col(ctx, t, d->aggs[j].col, in, &a.agg[j])) != GX_OK) return st;
+            (st = bind_side(jn ? jp->jx.agg_side[j] : 0, d->aggs[j].col,
+                            &a.agg[j])) != GX_OK) return st;
     for (int q = 0; q < d->nquals; q++)
         if ((st = gbd_bind_col(ctx, t, d->quals[q].col, in, &a.qual[q])) != GX_OK) return st;
     for (int o = 0; ex && o < xp->x.nopnd; o++)
         if ((st = gbd_bind_col(ctx, t, xp->opnd_col[o], in, &xp->x.opnd[o])) != GX_OK) return st;
+    for (int j = 0; jn && j < jp->jx.njoins; j++)
+    {
+        const gx_gb_join &J = jp->ext->joins[j];
+        if ((st = gbd_bind_col(ctx, t, J.fact_col, in, &jp->jx.j[j].fact)) != GX_OK ||
+            (st = gbd_bind_col(ctx, J.dim, J.dim_key_col, jp->din[j],
+                               &jp->jx.j[j].dkey)) != GX_OK)
+            return st;
+        jp->b[j].key = jp->jx.j[j].dkey;
+        for (int q = 0; q < J.nquals; q++)
+            if ((st = gbd_bind_col(ctx, J.dim, J.quals[q].col, jp->din[j],
+                                   &jp->b[j].qual[q])) != GX_OK) return st;
+    }
+    return GX_OK;
+}
+
+/* bytes a join scan allocates beside the group table: the join tables and the
+ * flat copies (value and validity bytes) gbd_bind materialises for format-1
+ * dimension columns; for the budget check before anything is bound */
+static uint64_t gbj_bytes(const gx_gb_desc *d, const gbd_xplan *xp, const gbj_plan *jp)
+{
+    if (!jp || !jp->on) return 0;
+    uint64_t b = 64;
+    std::set<std::pair<int, int>> seen;
+    auto col = [&](int j, int c) {
+        const gx_table *dim = jp->ext->joins[j].dim;
+        if (dim->cols[c].format != 0 && seen.insert({j, c}).second)
+            b += GX_AOCS_DATUM_OFF + (uint64_t) std::max<int64_t>(dim->nrows, 1) *
+                                         (uint64_t) (dim->cols[c].m.width + 1);
+    };
+    for (int j = 0; j < jp->jx.njoins; j++)
+    {
+        b += jp->nslots[j] * 4;
+        col(j, jp->ext->joins[j].dim_key_col);
+        for (int q = 0; q < jp->ext->joins[j].nquals; q++)
+            col(j, jp->ext->joins[j].quals[q].col);
+    }
+    for (int k = 0; k < d->nkeys; k++)
+        if (jp->jx.key_side[k]) col(jp->jx.key_side[k] - 1, d->key_cols[k]);
+    for (int j = 0; j < d->naggs; j++)
+        if (jp->jx.agg_side[j] && d->aggs[j].fn != GX_AGG_COUNT_STAR &&
+            !(xp && xp->on && xp->x.aexpr[j] >= 0))
+            col(jp->jx.agg_side[j] - 1, d->aggs[j].col);
+    return b;
+}
+
+/* BUILD the join tables of a bound plan and report a duplicate key among the
+ * participating rows of a dimension (one host sync) */
+static gx_status gbj_build(gx_ctx *ctx, gbj_plan &jp)
+{
+    hipStream_t s = ctx->stream;
+    const int nj = jp.jx.njoins;
+    evholder e0, e1;
+    HIP_CHK(ctx, e0.create()); HIP_CHK(ctx, e1.create());
+    HIP_CHK(ctx, jp.misc.alloc(32 * GX_GBJ_MAX_JOINS));
+    HIP_CHK(ctx, hipMemsetAsync(jp.misc.p, 0, 32 * GX_GBJ_MAX_JOINS, s));
+    for (int j = 0; j < nj; j++)
+    {
+        HIP_CHK(ctx, jp.slots[j].alloc(jp.nslots[j] * 4));
+        HIP_CHK(ctx, hipMemsetAsync(jp.slots[j].p, 0, jp.nslots[j] * 4, s));
+    }
+    HIP_CHK(ctx, hipEventRecord(e0, s));
+    for (int j = 0; j < nj; j++)
+    {
+        const int grid = (int) std::max<int64_t>(
+            1, std::min<int64_t>(GRID, (jp.b[j].nrows + TPB - 1) / TPB));
+        hipLaunchKernelGGL(k_gbj_build, dim3(grid), dim3(TPB), 0, s, jp.b[j],
+                           jp.slots[j].as<uint32_t>(), jp.nslots[j] - 1,
+                           jp.misc.as<unsigned long long>() + 4 * j);
+        jp.jx.j[j].slots = jp.slots[j].as<uint32_t>();
+        jp.jx.j[j].mask = jp.nslots[j] - 1;
+    }
+    HIP_CHK(ctx, hipEventRecord(e1, s));
+    unsigned long long hm[4 * GX_GBJ_MAX_JOINS] = {};
+    HIP_CHK(ctx, hipMemcpyAsync(hm, jp.misc.p, sizeof hm, hipMemcpyDeviceToHost, s));
+    HIP_CHK(ctx, hipStreamSynchronize(s));
+    HIP_CHK(ctx, hipGetLastError());
+    float ms = 0;
+    (void) hipEventElapsedTime(&ms, e0, e1);
+    jp.ms_build = (double) ms;
+    for (int j = 0; j < nj; j++)
+    {
+        if (hm[4 * j + 1] & 1)
+        {
+            char buf[120];
+            snprintf(buf, sizeof buf, "join %d: duplicate dimension key %lld among the "
+                                      "rows that take part", j, (long long) hm[4 * j + 2]);
+            set_err(ctx, "groupby_desc: %s", buf);
+            return GX_ERR_INVALID;
+        }
+        jp.dim_rows[j] = (int64_t) hm[4 * j];
+    }
     return GX_OK;
 }
 
@@ -7763,7 +8289,8 @@ static uint64_t gbd_operand_flat_bytes(const gx_table *t, const gbd_xplan *xp)
 /* one aggregation table on the device and its compacted groups: the scan's
  * over input rows, or the combine stage's over wire rows */
 struct gbd_table {
-    devbuf trow, tacc, misc;       /* misc: [0..1] stats, [2] cursor, [3] err */
+    devbuf trow, tacc, misc;       /* misc: [0..1] stats, [2] cursor, [3] err,
+                                      [4] a join scan's probed rows */
     devbuf okeys, oknull, oacc;    /* compacted groups, SoA, up to bound */
     uint64_t tslots = 0;
     int64_t bound = 0;
@@ -7797,13 +8324,13 @@ static gx_status gbd_table_alloc(gx_ctx *ctx, gbd_table &T, const gbd_args &a,
     T.sw = wide ? 8 : 4;
     HIP_CHK(ctx, T.trow.alloc(T.tslots * T.sw));
     HIP_CHK(ctx, T.tacc.alloc(T.tslots * (size_t) words * 8));
-    HIP_CHK(ctx, T.misc.alloc(32));
+    HIP_CHK(ctx, T.misc.alloc(40));
     HIP_CHK(ctx, T.okeys.alloc((size_t) bound * std::max(nk, 1) * 8));
     HIP_CHK(ctx, T.oknull.alloc((size_t) bound * std::max(nk, 1)));
     HIP_CHK(ctx, T.oacc.alloc((size_t) bound * words * 8));
     HIP_CHK(ctx, hipMemsetAsync(T.trow.p, 0, T.tslots * T.sw, s));
     HIP_CHK(ctx, hipMemsetAsync(T.tacc.p, 0, T.tslots * (size_t) words * 8, s));
-    HIP_CHK(ctx, hipMemsetAsync(T.misc.p, 0, 32, s));
+    HIP_CHK(ctx, hipMemsetAsync(T.misc.p, 0, 40, s));
     /* a plain aggregate's one group is all-identity until the extract writes
      * it: the state row the two-stage plan ships for an empty shard */
     if (nk == 0)
@@ -7833,7 +8360,8 @@ static void gbd_extract(gx_ctx *ctx, const gbd_args &a, const SRC &src, gbd_tabl
 static gx_status gbd_scan_stage(gx_ctx *ctx, const gx_gb_desc *d, gbd_args &a,
                                 gbd_inputs &in, gbd_table &T, int grid, bool wide,
                                 bool lds, uint64_t extra, hipEvent_t e0,
-                                hipEvent_t e1, gbd_xplan *xp = nullptr)
+                                hipEvent_t e1, gbd_xplan *xp = nullptr,
+                                gbj_plan *jp = nullptr)
 {
     if (grid < 1) return gbd_invalid(ctx, "grid %ld", grid);
     /* sizing: the table holds up to `bound` groups */
@@ -7842,11 +8370,15 @@ static gx_status gbd_scan_stage(gx_ctx *ctx, const gx_gb_desc *d, gbd_args &a,
         1, d->max_groups > 0 ? std::min<int64_t>(d->max_groups, n) : n);
     if (!wide && n >= (int64_t) UINT32_MAX)
         return gbd_invalid(ctx, "%ld rows need the 8-byte slot word", (long) n);
+    const bool jn = jp && jp->on;
     gx_status st = gbd_table_budget(ctx, a, bound, wide,
-                                    extra + gbd_operand_flat_bytes(d->t, xp),
-                                    "groupby_desc table");
+                                    extra + gbd_operand_flat_bytes(d->t, xp) +
+                                        gbj_bytes(d, xp, jp),
+                                    jn ? "groupby_desc table and join tables"
+                                       : "groupby_desc table");
     if (st != GX_OK) return st;
-    if ((st = gbd_bind(ctx, d, in, a, xp)) != GX_OK) return st;
+    if ((st = gbd_bind(ctx, d, in, a, xp, jp)) != GX_OK) return st;
+    if (jn && (st = gbj_build(ctx, *jp)) != GX_OK) return st;
     if ((st = gbd_table_alloc(ctx, T, a, bound, wide)) != GX_OK) return st;
     hipStream_t s = ctx->stream;
     const size_t lds_bytes = lds ? (size_t) a.lds_slots * ((size_t) a.awords * 8 + T.sw) : 0;
@@ -7854,19 +8386,25 @@ static gx_status gbd_scan_stage(gx_ctx *ctx, const gx_gb_desc *d, gbd_args &a,
     by_width((int) T.sw, T.trow.p, [&](auto *rows) {
         by_flag(lds, [&](auto use_lds) {
             by_flag(xp && xp->on, [&](auto use_expr) {
-                constexpr bool EX = decltype(use_expr)::value;
-                std::conditional_t<EX, gbd_xargs, gbd_noexpr> x{};
-                if constexpr (EX) x = xp->x;
-                hipLaunchKernelGGL((k_groupby_desc<std::decay_t<decltype(*rows)>,
-                                                   decltype(use_lds)::value, EX>),
-                                   dim3(grid), dim3(TPB), lds_bytes, s, a, x, rows,
-                                   T.tacc.as<unsigned long long>(), T.tslots - 1,
-                                   T.stat(), T.err());
+                by_flag(jn, [&](auto use_join) {
+                    constexpr bool EX = decltype(use_expr)::value;
+                    constexpr bool JN = decltype(use_join)::value;
+                    std::conditional_t<EX, gbd_xargs, gbd_noexpr> x{};
+                    std::conditional_t<JN, gbd_jargs, gbd_nojoin> jx{};
+                    if constexpr (EX) x = xp->x;
+                    if constexpr (JN) jx = jp->jx;
+                    hipLaunchKernelGGL((k_groupby_desc<std::decay_t<decltype(*rows)>,
+                                                       decltype(use_lds)::value, EX, JN>),
+                                       dim3(grid), dim3(TPB), lds_bytes, s, a, x, jx,
+                                       rows, T.tacc.as<unsigned long long>(),
+                                       T.tslots - 1, T.stat(), T.err());
+                });
             });
         });
     });
     if (e1) HIP_CHK(ctx, hipEventRecord(e1, s));
-    gbd_extract(ctx, a, gbd_key_cols{}, T);
+    if (jn) gbd_extract(ctx, a, gbd_key_join_args{jp->jx}, T);
+    else gbd_extract(ctx, a, gbd_key_cols{}, T);
     return GX_OK;
 }
 
@@ -7983,19 +8521,23 @@ static gx_status gbd_check_call(gx_ctx *ctx, const gx_gb_desc *d, gx_gb_result *
  * so the public call and the test entry run the same launches. */
 static gx_status gbd_run(gx_ctx *ctx, const gx_gb_desc *d, int grid, bool wide,
                          bool lds, gx_gb_result *out, gx_gbd_stats *stats,
-                         const gx_gb_ext *ext = nullptr)
+                         const gx_gb_ext *ext = nullptr,
+                         const gx_gbj_ext *jext = nullptr,
+                         gx_gbj_stats *jstats = nullptr)
 {
     gx_status st = gbd_check_call(ctx, d, out);
     if (stats) memset(stats, 0, sizeof *stats);
+    if (jstats) memset(jstats, 0, sizeof *jstats);
     if (st != GX_OK) return st;
     gbd_args a;
     gbd_xplan xp;
-    if ((st = gbd_plan(ctx, d, d->t, a, ext, &xp)) != GX_OK) return st;
+    gbj_plan jp;
+    if ((st = gbd_plan(ctx, d, d->t, a, ext, &xp, jext, &jp)) != GX_OK) return st;
     gbd_inputs in;
     gbd_table T;
     evholder e0, e1;
     HIP_CHK(ctx, e0.create()); HIP_CHK(ctx, e1.create());
-    st = gbd_scan_stage(ctx, d, a, in, T, grid, wide, lds, 0, e0, e1, &xp);
+    st = gbd_scan_stage(ctx, d, a, in, T, grid, wide, lds, 0, e0, e1, &xp, &jp);
     if (st != GX_OK) return st;
     const int64_t n = d->t->nrows;
     unsigned long long hm[4] = {0, 0, 0, 0};
@@ -8012,6 +8554,24 @@ static gx_status gbd_run(gx_ctx *ctx, const gx_gb_desc *d, int grid, bool wide,
         stats->rows_lds = (int64_t) hm[1];
         stats->rows_global = (int64_t) (hm[0] - hm[1]);
         stats->groups = out->ngroups;
+    }
+    if (jstats)
+    {
+        float ms = 0;
+        (void) hipEventElapsedTime(&ms, e0, e1);
+        /* without a join every row the quals leave "reaches the probes" */
+        unsigned long long probed = hm[0];
+        if (jp.on)
+            HIP_CHK(ctx, hipMemcpy(&probed, T.stat() + 4, 8, hipMemcpyDeviceToHost));
+        jstats->ms_build = jp.ms_build;
+        jstats->ms_kernel = (double) ms;
+        jstats->rows_in = n;
+        jstats->rows_probed = (int64_t) probed;
+        jstats->rows_pass = (int64_t) hm[0];
+        jstats->rows_lds = (int64_t) hm[1];
+        jstats->rows_global = (int64_t) (hm[0] - hm[1]);
+        jstats->groups = out->ngroups;
+        for (int j = 0; j < jp.jx.njoins; j++) jstats->dim_rows[j] = jp.dim_rows[j];
     }
     return GX_OK;
 }
@@ -8053,15 +8613,53 @@ extern "C" gx_status gx_test_groupby_expr(gx_ctx *ctx, const gx_gb_desc *d,
                    ext);
 }
 
+/* the join entry points need their join descriptor */
+static gx_status gbj_check_call(gx_ctx *ctx, const gx_gbj_ext *jext, gx_gb_result *out)
+{
+    if (!ctx || jext) return GX_OK;               /* no ctx: gbd_check_call answers */
+    if (out) memset(out, 0, sizeof *out);
+    set_err(ctx, "groupby_desc: no join descriptor%s", "");
+    return GX_ERR_INVALID;
+}
+
+extern "C" gx_status gx_groupby_join(gx_ctx *ctx, const gx_gb_desc *d,
+                                     const gx_gbj_ext *jext, const gx_gb_ext *ext,
+                                     gx_gb_result *out, gx_gbj_stats *stats)
+{
+    gx_status st = gbj_check_call(ctx, jext, out);
+    if (st != GX_OK) return st;
+    bool wide = d && d->t && d->t->nrows >= (int64_t) UINT32_MAX;
+    return gbd_run(ctx, d, GRID, wide, gbd_env_lds(), out, nullptr, ext, jext, stats);
+}
+
+extern "C" gx_status gx_test_groupby_join(gx_ctx *ctx, const gx_gb_desc *d,
+                                          const gx_gbj_ext *jext,
+                                          const gx_gb_ext *ext, int grid,
+                                          int wide_rowid, gx_gb_result *out,
+                                          gx_gbj_stats *stats)
+{
+    gx_status st = gbj_check_call(ctx, jext, out);
+    if (st != GX_OK) return st;
+    bool wide = wide_rowid != 0 ||
+                (d && d->t && d->t->nrows >= (int64_t) UINT32_MAX);
+    return gbd_run(ctx, d, grid == 0 ? GRID : grid, wide, gbd_env_lds(), out, nullptr,
+                   ext, jext, stats);
+}
+
 /* ---- two-stage descriptor GROUP BY: host side ----
  * (kernels: k_gbd_part_hist, k_gbd_part_emit, k_gbd_combine) */
 
-/* bit k set: key column k is 8 bytes wide (hashint8; the others hashint4) */
-static unsigned gbd_wide_mask(const gx_gb_desc *d)
+/* bit k set: key column k is 8 bytes wide (hashint8; the others hashint4); a
+ * dim-side key takes its width from the dimension's column */
+static unsigned gbd_wide_mask(const gx_gb_desc *d, const gx_gbj_ext *jext = nullptr)
 {
     unsigned m = 0;
     for (int k = 0; k < d->nkeys; k++)
-        if (d->t->cols[d->key_cols[k]].m.width == 8) m |= 1u << k;
+    {
+        const gx_table *kt = jext && jext->key_side[k] > 0
+                                 ? jext->joins[jext->key_side[k] - 1].dim : d->t;
+        if (kt->cols[d->key_cols[k]].m.width == 8) m |= 1u << k;
+    }
     return m;
 }
 
@@ -8141,7 +8739,7 @@ static gx_status gbd_partial_failed(gx_ctx *ctx)
 
 static gx_status gbd_run_dist(gx_ctx *ctx, const gx_gb_desc *d,
                               const gx_gb_ext *ext, gx_gb_result *out,
-                              gx_gb_stats *stats)
+                              gx_gb_stats *stats, const gx_gbj_ext *jext = nullptr)
 {
     gx_status st = gbd_check_call(ctx, d, out);
     if (stats) memset(stats, 0, sizeof *stats);
@@ -8156,7 +8754,7 @@ static gx_status gbd_run_dist(gx_ctx *ctx, const gx_gb_desc *d,
     if (ctx->nsegs == 1 && env_int("GX_FORCE_MOTION", 0) == 0)
     {
         gx_gbd_stats one{};
-        st = gbd_run(ctx, d, GRID, wide, gbd_env_lds(), out, &one, ext);
+        st = gbd_run(ctx, d, GRID, wide, gbd_env_lds(), out, &one, ext, jext);
         if (st != GX_OK) return st;
         S.ms_partial = one.ms_kernel;
         S.partial_groups = S.final_groups = out->ngroups;
@@ -8165,7 +8763,8 @@ static gx_status gbd_run_dist(gx_ctx *ctx, const gx_gb_desc *d,
     }
     gbd_args a;
     gbd_xplan xp;
-    if ((st = gbd_plan(ctx, d, t, a, ext, &xp)) != GX_OK) return st;
+    gbj_plan jp;
+    if ((st = gbd_plan(ctx, d, t, a, ext, &xp, jext, &jp)) != GX_OK) return st;
     if (!ctx->comm)
     { set_err(ctx, "nsegs>1 but gx_comm_init not called%s", ""); return GX_ERR_STATE; }
     const int n = ctx->nsegs;
@@ -8188,7 +8787,7 @@ static gx_status gbd_run_dist(gx_ctx *ctx, const gx_gb_desc *d,
     const uint64_t side = (uint64_t) std::max<int64_t>(t->nrows, 1) * 2 +
                           (uint64_t) n * (n + 2) * 8;
     st = gbd_scan_stage(ctx, d, a, in, T, GRID, wide, gbd_env_lds(), side, ev[0],
-                        nullptr, &xp);
+                        nullptr, &xp, &jp);
     if (st != GX_OK) return st;
     HIP_CHK(ctx, hipEventRecord(ev[1], s));
 
@@ -8202,7 +8801,7 @@ static gx_status gbd_run_dist(gx_ctx *ctx, const gx_gb_desc *d,
     HIP_CHK(ctx, dest_b.alloc((size_t) T.bound * 2));
     unsigned long long *dhist = hist_b.as<unsigned long long>();
     HIP_CHK(ctx, hipMemsetAsync(dhist, 0, (size_t) n * 8, s));
-    gbd_part_hist(ctx, a, T, gbd_wide_mask(d), n, dest_b.as<uint16_t>(), dhist);
+    gbd_part_hist(ctx, a, T, gbd_wide_mask(d, jext), n, dest_b.as<uint16_t>(), dhist);
     HIP_CHK(ctx, hipEventRecord(ev[2], s));
     RCCL_CHK(ctx, ncclAllGather(dhist, all_b.p, n, ncclUint64, ctx->comm, s));
     std::vector<unsigned long long> cnts_all((size_t) n * n);
@@ -8271,12 +8870,22 @@ extern "C" gx_status gx_groupby_expr_dist(gx_ctx *ctx, const gx_gb_desc *d,
     return gbd_run_dist(ctx, d, ext, out, stats);
 }
 
+extern "C" gx_status gx_groupby_join_dist(gx_ctx *ctx, const gx_gb_desc *d,
+                                          const gx_gbj_ext *jext,
+                                          const gx_gb_ext *ext, gx_gb_result *out,
+                                          gx_gb_stats *stats)
+{
+    gx_status st = gbj_check_call(ctx, jext, out);
+    if (st != GX_OK) return st;
+    return gbd_run_dist(ctx, d, ext, out, stats, jext);
+}
+
 /* Test ABI: partial agg + partition kernels on one GPU for a given nsegs,
- * through the launch helpers of gx_groupby_desc_dist */
-extern "C" gx_status gx_test_gbd_partial(gx_ctx *ctx, const gx_gb_desc *d,
-                                         int nsegs, int64_t *out_counts,
-                                         void *out_rows, int64_t cap_rows,
-                                         int64_t *out_total)
+ * through the launch helpers of gx_groupby_desc_dist; jext: the join form */
+static gx_status gbd_test_partial(gx_ctx *ctx, const gx_gb_desc *d,
+                                  const gx_gbj_ext *jext, int nsegs,
+                                  int64_t *out_counts, void *out_rows,
+                                  int64_t cap_rows, int64_t *out_total)
 {
     if (!ctx || !d || !out_counts || !out_total || cap_rows < 0 ||
         (cap_rows > 0 && !out_rows))
@@ -8285,7 +8894,8 @@ extern "C" gx_status gx_test_gbd_partial(gx_ctx *ctx, const gx_gb_desc *d,
     if (nsegs < 1 || nsegs > GB_MAX_SEGS)
         return gbd_invalid(ctx, "nsegs %ld outside 1..%ld", nsegs, GB_MAX_SEGS);
     gbd_args a;
-    gx_status st = gbd_plan(ctx, d, d->t, a);
+    gbj_plan jp;
+    gx_status st = gbd_plan(ctx, d, d->t, a, nullptr, nullptr, jext, &jp);
     if (st != GX_OK) return st;
     hipStream_t s = ctx->stream;
     const bool wide = d->t->nrows >= (int64_t) UINT32_MAX;
@@ -8294,14 +8904,14 @@ extern "C" gx_status gx_test_gbd_partial(gx_ctx *ctx, const gx_gb_desc *d,
     const uint64_t side = (uint64_t) std::max<int64_t>(d->t->nrows, 1) * 2 +
                           (uint64_t) nsegs * 16;
     st = gbd_scan_stage(ctx, d, a, in, T, GRID, wide, gbd_env_lds(), side, nullptr,
-                        nullptr);
+                        nullptr, nullptr, &jp);
     if (st != GX_OK) return st;
     devbuf hist_b, cur_b, dest_b, send_b;
     HIP_CHK(ctx, hist_b.alloc((size_t) nsegs * 8));
     HIP_CHK(ctx, cur_b.alloc((size_t) nsegs * 8));
     HIP_CHK(ctx, dest_b.alloc((size_t) T.bound * 2));
     HIP_CHK(ctx, hipMemsetAsync(hist_b.p, 0, (size_t) nsegs * 8, s));
-    gbd_part_hist(ctx, a, T, gbd_wide_mask(d), nsegs, dest_b.as<uint16_t>(),
+    gbd_part_hist(ctx, a, T, gbd_wide_mask(d, jext), nsegs, dest_b.as<uint16_t>(),
                   hist_b.as<unsigned long long>());
     std::vector<unsigned long long> h(nsegs), off(nsegs + 1, 0);
     unsigned long long hm[4] = {0, 0, 0, 0};
@@ -8332,6 +8942,26 @@ extern "C" gx_status gx_test_gbd_partial(gx_ctx *ctx, const gx_gb_desc *d,
     for (int i = 0; i < nsegs; i++) out_counts[i] = (int64_t) h[i];
     *out_total = total;
     return GX_OK;
+}
+
+extern "C" gx_status gx_test_gbd_partial(gx_ctx *ctx, const gx_gb_desc *d,
+                                         int nsegs, int64_t *out_counts,
+                                         void *out_rows, int64_t cap_rows,
+                                         int64_t *out_total)
+{
+    return gbd_test_partial(ctx, d, nullptr, nsegs, out_counts, out_rows, cap_rows,
+                            out_total);
+}
+
+extern "C" gx_status gx_test_gbj_partial(gx_ctx *ctx, const gx_gb_desc *d,
+                                         const gx_gbj_ext *jext, int nsegs,
+                                         int64_t *out_counts, void *out_rows,
+                                         int64_t cap_rows, int64_t *out_total)
+{
+    gx_status st = gbj_check_call(ctx, jext, nullptr);
+    if (st != GX_OK) return st;
+    return gbd_test_partial(ctx, d, jext, nsegs, out_counts, out_rows, cap_rows,
+                            out_total);
 }
 
 /* Test ABI: the combine stage over host-supplied wire rows */
@@ -8414,6 +9044,54 @@ extern "C" int gx_selftest_expr_eval(const gx_expr *ex, const double *vals,
     return 0;
 }
 
+/* host restatement of the join table through gbj_home / gbj_next /
+ * gbj_key_eq / gbj_probe, which k_gbj_build and the scan kernel call */
+struct gbj_host_key {
+    const int64_t *k;
+    int64_t operator()(int64_t r) const { return k[r]; }
+};
+
+extern "C" int64_t gx_selftest_gbj_join(const int64_t *dim_keys, const uint8_t *dim_null,
+                                        int64_t ndim, const int64_t *fact_keys,
+                                        const uint8_t *fact_null, int64_t nfact,
+                                        int64_t *out_row, int64_t *dup_key)
+{
+    if (ndim < 0 || nfact < 0 || ndim >= (int64_t) UINT32_MAX || !dup_key ||
+        (ndim > 0 && !dim_keys) || (nfact > 0 && (!fact_keys || !out_row)))
+        return -1;
+    const uint64_t mask = gbj_slots(ndim) - 1;
+    std::vector<uint32_t> slots(mask + 1, 0u);
+    for (int64_t i = 0; i < ndim; i++)
+    {
+        if (dim_null && dim_null[i]) continue;
+        uint64_t s = gbj_home(dim_keys[i], mask);
+        for (;;)
+        {
+            const uint32_t cur = slots[s];
+            if (cur == 0u) { slots[s] = (uint32_t) (i + 1); break; }
+            if (gbj_key_eq(dim_keys[cur - 1], dim_keys[i]))
+            { *dup_key = dim_keys[i]; return 1; }
+            s = gbj_next(s, mask);
+        }
+    }
+    for (int64_t f = 0; f < nfact; f++)
+        out_row[f] = (fact_null && fact_null[f])
+                         ? -1
+                         : gbj_probe(slots.data(), mask, fact_keys[f],
+                                     gbj_host_key{dim_keys});
+    return 0;
+}
+
+extern "C" int64_t gx_selftest_gbj_slots(const int64_t *keys, int64_t n, int64_t ndim,
+                                         uint32_t *out)
+{
+    if (n < 0 || ndim < 0 || ndim >= (int64_t) UINT32_MAX || (n > 0 && (!keys || !out)))
+        return -1;
+    const uint64_t mask = gbj_slots(ndim) - 1;
+    for (int64_t i = 0; i < n; i++) out[i] = (uint32_t) gbj_home(keys[i], mask);
+    return (int64_t) (mask + 1);
+}
+
 extern "C" int gx_selftest_fqual(int op, double x, double literal)
 {
     if (op < 0 || op > 5) return -1;
@@ -8427,8 +9105,8 @@ extern "C" int gx_selftest_fqual(int op, double x, double literal)
  * mirrors (ctypes tests; the PG extension's abi-check compiles against the
  * real header instead).  kind: 0 stats, 1 group, 2 kv_group, 3 desc,
  * 4 coldesc, 5 filter, 6 gb_stats, 7 test_tbl_layout, 8 gb_desc,
- * 9 gb_result, 10 agg, 11 gbd_stats, 13 gb_ext, 14 expr, 15 fqual; 12 is
- * unassigned and stays -1. */
+ * 9 gb_result, 10 agg, 11 gbd_stats, 13 gb_ext, 14 expr, 15 fqual,
+ * 16 gb_join, 17 gbj_ext, 18 gbj_stats; 12 is unassigned and stays -1. */
 extern "C" int64_t gx_abi_sizeof(int kind)
 {
     switch (kind)
@@ -8448,6 +9126,9 @@ extern "C" int64_t gx_abi_sizeof(int kind)
         case 13: return (int64_t) sizeof(gx_gb_ext);
         case 14: return (int64_t) sizeof(gx_expr);
         case 15: return (int64_t) sizeof(gx_fqual);
+        case 16: return (int64_t) sizeof(gx_gb_join);
+        case 17: return (int64_t) sizeof(gx_gbj_ext);
+        case 18: return (int64_t) sizeof(gx_gbj_stats);
         default: return -1;
     }
 }

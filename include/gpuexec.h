@@ -351,7 +351,8 @@ void gx_free(void *p);
 /* ABI self-description for foreign mirrors (0 stats, 1 q3_group,
  * 2 kv_group, 3 q3_desc, 4 coldesc, 5 filter, 6 gb_stats,
  * 7 test_tbl_layout, 8 gb_desc, 9 gb_result, 10 agg, 11 gbd_stats,
- * 13 gb_ext, 14 expr, 15 fqual); -1 for unknown kinds.  Kind 12 is left
+ * 13 gb_ext, 14 expr, 15 fqual, 16 gb_join, 17 gbj_ext, 18 gbj_stats); -1
+ * for unknown kinds.  Kind 12 is left
  * unassigned on purpose and stays -1: the suite pins it as an unknown kind. */
 int64_t gx_abi_sizeof(int kind);
 
@@ -574,6 +575,90 @@ gx_status gx_groupby_expr(gx_ctx *, const gx_gb_desc *, const gx_gb_ext * /* may
 gx_status gx_groupby_expr_dist(gx_ctx *, const gx_gb_desc *, const gx_gb_ext * /* may be NULL */,
                                gx_gb_result *out, gx_gb_stats *stats /* may be NULL */);
 
+/* ---- descriptor GROUP BY over a join: the scanned table desc->t is the fact
+ * side of up to GX_GBJ_MAX_JOINS inner equi-joins against dimension tables,
+ * and a group key column or a column aggregate's argument may come from the
+ * matched dimension row ("fact JOIN dim GROUP BY dim.attr").  nodeHashjoin.c
+ * inner-join semantics over execScan.c quals, feeding nodeAgg.c.  The
+ * descriptor, gx_gb_ext, the result struct, the result order, max_groups, the
+ * error style and gx_gbd_wire_stride are those of gx_groupby_desc /
+ * gx_groupby_expr; the join items travel in gx_gbj_ext beside them.
+ *
+ * Join matching: join j is t.fact_col = dim.dim_key_col, an inner join.  Both
+ *   are integer columns of width 1, 2, 4 or 8 (format 0 or 1) and may differ
+ *   in width: both sides are sign-extended to int64 and compared, the
+ *   mathematically correct cross-type equality (int48eq and kin).  The
+ *   operator is strict: a fact row whose join column is NULL matches nothing
+ *   and is dropped, a dimension row whose key is NULL is never matched.
+ * Rows: a dimension row takes part only if its visimap bit is off and all of
+ *   its join's quals pass (folded as gx_filter describes; a NULL qual input
+ *   fails).  A fact row contributes if its visimap bit is off, the
+ *   descriptor's quals and the ext's fquals pass, and EVERY join finds its
+ *   row.  rows_probed counts the rows that reached the probes (visimap, quals
+ *   and fquals passed), rows_pass those that also matched every join.
+ * Unique dimension keys: among the dimension rows that take part, keys must
+ *   be unique; this executor does not multiply rows.  A duplicate is
+ *   GX_ERR_INVALID, and gx_last_error names the join and one duplicated key
+ *   value.  Duplicates among rows the quals or the visimap remove are legal.
+ * Keys and aggregates from a dimension: key_side[k] = 0 reads key_cols[k]
+ *   from desc->t as before; key_side[k] = j + 1 makes key k the value (or
+ *   NULL) of column key_cols[k] of joins[j].dim at the matched row.  Grouping
+ *   stays NOT DISTINCT per column: a NULL attribute forms its own group, every
+ *   int64 value is a legal key.  agg_side[j] likewise says which table
+ *   aggs[j].col indexes; widths, is_f64, strictness and the NULL result rule
+ *   are unchanged.  COUNT(*) counts joined rows.  Expression operands, fquals
+ *   and the descriptor's quals name columns of the fact table only and have no
+ *   side tag.
+ * Degenerate inputs: nkeys == 0 gives exactly one group, also when nothing
+ *   joins (COUNT 0, the rest NULL).  With keys, an empty fact table, an empty
+ *   dimension or a dimension whose quals remove everything gives zero groups.
+ *   njoins == 0 with every side 0 is exactly gx_groupby_expr: the same kernel
+ *   instantiations, result bytes and error texts.
+ * Errors: GX_ERR_INVALID names the item in gx_last_error: njoins out of
+ *   range, a NULL dim, a side outside 0..njoins, a column out of range in the
+ *   table its side names, a width that is not 1, 2, 4 or 8, a join qual op
+ *   outside 0..5, a dimension of 2^32 - 1 rows or more (a join-table slot is a
+ *   u32 holding row + 1).  The context stays usable.  The HBM budget check
+ *   runs before anything is allocated and includes the join tables (4 bytes
+ *   per slot, a power of two of at least 2 x the dimension's rows) and the
+ *   flat materialisations of format-1 dimension columns (GX_ERR_OOM).
+ * gx_groupby_join_dist: every segment is taken to hold each dimension
+ *   COMPLETE (a replicated table, a Broadcast Motion done by the caller, or a
+ *   dimension co-located with fact_col); this call moves no dimension rows.
+ *   Otherwise it is gx_groupby_expr_dist: the scan is the partial stage,
+ *   partition, exchange and combine are unchanged, and a dim-side key routes
+ *   by the width of the DIMENSION's column (hashint8 for width 8, hashint4
+ *   below).
+ * Not supported (DESIGN.md "Descriptor GROUP BY: joins"): outer, semi and
+ *   anti joins, non-unique dimension keys, joins of dimensions to dimensions,
+ *   dimension columns as expression operands or fqual inputs.
+ * Not verified: more than one rank; dimensions near 2^32 rows. ---- */
+#define GX_GBJ_MAX_JOINS 2
+typedef struct gx_gb_join {
+    const gx_table *dim;
+    int32_t fact_col;      /* integer column of desc->t, width 1, 2, 4 or 8 */
+    int32_t dim_key_col;   /* integer column of dim, width 1, 2, 4 or 8 */
+    int32_t nquals, _pad;
+    gx_filter quals[GX_MAX_EXTRA_QUALS];   /* AND-ed, over dim's integer/date columns */
+} gx_gb_join;
+typedef struct gx_gbj_ext {
+    int32_t njoins, _pad;                  /* 0..GX_GBJ_MAX_JOINS */
+    gx_gb_join joins[GX_GBJ_MAX_JOINS];
+    int32_t key_side[GX_GB_MAX_KEYS];      /* 0 = desc->t; j + 1 = joins[j].dim */
+    int32_t agg_side[GX_GB_MAX_AGGS];      /* same; key_cols[k] / aggs[j].col index that table */
+} gx_gbj_ext;
+typedef struct gx_gbj_stats {
+    double  ms_build, ms_kernel;           /* join-table builds; scan kernel alone */
+    int64_t rows_in, rows_probed, rows_pass, rows_lds, rows_global, groups;
+    int64_t dim_rows[GX_GBJ_MAX_JOINS];    /* rows each join table holds */
+} gx_gbj_stats;
+gx_status gx_groupby_join(gx_ctx *, const gx_gb_desc *, const gx_gbj_ext *,
+                          const gx_gb_ext * /* may be NULL */,
+                          gx_gb_result *out, gx_gbj_stats * /* may be NULL */);
+gx_status gx_groupby_join_dist(gx_ctx *, const gx_gb_desc *, const gx_gbj_ext *,
+                               const gx_gb_ext * /* may be NULL */,
+                               gx_gb_result *out, gx_gb_stats * /* may be NULL */);
+
 /* ---- test-only entry points (parity harness; not part of the drop-in) ---- */
 /* gx_groupby_desc through the same launch helper with the scan grid and the
  * slot word chosen by the caller: grid = 0 is production (2048 workgroups),
@@ -597,6 +682,30 @@ int gx_selftest_expr_eval(const gx_expr *, const double *vals,
                           const uint8_t *isnull, int64_t n, int ncols,
                           double *out, uint8_t *out_null);
 int gx_selftest_fqual(int op, double x, double literal);
+/* gx_groupby_join through the same seam (grid, wide_rowid as above) */
+gx_status gx_test_groupby_join(gx_ctx *, const gx_gb_desc *, const gx_gbj_ext *,
+                               const gx_gb_ext *, int grid, int wide_rowid,
+                               gx_gb_result *, gx_gbj_stats *);
+/* partial agg + partition of gx_groupby_join_dist on one GPU, as
+ * gx_test_gbd_partial */
+gx_status gx_test_gbj_partial(gx_ctx *, const gx_gb_desc *, const gx_gbj_ext *,
+                              int nsegs, int64_t *out_counts, void *out_rows,
+                              int64_t cap_rows, int64_t *out_total);
+/* Host restatement of the join table: a serial build over the dimension keys
+ * (dim_null[i] != 0 = NULL, never inserted; dim_null may be NULL) and a probe
+ * per fact key, through the same hash, slot and compare functions the
+ * kernels call, no GPU needed.  out_row[i] = the matched dimension row or -1
+ * (also for a NULL fact key).  Returns 0, 1 for a duplicate dimension key
+ * (*dup_key set; out_row untouched), -1 for bad arguments (a negative count,
+ * a missing array, 2^32 - 1 dimension rows or more).
+ * gx_selftest_gbj_slots: out[i] = the home slot of keys[i] in the join table
+ * of a dimension of ndim rows; returns that table's slot count, or -1. */
+int64_t gx_selftest_gbj_join(const int64_t *dim_keys, const uint8_t *dim_null,
+                             int64_t ndim, const int64_t *fact_keys,
+                             const uint8_t *fact_null, int64_t nfact,
+                             int64_t *out_row, int64_t *dup_key);
+int64_t gx_selftest_gbj_slots(const int64_t *keys, int64_t n, int64_t ndim,
+                              uint32_t *out);
 /* The final ordering of gx_groupby_desc alone, no GPU needed: perm[0..n)
  * receives the row order of n rows of nkeys (1..GX_GB_MAX_KEYS) columns,
  * row-major keys / key_null, sorted by the (key_null, key) pairs column by
