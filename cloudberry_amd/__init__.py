@@ -327,6 +327,21 @@ def _load():
                                               ctypes.c_uint64, ctypes.c_int]
     lib.gx_rank_scan_block_keys.restype = ctypes.c_int64
     lib.gx_rank_scan_block_keys.argtypes = []
+    lib.gx_q3_orders_mode.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
+    lib.gx_q3_orders_stage_claims.argtypes = [ctypes.c_void_p,
+                                              ctypes.POINTER(ctypes.c_int64),
+                                              ctypes.POINTER(ctypes.c_int64),
+                                              ctypes.POINTER(ctypes.c_int64)]
+    lib.gx_q3_test_set_orders_grid.argtypes = [ctypes.c_void_p, ctypes.c_int64]
+    lib.gx_selftest_orders_staged.restype = ctypes.c_int
+    lib.gx_selftest_orders_staged.argtypes = [ctypes.c_int64, ctypes.c_int64,
+                                              ctypes.c_int]
+    lib.gx_orders_stage_rule_k.restype = ctypes.c_int64
+    lib.gx_orders_stage_rule_k.argtypes = []
+    lib.gx_selftest_orders_stage_grid.restype = ctypes.c_int64
+    lib.gx_selftest_orders_stage_grid.argtypes = [ctypes.c_int64, ctypes.c_int64]
+    lib.gx_orders_stage_wave_records.restype = ctypes.c_int64
+    lib.gx_orders_stage_wave_records.argtypes = []
     lib.gx_q3_result.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.POINTER(_Group)),
                                  ctypes.POINTER(ctypes.c_int64)]
     lib.gx_q3_topn.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
@@ -538,6 +553,29 @@ def rank_eligible(qual, kmin, kmax, enabled=True):
 def rank_scan_block_keys():
     """Keys one block of the rank table's prefix-popcount scan covers."""
     return int(lib().gx_rank_scan_block_keys())
+
+
+def orders_staged(qual, nrows, env=None):
+    """The rank-form orders stage's form rule: True = staged, False =
+    two-pass, for qual qualifying of nrows mid rows.  env is the value of
+    GX_ORDERS_STAGED (0 or 1 forces a form, None = unset).  Host only."""
+    return bool(lib().gx_selftest_orders_staged(
+        int(qual), int(nrows), -1 if env is None else int(env)))
+
+
+def orders_stage_k():
+    """K of that rule: staged iff qual * K <= nrows."""
+    return int(lib().gx_orders_stage_rule_k())
+
+
+def orders_stage_grid(qual, nrows):
+    """Blocks of the staged form's filter grid for those counts (host only)."""
+    return int(lib().gx_selftest_orders_stage_grid(int(qual), int(nrows)))
+
+
+def orders_stage_wave_records():
+    """Records of one wave's LDS segment in the staged filter kernel."""
+    return int(lib().gx_orders_stage_wave_records())
 
 
 def gb_lds_groups(naggs):
@@ -1581,6 +1619,27 @@ class Q3:
         m = ctypes.c_int()
         self.ctx._chk(self.ctx._lib.gx_q3_table_mode(self._q, ctypes.byref(m)))
         return m.value
+
+    def orders_mode(self):
+        """Form the last run's rank-form orders stage took: 0 = two-pass
+        (row mask, second walk), 1 = staged (compacted records)."""
+        m = ctypes.c_int()
+        self.ctx._chk(self.ctx._lib.gx_q3_orders_mode(self._q, ctypes.byref(m)))
+        return m.value
+
+    def orders_stage_claims(self):
+        """(blocks, mid-loop flushes, records) of the last run's staged orders
+        stage: its cursor claims number at most blocks + flushes, and they
+        added up to `records` qualifying rows."""
+        b, f, r = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        self.ctx._chk(self.ctx._lib.gx_q3_orders_stage_claims(
+            self._q, ctypes.byref(b), ctypes.byref(f), ctypes.byref(r)))
+        return b.value, f.value, r.value
+
+    def _test_set_orders_grid(self, blocks):
+        """Test seam: grid of the staged filter kernel; 0 = production rule."""
+        self.ctx._chk(self.ctx._lib.gx_q3_test_set_orders_grid(self._q, int(blocks)))
+        return self
 
     def result(self):
         gp = ctypes.POINTER(_Group)()

@@ -1535,16 +1535,69 @@ __global__ void k_orders_build(const uint8_t *ok_s, gx_colmeta ok_m,
 }
 
 /* ---- orders stage in rank form (gx_rankview): mark, prefix popcounts, fill.
- * Replaces k_orders_build when the run uses the rank table. ---- */
+ * Replaces k_orders_build when the run uses the rank table.  The stage has
+ * two forms, chosen per run by q3_orders_staged from the selectivity sizing
+ * measured (GX_ORDERS_STAGED forces one):
+ *
+ * - two-pass: k_orders_mark writes a per-row mask, and k_orders_fill walks
+ *   every mid row again and re-reads key, date and attr2 of the rows whose
+ *   mask bit is set.  Wastes little where most rows qualify.
+ * - staged: k_orders_mark<STAGE> compacts {key, attr1, attr2} of the
+ *   qualifying rows, which it has in registers when it decides, into a
+ *   staging array of local_qual 16-byte records, and k_orders_fill_staged
+ *   reads only those.  Where few rows qualify the second walk over three
+ *   columns, a third to a half of whose sectors it touched for one lane in
+ *   ten, is gone (profiles/orders_stage_kernels.txt). ---- */
+
+/* records one wave collects in LDS before it has to claim staging space
+ * (W): 4 waves x 256 x 16 B = 16 KiB per block, 8 blocks per CU */
+static constexpr int GX_STAGE_WAVE_RECS = 256;
+static_assert(GX_STAGE_WAVE_RECS >= 64, "a segment takes one wave iteration");
+
+/* staging record {u64 key; i32 attr1; i32 attr2}, moved as one ulonglong2 */
+__device__ __forceinline__ ulonglong2 d_stage_pack(uint64_t k, int32_t a1, int32_t a2)
+{
+    return make_ulonglong2(k, (unsigned long long) (uint32_t) a1 |
+                                  ((unsigned long long) (uint32_t) a2 << 32));
+}
+
+/* Copy n records of this wave's LDS segment to stage[off ..), clamped to the
+ * staging capacity: input that changed after sizing drops rows but never
+ * leaves the allocation.  Coalesced 16-byte stores.  Every lane calls it. */
+__device__ __forceinline__ void d_stage_copy_out(const ulonglong2 *seg, uint32_t n,
+                                                 unsigned long long off,
+                                                 ulonglong2 *stage, uint64_t cap,
+                                                 int lane)
+{
+    uint64_t o = off < cap ? off : cap;
+    uint64_t room = cap - o;
+    uint32_t m = (uint64_t) n < room ? n : (uint32_t) room;
+    for (uint32_t j = (uint32_t) lane; j < m; j += 64)
+        stage[o + j] = seg[j];
+}
 
 /* Mark: k_orders_build's filters and dim test; a qualifying row sets its
  * key's bit (d_dimbits_set_wave, so whole waves iterate together: no
- * `continue`, wave-uniform bounds) and the wave's qualifying mask goes to
- * rowmask[row / 64] with one plain store — every word of the mask is
- * rewritten each run.  The fill kernel selects rows by that mask, not by the
- * key's bit, so a key on two rows of which one fails the filter keeps the
- * qualifying row's attrs.  blockDim.x must be a multiple of 64. */
-template <typename KS, bool VM = false, bool ANTI = false, bool BM = false>
+ * `continue`, wave-uniform bounds).  blockDim.x must be a multiple of 64.
+ *
+ * Two-pass form: the wave's qualifying mask goes to rowmask[row / 64] with
+ * one plain store — every word of the mask is rewritten each run.  The fill
+ * kernel selects rows by that mask, not by the key's bit, so a key on two
+ * rows of which one fails the filter keeps the qualifying row's attrs.
+ *
+ * STAGE form (blockDim.x == TPB): no rowmask.  A qualifying lane also loads
+ * attr2 and appends its record to its wave's LDS segment of
+ * GX_STAGE_WAVE_RECS records, at the wave's count plus its rank in the
+ * ballot; nothing in the row loop waits on another wave.  After the loop the
+ * block claims one contiguous staging region with ONE returning atomic on
+ * cursor[0] and every wave copies its segment out.  A wave whose segment
+ * cannot take an iteration's records first flushes on its own (one claim, a
+ * coalesced copy, cursor[1] counts these); the host sizes the grid so that
+ * this stays the exception, because same-address atomics cost 6 ms per
+ * 500 k (d_wave_claim).  The template flag is compile-time so that the
+ * two-pass instantiations are what they were before it existed. */
+template <typename KS, bool VM = false, bool ANTI = false, bool BM = false,
+          bool STAGE = false>
 __global__ void k_orders_mark(const uint8_t *ok_s, gx_colmeta ok_m,
                               const uint8_t *oc_s, gx_colmeta oc_m,
                               const uint8_t *od_s, gx_colmeta od_m,
@@ -1553,9 +1606,17 @@ __global__ void k_orders_mark(const uint8_t *ok_s, gx_colmeta ok_m,
                               const unsigned long long *bloom, uint64_t bwmask,
                               gx_dimbits bm,
                               ulonglong2 *rent, uint64_t kmin,
-                              uint64_t range, unsigned long long *rowmask)
+                              uint64_t range, unsigned long long *rowmask,
+                              const uint8_t *op_s, gx_colmeta op_m,
+                              ulonglong2 *stage, unsigned long long *cursor,
+                              uint64_t cap)
 {
+    __shared__ ulonglong2 s_rec[STAGE ? (TPB / 64) * GX_STAGE_WAVE_RECS : 1];
+    __shared__ uint32_t s_cnt[TPB / 64];
+    __shared__ unsigned long long s_off;
     const int lane = (int) (threadIdx.x & 63);
+    const int wave = (int) (threadIdx.x >> 6);
+    uint32_t wn = 0;                   /* records in this wave's segment */
     int64_t base = blockIdx.x * (int64_t) blockDim.x + threadIdx.x - lane;
     int64_t stride = gridDim.x * (int64_t) blockDim.x;
     for (; base < ok_m.nrows; base += stride)
@@ -1565,10 +1626,10 @@ __global__ void k_orders_mark(const uint8_t *ok_s, gx_colmeta ok_m,
         if constexpr (VM)
             act = act && !gx_vm_hidden(vmap, r);
         uint64_t ck = 0, k = 0;
+        int32_t od = 0;
         if constexpr (BM)
         {
             /* early fk load, non-temporal streams: see k_orders_build */
-            int32_t od = 0;
             if (act)
             {
                 od = gx_col_get_nt<int32_t>(od_s, od_m, r);
@@ -1578,7 +1639,8 @@ __global__ void k_orders_mark(const uint8_t *ok_s, gx_colmeta ok_m,
         }
         else
         {
-            act = act && gx_cmp(oop, gx_col_get<int32_t>(od_s, od_m, r), olit);
+            if (act) od = gx_col_get<int32_t>(od_s, od_m, r);
+            act = act && gx_cmp(oop, od, olit);
             if (act) ck = (uint64_t) gx_col_get<int64_t>(oc_s, oc_m, r);
         }
         if (act)
@@ -1594,7 +1656,61 @@ __global__ void k_orders_mark(const uint8_t *ok_s, gx_colmeta ok_m,
         d_dimbits_set_wave<2>(reinterpret_cast<unsigned long long *>(rent),
                               kmin, range, act, k);
         unsigned long long m = __ballot(act);
-        if (lane == 0) rowmask[base >> 6] = m;
+        if constexpr (STAGE)
+        {
+            if (m == 0) continue;          /* wave-uniform */
+            ulonglong2 *seg = s_rec + wave * GX_STAGE_WAVE_RECS;
+            int32_t a2 = 0;
+            if (act)
+            {
+                if constexpr (BM)
+                    a2 = gx_col_get_nt<int32_t>(op_s, op_m, r);
+                else
+                    a2 = gx_col_get<int32_t>(op_s, op_m, r);
+            }
+            uint32_t c = (uint32_t) __popcll(m);
+            if (wn + c > (uint32_t) GX_STAGE_WAVE_RECS)   /* wave-uniform */
+            {
+                unsigned long long off = 0;
+                if (lane == 0)
+                {
+                    off = atomicAdd(&cursor[0], (unsigned long long) wn);
+                    atomicAdd(&cursor[1], 1ULL);
+                }
+                off = __shfl(off, 0, 64);
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                d_stage_copy_out(seg, wn, off, stage, cap, lane);
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                wn = 0;
+            }
+            if (act)
+                seg[wn + (uint32_t) __popcll(m & ((1ULL << lane) - 1ULL))] =
+                    d_stage_pack(k, od, a2);
+            wn += c;
+        }
+        else
+        {
+            if (lane == 0) rowmask[base >> 6] = m;
+        }
+    }
+    if constexpr (STAGE)
+    {
+        const int nw = (int) (blockDim.x >> 6);
+        if (lane == 0) s_cnt[wave] = wn;
+        __syncthreads();                   /* counts and segments complete */
+        uint32_t before = 0, total = 0;
+        for (int w = 0; w < nw; w++)
+        {
+            uint32_t c = s_cnt[w];
+            before += w < wave ? c : 0;
+            total += c;
+        }
+        if (threadIdx.x == 0 && total)
+            s_off = atomicAdd(&cursor[0], (unsigned long long) total);
+        __syncthreads();                   /* the claim, to every wave */
+        if (total)
+            d_stage_copy_out(s_rec + wave * GX_STAGE_WAVE_RECS, wn,
+                             s_off + before, stage, cap, lane);
     }
 }
 
@@ -1672,6 +1788,32 @@ __global__ void k_orders_fill(const uint8_t *ok_s, gx_colmeta ok_m,
         if (idx == ~0ULL) continue;
         dkey[idx] = (KT) k;
         d_slot_claim(dattr, dagg, idx, a1, a2);
+    }
+}
+
+/* Fill of the staged form: the same three stores, driven by the records
+ * k_orders_mark<STAGE> compacted instead of a second walk over the mid
+ * table.  The record count is what the mark kernel's claims added up to,
+ * read from the device cursor (no host sync between mark, scans and fill)
+ * and clamped to the staging capacity. */
+template <typename KT>
+__global__ void k_orders_fill_staged(const ulonglong2 *stage,
+                                     const unsigned long long *cursor,
+                                     uint64_t cap, gx_rankview rv,
+                                     KT *dkey, gx_attrpair *dattr, gx_aggslot *dagg)
+{
+    unsigned long long have = cursor[0];
+    uint64_t n = have < cap ? have : cap;
+    uint64_t i = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x;
+    uint64_t stride = gridDim.x * (uint64_t) blockDim.x;
+    for (; i < n; i += stride)
+    {
+        ulonglong2 rec = stage[i];
+        uint64_t idx = d_rank_find(rv, rec.x);
+        if (idx == ~0ULL) continue;
+        dkey[idx] = (KT) rec.x;
+        d_slot_claim(dattr, dagg, idx, (int32_t) (uint32_t) rec.y,
+                     (int32_t) (uint32_t) (rec.y >> 32));
     }
 }
 
@@ -3889,8 +4031,18 @@ struct gx_q3 {
     uint64_t rank_kmin = 0, rank_range = 0;
     ulonglong2 *rent = nullptr;            /* {bits, base} per 64 keys */
     uint32_t *rblk = nullptr;              /* per-scan-block popcounts */
-    unsigned long long *rowmask = nullptr; /* per mid row: qualifies this run */
-    void *dkey = nullptr;                  /* dense arrays, local_qual slots */
+    unsigned long long *rowmask = nullptr; /* per mid row: qualifies this run
+                                              (two-pass orders stage only) */
+    /* staged orders stage (k_orders_mark<STAGE>): local_qual records and
+     * {record cursor, mid-loop flush count}, allocated by the first run
+     * that takes the form */
+    ulonglong2 *stage = nullptr;
+    unsigned long long *stage_cur = nullptr;
+    int orders_mode = 0;             /* form the last rank-form run's orders
+                                        stage took: 0 two-pass, 1 staged */
+    int64_t test_orders_grid = 0;    /* gx_q3_test_set_orders_grid; 0 = rule */
+    int64_t stage_blocks = 0;        /* mark grid of the last staged run */
+    void *dkey = nullptr;                 /* dense arrays, local_qual slots */
     gx_attrpair *dattr = nullptr;
     gx_aggslot *dagg = nullptr;
     unsigned long long *dcount = nullptr, *dhits = nullptr, *dmin = nullptr;
@@ -6149,6 +6301,7 @@ static void q3_free_runstate(gx_q3 *q)
     auto fr = [](auto *&p) { if (p) { (void) hipFree(p); p = nullptr; } };
     fr(q->cset); fr(q->bloom); fr(q->dbits); fr(q->tkey); fr(q->tattr); fr(q->tagg);
     fr(q->rent); fr(q->rblk); fr(q->rowmask);
+    fr(q->stage); fr(q->stage_cur);
     fr(q->dkey); fr(q->dattr); fr(q->dagg);
     fr(q->r_okey); fr(q->r_odate); fr(q->r_oprio); fr(q->r_rev); fr(q->r_cnt);
     fr(q->r_flags);
@@ -6355,29 +6508,93 @@ static bool q3_rank_eligible(int64_t qual, uint64_t kmin, uint64_t kmax,
     return span < 64 * (uint64_t) qual;
 }
 
-/* first rank-form run of a q: allocate the rank storage */
+/* Which form the rank-form orders stage takes for qual qualifying of nrows
+ * mid rows: staged (k_orders_mark<STAGE>, k_orders_fill_staged) where at
+ * most one row in GX_ORDERS_STAGE_K qualifies, two-pass (rowmask,
+ * k_orders_fill) above.  The staged form saves the second walk over the mid
+ * table and pays 32 B of staging traffic per qualifying row; the threshold
+ * is where the SF100 sweep stops showing a win
+ * (profiles/orders_stage_ab.json).  env is GX_ORDERS_STAGED: 0 or 1 forces
+ * a form, anything negative (unset) means the rule.  Pure host function;
+ * gx_selftest_orders_staged. */
+static constexpr int64_t GX_ORDERS_STAGE_K = 4;
+static bool q3_orders_staged(int64_t qual, int64_t nrows, int env)
+{
+    if (env >= 0) return env != 0;
+    if (qual < 0 || nrows < 0) return false;
+    return qual <= nrows / GX_ORDERS_STAGE_K;   /* qual * K <= nrows, no product */
+}
+
+/* Mark grid of the staged form: enough row iterations per wave that the
+ * records a wave expects (64 x selectivity each) fill three quarters of its
+ * LDS segment, so nearly every block ends with ONE cursor claim and a
+ * mid-loop flush is rare.  At 10 % and 256 records that is 30 iterations,
+ * 19.5 k blocks at SF100.  Never fewer blocks than fill the machine a few
+ * times over (unless the table is smaller), never more than 2^20. */
+static int64_t q3_stage_grid(int64_t qual, int64_t nrows)
+{
+    int64_t rowblocks = std::max<int64_t>((nrows + TPB - 1) / TPB, 1);
+    int64_t iters = qual > 0
+        ? (int64_t) ((3.0 * GX_STAGE_WAVE_RECS / 4.0) * (double) nrows /
+                     (64.0 * (double) qual))
+        : rowblocks;
+    iters = std::max<int64_t>(iters, 1);
+    int64_t blocks = (rowblocks + iters - 1) / iters;
+    blocks = std::max<int64_t>(blocks, std::min<int64_t>(rowblocks, 8192));
+    return std::min<int64_t>(blocks, 1 << 20);
+}
+
+/* first rank-form run of a q: allocate the rank storage.  What only one
+ * form of the orders stage needs (rowmask; staging records) is allocated by
+ * that form's first run. */
 static gx_status q3_alloc_rank(gx_q3 *q)
 {
     gx_ctx *ctx = q->ctx;
     uint64_t nwords = (q->rank_range + 63) / 64;
     uint64_t nblk = (nwords + GX_RANK_SCAN_WORDS - 1) / GX_RANK_SCAN_WORDS;
     uint64_t qual = (uint64_t) q->local_qual;
-    uint64_t mwords = ((uint64_t) q->ord->nrows + 63) / 64;
     auto fr = [](auto *&p) { if (p) { (void) hipFree(p); p = nullptr; } };
-    fr(q->rent); fr(q->rblk); fr(q->rowmask);   /* a failed earlier try */
+    fr(q->rent); fr(q->rblk);                   /* a failed earlier try */
     fr(q->dkey); fr(q->dattr); fr(q->dagg);
     gx_status st = hbm_budget_check(
         ctx,
-        nwords * 16 + nblk * 4 + mwords * 8 +
+        nwords * 16 + nblk * 4 +
             qual * (q->rank_kw + sizeof(gx_attrpair) + sizeof(gx_aggslot)),
         "rank join/agg table");
     if (st != GX_OK) return st;
     HIP_CHK(ctx, hipMalloc(&q->rent, nwords * sizeof(ulonglong2)));
     HIP_CHK(ctx, hipMalloc(&q->rblk, nblk * 4));
-    HIP_CHK(ctx, hipMalloc(&q->rowmask, std::max<uint64_t>(mwords, 1) * 8));
     HIP_CHK(ctx, hipMalloc(&q->dkey, qual * q->rank_kw));
     HIP_CHK(ctx, hipMalloc(&q->dattr, qual * sizeof(gx_attrpair)));
     HIP_CHK(ctx, hipMalloc(&q->dagg, qual * sizeof(gx_aggslot)));
+    return GX_OK;
+}
+
+/* first two-pass run of a q: the per-row mask */
+static gx_status q3_alloc_rowmask(gx_q3 *q)
+{
+    gx_ctx *ctx = q->ctx;
+    uint64_t mwords = ((uint64_t) q->ord->nrows + 63) / 64;
+    gx_status st = hbm_budget_check(ctx, mwords * 8, "orders row mask");
+    if (st != GX_OK) return st;
+    HIP_CHK(ctx, hipMalloc(&q->rowmask, std::max<uint64_t>(mwords, 1) * 8));
+    return GX_OK;
+}
+
+/* first staged run of a q: local_qual staging records (sizing counted
+ * qualifying ROWS, so they all fit while the input is what it was) and the
+ * cursor pair */
+static gx_status q3_alloc_stage(gx_q3 *q)
+{
+    gx_ctx *ctx = q->ctx;
+    uint64_t cap = (uint64_t) q->local_qual;
+    auto fr = [](auto *&p) { if (p) { (void) hipFree(p); p = nullptr; } };
+    fr(q->stage); fr(q->stage_cur);             /* a failed earlier try */
+    gx_status st = hbm_budget_check(ctx, cap * sizeof(ulonglong2) + 16,
+                                    "orders staging records");
+    if (st != GX_OK) return st;
+    HIP_CHK(ctx, hipMalloc(&q->stage, std::max<uint64_t>(cap, 1) * sizeof(ulonglong2)));
+    HIP_CHK(ctx, hipMalloc(&q->stage_cur, 16));
     return GX_OK;
 }
 
@@ -6900,6 +7117,35 @@ extern "C" gx_status gx_q3_table_mode(gx_q3 *q, int *mode)
     return GX_OK;
 }
 
+extern "C" gx_status gx_q3_orders_mode(gx_q3 *q, int *mode)
+{
+    if (!q || !mode) return GX_ERR_INVALID;
+    if (!q->ran) return GX_ERR_STATE;
+    *mode = q->table_mode == 1 ? q->orders_mode : 0;
+    return GX_OK;
+}
+
+extern "C" gx_status gx_q3_orders_stage_claims(gx_q3 *q, int64_t *blocks,
+                                               int64_t *flushes, int64_t *records)
+{
+    if (!q || !blocks || !flushes || !records) return GX_ERR_INVALID;
+    if (!q->ran || q->table_mode != 1 || q->orders_mode != 1 || !q->stage_cur)
+        return GX_ERR_STATE;
+    unsigned long long cur[2] = {0, 0};
+    HIP_CHK(q->ctx, hipMemcpy(cur, q->stage_cur, sizeof cur, hipMemcpyDeviceToHost));
+    *blocks = q->stage_blocks;
+    *flushes = (int64_t) cur[1];
+    *records = (int64_t) cur[0];
+    return GX_OK;
+}
+
+extern "C" gx_status gx_q3_test_set_orders_grid(gx_q3 *q, int64_t blocks)
+{
+    if (!q || blocks < 0 || blocks > (1 << 20)) return GX_ERR_INVALID;
+    q->test_orders_grid = blocks;
+    return GX_OK;
+}
+
 /* the columns and effective visibility masks one Q3 run reads (extra-qual
  * masks fold the visimap in) */
 struct q3_runcols {
@@ -6966,7 +7212,9 @@ static inline gx_rankview q3_rankview(const gx_q3 *q)
 
 /* Stage 2, single segment, rank form: mark the qualifying keys' bits and the
  * qualifying rows, turn the bit words into ranks (prefix popcounts), then
- * store each qualifying row's key and attrs at its key's rank */
+ * store each qualifying row's key and attrs at its key's rank.  The rows
+ * reach the fill kernel as a per-row mask (two-pass) or as compacted records
+ * (staged): q3_orders_staged picks per run. */
 static gx_status q3_orders_rank(gx_q3 *q, const q3_runcols &C, bool use_bitmap)
 {
     gx_ctx *ctx = q->ctx;
@@ -6976,6 +7224,19 @@ static gx_status q3_orders_rank(gx_q3 *q, const q3_runcols &C, bool use_bitmap)
     if (q->dagg == nullptr)     /* first rank-form run of this q */
     {
         gx_status st = q3_alloc_rank(q);
+        if (st != GX_OK) return st;
+    }
+    const bool staged = q3_orders_staged(q->local_qual, ok.m.nrows,
+                                         env_int("GX_ORDERS_STAGED", -1));
+    q->orders_mode = staged ? 1 : 0;
+    if (staged && q->stage_cur == nullptr)      /* first staged run */
+    {
+        gx_status st = q3_alloc_stage(q);
+        if (st != GX_OK) return st;
+    }
+    if (!staged && q->rowmask == nullptr)       /* first two-pass run */
+    {
+        gx_status st = q3_alloc_rowmask(q);
         if (st != GX_OK) return st;
     }
     uint64_t nwords = (q->rank_range + 63) / 64;
@@ -6991,6 +7252,8 @@ static gx_status q3_orders_rank(gx_q3 *q, const q3_runcols &C, bool use_bitmap)
     HIP_CHK(ctx, hipMemsetAsync(q->rent, 0, nwords * sizeof(ulonglong2), s));
     HIP_CHK(ctx, hipMemsetAsync(q->dkey, 0,
                                 (uint64_t) q->local_qual * q->rank_kw, s));
+    if (staged)
+        HIP_CHK(ctx, hipMemsetAsync(q->stage_cur, 0, 16, s));
     if (D.fact_join == 1)
     {
         HIP_CHK(ctx, hipMemsetAsync(q->ukey, 0, (q->umask + 1) * 8, s));
@@ -6999,20 +7262,35 @@ static gx_status q3_orders_rank(gx_q3 *q, const q3_runcols &C, bool use_bitmap)
     }
     gx_dimbits dbm = {q->dbits, q->dim_kmin, q->dim_range};
     const gx_rankview rv = q3_rankview(q);
+    const uint64_t cap = (uint64_t) q->local_qual;
+    /* two-pass: the grid k_orders_build measured best.  staged: sized from
+     * the selectivity (q3_stage_grid), or the caller's in tests. */
+    int64_t mark_grid = ORDERS_GRID;
+    if (staged)
+    {
+        mark_grid = q->test_orders_grid > 0
+            ? q->test_orders_grid
+            : q3_stage_grid(q->local_qual, ok.m.nrows);
+        q->stage_blocks = mark_grid;
+    }
     auto launch_mark = [&](auto *cs, auto bmode) {
         by_flag(C.ovm != nullptr, [&](auto vm) {
             by_flag(D.dim_join != 0, [&](auto anti) {
-                hipLaunchKernelGGL((k_orders_mark<std::decay_t<decltype(*cs)>,
-                                                  decltype(vm)::value,
-                                                  decltype(anti)::value,
-                                                  decltype(bmode)::value>),
-                                   dim3(ORDERS_GRID), dim3(TPB), 0, s,
-                                   ok.dstream, ok.m, oc.dstream, oc.m,
-                                   od.dstream, od.m, C.ovm, D.mid_filter.op,
-                                   (int32_t) D.mid_filter.literal, cs, q->cmask,
-                                   q->bloom, q->bwmask, dbm,
-                                   q->rent, q->rank_kmin, q->rank_range,
-                                   q->rowmask);
+                by_flag(staged, [&](auto stg) {
+                    hipLaunchKernelGGL((k_orders_mark<std::decay_t<decltype(*cs)>,
+                                                      decltype(vm)::value,
+                                                      decltype(anti)::value,
+                                                      decltype(bmode)::value,
+                                                      decltype(stg)::value>),
+                                       dim3((unsigned) mark_grid), dim3(TPB), 0, s,
+                                       ok.dstream, ok.m, oc.dstream, oc.m,
+                                       od.dstream, od.m, C.ovm, D.mid_filter.op,
+                                       (int32_t) D.mid_filter.literal, cs, q->cmask,
+                                       q->bloom, q->bwmask, dbm,
+                                       q->rent, q->rank_kmin, q->rank_range,
+                                       q->rowmask, op.dstream, op.m,
+                                       q->stage, q->stage_cur, cap);
+                });
             });
         });
     };
@@ -7029,11 +7307,22 @@ static gx_status q3_orders_rank(gx_q3 *q, const q3_runcols &C, bool use_bitmap)
     hipLaunchKernelGGL(k_rank_localscan, dim3((unsigned) nblk), dim3(TPB), 0, s,
                        q->rent, nwords, q->rblk);
     by_width(q->rank_kw, q->dkey, [&](auto *dk) {
-        hipLaunchKernelGGL(k_orders_fill<std::decay_t<decltype(*dk)>>,
-                           dim3(ORDERS_GRID), dim3(TPB), 0, s,
-                           ok.dstream, ok.m, od.dstream, od.m,
-                           op.dstream, op.m, q->rowmask, rv, dk,
-                           q->dattr, q->dagg);
+        if (staged)
+        {
+            /* the record count is on the device: grid from the capacity */
+            uint64_t fb = std::min<uint64_t>(
+                std::max<uint64_t>((cap + TPB - 1) / TPB, 1), ORDERS_GRID);
+            hipLaunchKernelGGL(k_orders_fill_staged<std::decay_t<decltype(*dk)>>,
+                               dim3((unsigned) fb), dim3(TPB), 0, s,
+                               q->stage, q->stage_cur, cap, rv, dk,
+                               q->dattr, q->dagg);
+        }
+        else
+            hipLaunchKernelGGL(k_orders_fill<std::decay_t<decltype(*dk)>>,
+                               dim3(ORDERS_GRID), dim3(TPB), 0, s,
+                               ok.dstream, ok.m, od.dstream, od.m,
+                               op.dstream, op.m, q->rowmask, rv, dk,
+                               q->dattr, q->dagg);
     });
     return GX_OK;
 }
@@ -9609,6 +9898,29 @@ extern "C" int gx_selftest_rank_eligible(int64_t qual, uint64_t kmin,
 extern "C" int64_t gx_rank_scan_block_keys(void)
 {
     return (int64_t) GX_RANK_SCAN_WORDS * 64;
+}
+
+/* the orders stage's form rule (q3_orders_staged), its threshold, the staged
+ * form's mark grid and the records of one wave's LDS segment; callable
+ * without a GPU */
+extern "C" int gx_selftest_orders_staged(int64_t qual, int64_t nrows, int env)
+{
+    return q3_orders_staged(qual, nrows, env) ? 1 : 0;
+}
+
+extern "C" int64_t gx_orders_stage_rule_k(void)
+{
+    return GX_ORDERS_STAGE_K;
+}
+
+extern "C" int64_t gx_selftest_orders_stage_grid(int64_t qual, int64_t nrows)
+{
+    return q3_stage_grid(qual, nrows);
+}
+
+extern "C" int64_t gx_orders_stage_wave_records(void)
+{
+    return GX_STAGE_WAVE_RECS;
 }
 
 /* bind's per-block routing of the fused RLE probe (parse_block_dir +

@@ -335,6 +335,28 @@ gx_status gx_q3_dim_mode(gx_q3 *q, int *mode);
  * measures over a plain fact key, and the hash form otherwise.  GX_ERR_STATE
  * before the first run. */
 gx_status gx_q3_table_mode(gx_q3 *q, int *mode);
+/* Form the orders stage of the LAST run took when that run used the rank
+ * table: 0 = two-pass (a per-row mask, then a second walk over the mid table
+ * that re-reads the qualifying rows), 1 = staged (the filter pass compacts
+ * {key, attr1, attr2} of the qualifying rows into 16-byte records and the
+ * fill reads only those).  Staged is taken where at most one mid row in K
+ * qualified at sizing (K: gx_orders_stage_rule_k); GX_ORDERS_STAGED=0 or =1
+ * forces a form.  0 for a hash-form run.  GX_ERR_STATE before the first
+ * run. */
+gx_status gx_q3_orders_mode(gx_q3 *q, int *mode);
+/* Cursor claims of the last run's staged orders stage: the blocks of its
+ * filter grid (each ends with at most one claim) and the mid-loop flushes of
+ * waves whose LDS segment filled up; and the records those claims added up
+ * to (the run's qualifying mid rows; more than the staging capacity only if
+ * the input changed after sizing).  Copies 16 bytes from the device.
+ * GX_ERR_STATE unless the last run took the staged form. */
+gx_status gx_q3_orders_stage_claims(gx_q3 *q, int64_t *blocks, int64_t *flushes,
+                                    int64_t *records);
+/* Test seam: grid (in blocks of 256 threads, at most 2^20) of the staged
+ * form's filter kernel for later runs of q, same launches otherwise; 0
+ * restores the production rule.  Small grids on small tables reach the
+ * multi-iteration accumulation and the segment-overflow flush. */
+gx_status gx_q3_test_set_orders_grid(gx_q3 *q, int64_t blocks);
 /* groups of THIS segment, sorted by l_orderkey asc; caller frees with gx_free */
 gx_status gx_q3_result(gx_q3 *q, gx_q3_group **out, int64_t *ngroups);
 /* top-N of this segment's groups (Q3's ORDER BY revenue DESC, o_orderdate
@@ -858,6 +880,18 @@ int gx_selftest_rank_eligible(int64_t qual, uint64_t kmin, uint64_t kmax,
 /* Keys covered by one block of the rank table's prefix-popcount scan (ranks
  * of keys further apart cross a block boundary of that scan). */
 int64_t gx_rank_scan_block_keys(void);
+/* The rule behind gx_q3_orders_mode on caller-supplied counts: qual
+ * qualifying of nrows mid rows; env is GX_ORDERS_STAGED (0 or 1 forces,
+ * negative = unset: staged iff qual * K <= nrows, computed without the
+ * product).  No GPU needed.  Returns 1 (staged) or 0 (two-pass). */
+int gx_selftest_orders_staged(int64_t qual, int64_t nrows, int env);
+/* K of that rule. */
+int64_t gx_orders_stage_rule_k(void);
+/* Blocks of the staged form's filter grid for those counts (a wave's
+ * expected records fill three quarters of its segment).  No GPU needed. */
+int64_t gx_selftest_orders_stage_grid(int64_t qual, int64_t nrows);
+/* Records of one wave's LDS segment in the staged filter kernel (W). */
+int64_t gx_orders_stage_wave_records(void);
 /* How bind routes each block of a format-1 stream of 8-byte datums for the
  * fused RLE fact-key probe; no GPU needed.  cls[b]: 0 = not fused (Orig,
  * DELTA, NULL bitmap, more than 4096 physical datums: one such block and
