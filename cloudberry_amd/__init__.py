@@ -1004,32 +1004,52 @@ class Context:
         array per aggregate (float64 where is_f64, else int64), agg_null
         (ngroups, naggs) bool; groups sorted by key, NULLS LAST per column.
         With stats=True returns (result, gx_gbd_stats as a dict)."""
-        return self._groupby_desc(table, keys, aggs, quals, max_groups, stats,
-                                  None)
+        return self._gb_run("gx_groupby_desc", _GbdStats(), table, keys, aggs,
+                            quals, max_groups, stats)
 
     def test_groupby_desc(self, table, keys, aggs, quals=(), max_groups=0,
                           stats=False, grid=0, wide_rowid=False):
         """groupby_desc through the test seam: grid workgroups scan the input
         (0 = production) and wide_rowid forces the 8-byte slot word."""
-        return self._groupby_desc(table, keys, aggs, quals, max_groups, stats,
-                                  (grid, 1 if wide_rowid else 0))
+        return self._gb_run("gx_test_groupby_desc", _GbdStats(), table, keys,
+                            aggs, quals, max_groups, stats,
+                            seam=(grid, 1 if wide_rowid else 0))
 
-    def _groupby_desc(self, table, keys, aggs, quals, max_groups, stats, seam):
+    def _gb_run(self, entry, st, table, keys, aggs, quals, max_groups, stats,
+                fquals=None, joins=None, seam=(), ext=True, jext=None):
+        """The one path behind groupby_desc / _expr / _join, their test seams
+        and their _dist forms: build the descriptors the family takes (fquals
+        None: gx_gb_desc alone; joins None: and gx_gb_ext; else and
+        gx_gbj_ext), call `entry` with the seam's arguments before the result
+        and the stats struct `st`, check, convert."""
         keys, aggs, quals = list(keys), list(aggs), list(quals)
-        d = self._gb_desc(table, keys, aggs, quals, max_groups)
-        res, st = _GbResult(), _GbdStats()
-        if seam is None:
-            rc = self._lib.gx_groupby_desc(self._h, ctypes.byref(d),
-                                           ctypes.byref(res), ctypes.byref(st))
+        if fquals is None:
+            d, descs, plain = self._gb_desc(table, keys, aggs, quals, max_groups), [], aggs
         else:
-            rc = self._lib.gx_test_groupby_desc(
-                self._h, ctypes.byref(d), seam[0], seam[1], ctypes.byref(res),
-                ctypes.byref(st))
-        self._chk(rc)
-        out = self._gb_result(res, aggs)
-        if stats:
-            return out, {f: getattr(st, f) for f, _ in st._fields_}
-        return out
+            if joins is None:
+                d, x, plain = _gb_expr_desc(table, keys, aggs, quals, list(fquals),
+                                            max_groups)
+                descs = []
+            else:
+                d, jx, x, plain = _gbj_desc(table, keys, aggs, list(joins), quals,
+                                            list(fquals), max_groups)
+                if callable(jext):
+                    jext(jx)
+                descs = [ctypes.byref(jx)]
+            if callable(ext):
+                ext(x)
+            descs.append(ctypes.byref(x) if ext is not None else None)
+        res = _GbResult()
+        self._chk(getattr(self._lib, entry)(
+            self._h, ctypes.byref(d), *descs, *seam, ctypes.byref(res),
+            ctypes.byref(st)))
+        out = self._gb_result(res, plain)
+        if not stats:
+            return out
+        sd = {f: getattr(st, f) for f, _ in st._fields_}
+        if "dim_rows" in sd:
+            sd["dim_rows"] = list(st.dim_rows)
+        return out, sd
 
     def groupby_desc_dist(self, table, keys, aggs, quals=(), max_groups=0,
                           stats=False):
@@ -1037,15 +1057,8 @@ class Context:
         (gx_groupby_desc_dist): the arguments and the result shape of
         groupby_desc, holding the groups THIS segment owns; with stats=True
         returns (result, gx_gb_stats as a dict)."""
-        keys, aggs, quals = list(keys), list(aggs), list(quals)
-        d = self._gb_desc(table, keys, aggs, quals, max_groups)
-        res, st = _GbResult(), _GbStats()
-        self._chk(self._lib.gx_groupby_desc_dist(
-            self._h, ctypes.byref(d), ctypes.byref(res), ctypes.byref(st)))
-        out = self._gb_result(res, aggs)
-        if stats:
-            return out, {f: getattr(st, f) for f, _ in st._fields_}
-        return out
+        return self._gb_run("gx_groupby_desc_dist", _GbStats(), table, keys,
+                            aggs, quals, max_groups, stats)
 
     def groupby_expr(self, table, keys, aggs, quals=(), fquals=(),
                      max_groups=0, stats=False):
@@ -1057,8 +1070,8 @@ class Context:
         op, float) triples over float8 columns, compared in the reference's
         float8 order (NaN above +inf, -0 = +0).  Everything else as
         groupby_desc."""
-        return self._groupby_expr(table, keys, aggs, quals, fquals, max_groups,
-                                  stats, None)
+        return self._gb_run("gx_groupby_expr", _GbdStats(), table, keys, aggs,
+                            quals, max_groups, stats, fquals)
 
     def test_groupby_expr(self, table, keys, aggs, quals=(), fquals=(),
                           max_groups=0, stats=False, grid=0, wide_rowid=False,
@@ -1067,45 +1080,17 @@ class Context:
         test_groupby_desc).  ext=None passes a NULL gx_gb_ext; a callable is
         given the filled gx_gb_ext mirror to alter before the call (raw
         counts, forms and indexes for the error paths)."""
-        return self._groupby_expr(table, keys, aggs, quals, fquals, max_groups,
-                                  stats, (grid, 1 if wide_rowid else 0), ext)
-
-    def _groupby_expr(self, table, keys, aggs, quals, fquals, max_groups, stats,
-                      seam, ext_arg=True):
-        d, ext, plain = _gb_expr_desc(table, list(keys), list(aggs), list(quals),
-                                      list(fquals), max_groups)
-        if callable(ext_arg):
-            ext_arg(ext)
-        pext = ctypes.byref(ext) if ext_arg is not None else None
-        res, st = _GbResult(), _GbdStats()
-        if seam is None:
-            rc = self._lib.gx_groupby_expr(self._h, ctypes.byref(d), pext,
-                                           ctypes.byref(res), ctypes.byref(st))
-        else:
-            rc = self._lib.gx_test_groupby_expr(
-                self._h, ctypes.byref(d), pext, seam[0], seam[1],
-                ctypes.byref(res), ctypes.byref(st))
-        self._chk(rc)
-        out = self._gb_result(res, plain)
-        if stats:
-            return out, {f: getattr(st, f) for f, _ in st._fields_}
-        return out
+        return self._gb_run("gx_test_groupby_expr", _GbdStats(), table, keys,
+                            aggs, quals, max_groups, stats, fquals,
+                            seam=(grid, 1 if wide_rowid else 0), ext=ext)
 
     def groupby_expr_dist(self, table, keys, aggs, quals=(), fquals=(),
                           max_groups=0, stats=False):
         """Two-stage groupby_expr across all segments of this context
         (gx_groupby_expr_dist): the groups THIS segment owns; with stats=True
         returns (result, gx_gb_stats as a dict)."""
-        d, ext, plain = _gb_expr_desc(table, list(keys), list(aggs), list(quals),
-                                      list(fquals), max_groups)
-        res, st = _GbResult(), _GbStats()
-        self._chk(self._lib.gx_groupby_expr_dist(
-            self._h, ctypes.byref(d), ctypes.byref(ext), ctypes.byref(res),
-            ctypes.byref(st)))
-        out = self._gb_result(res, plain)
-        if stats:
-            return out, {f: getattr(st, f) for f, _ in st._fields_}
-        return out
+        return self._gb_run("gx_groupby_expr_dist", _GbStats(), table, keys,
+                            aggs, quals, max_groups, stats, fquals)
 
     def groupby_join(self, table, keys, aggs, joins, quals=(), fquals=(),
                      max_groups=0, stats=False):
@@ -1118,8 +1103,8 @@ class Context:
         misses any join is dropped.  Everything else, and the result, as
         groupby_expr; with stats=True returns (result, gx_gbj_stats as a
         dict, its dim_rows a list)."""
-        return self._groupby_join(table, keys, aggs, joins, quals, fquals,
-                                  max_groups, stats, None)
+        return self._gb_run("gx_groupby_join", _GbjStats(), table, keys, aggs,
+                            quals, max_groups, stats, fquals, joins)
 
     def test_groupby_join(self, table, keys, aggs, joins, quals=(), fquals=(),
                           max_groups=0, stats=False, grid=0, wide_rowid=False,
@@ -1128,32 +1113,9 @@ class Context:
         test_groupby_desc).  A callable jext is given the filled gx_gbj_ext
         mirror to alter before the call (raw counts, sides and indexes for
         the error paths)."""
-        return self._groupby_join(table, keys, aggs, joins, quals, fquals,
-                                  max_groups, stats,
-                                  (grid, 1 if wide_rowid else 0), jext)
-
-    def _groupby_join(self, table, keys, aggs, joins, quals, fquals, max_groups,
-                      stats, seam, jext_arg=None):
-        d, jext, ext, plain = _gbj_desc(table, list(keys), list(aggs), list(joins),
-                                        list(quals), list(fquals), max_groups)
-        if callable(jext_arg):
-            jext_arg(jext)
-        res, st = _GbResult(), _GbjStats()
-        if seam is None:
-            rc = self._lib.gx_groupby_join(
-                self._h, ctypes.byref(d), ctypes.byref(jext), ctypes.byref(ext),
-                ctypes.byref(res), ctypes.byref(st))
-        else:
-            rc = self._lib.gx_test_groupby_join(
-                self._h, ctypes.byref(d), ctypes.byref(jext), ctypes.byref(ext),
-                seam[0], seam[1], ctypes.byref(res), ctypes.byref(st))
-        self._chk(rc)
-        out = self._gb_result(res, plain)
-        if stats:
-            sd = {f: getattr(st, f) for f, _ in st._fields_}
-            sd["dim_rows"] = list(st.dim_rows)
-            return out, sd
-        return out
+        return self._gb_run("gx_test_groupby_join", _GbjStats(), table, keys,
+                            aggs, quals, max_groups, stats, fquals, joins,
+                            seam=(grid, 1 if wide_rowid else 0), jext=jext)
 
     def groupby_join_dist(self, table, keys, aggs, joins, quals=(), fquals=(),
                           max_groups=0, stats=False):
@@ -1161,16 +1123,8 @@ class Context:
         (gx_groupby_join_dist): every segment holds each dimension complete;
         returns the groups THIS segment owns; with stats=True returns
         (result, gx_gb_stats as a dict)."""
-        d, jext, ext, plain = _gbj_desc(table, list(keys), list(aggs), list(joins),
-                                        list(quals), list(fquals), max_groups)
-        res, st = _GbResult(), _GbStats()
-        self._chk(self._lib.gx_groupby_join_dist(
-            self._h, ctypes.byref(d), ctypes.byref(jext), ctypes.byref(ext),
-            ctypes.byref(res), ctypes.byref(st)))
-        out = self._gb_result(res, plain)
-        if stats:
-            return out, {f: getattr(st, f) for f, _ in st._fields_}
-        return out
+        return self._gb_run("gx_groupby_join_dist", _GbStats(), table, keys,
+                            aggs, quals, max_groups, stats, fquals, joins)
 
     def test_gbj_partial(self, table, keys, aggs, joins, nsegs, quals=(),
                          max_groups=0):

@@ -3239,14 +3239,24 @@ __device__ __forceinline__ gbd_key_cols gbd_scan_src(const gbd_nojoin &)
 __device__ __forceinline__ gbd_key_join gbd_scan_src(const gbd_jargs &jx)
 { return gbd_key_join{jx}; }
 
-/* key values (0 where NULL), null bits and hash of one row */
+/* the group hash: its seed, and the step that folds one key column (value 0
+ * where NULL) into it */
+static constexpr uint64_t GBD_HASH_SEED = 0x9E3779B97F4A7C15ULL;
+static constexpr uint64_t GBD_HASH_NULL = 0xD6E8FEB86659FD93ULL;
+__device__ __forceinline__ uint64_t gbd_hash_key(uint64_t h, int64_t v, bool isnull)
+{
+    return gx_hmix64((h ^ (uint64_t) v) + (isnull ? GBD_HASH_NULL : 0ULL));
+}
+
+/* key values (0 where NULL), null bits and hash of one row; each key is
+ * folded in as it arrives */
 template <typename SRC>
 __device__ __forceinline__ uint64_t gbd_row_keys(const SRC &src, const gbd_args &a,
                                                  int64_t row,
                                                  int64_t (&kv)[GX_GB_MAX_KEYS],
                                                  unsigned &kn)
 {
-    uint64_t h = 0x9E3779B97F4A7C15ULL;
+    uint64_t h = GBD_HASH_SEED;
     kn = 0;
 #pragma unroll
     for (int k = 0; k < GX_GB_MAX_KEYS; k++)
@@ -3257,10 +3267,26 @@ __device__ __forceinline__ uint64_t gbd_row_keys(const SRC &src, const gbd_args 
             bool isnull = src.isnull(a, k, row);
             kv[k] = isnull ? 0 : src.load(a, k, row);
             kn |= (unsigned) isnull << k;
-            h = gx_hmix64((h ^ (uint64_t) kv[k]) +
-                          (isnull ? 0xD6E8FEB86659FD93ULL : 0ULL));
+            h = gbd_hash_key(h, kv[k], isnull);
         }
     }
+    return h;
+}
+
+/* gbd_row_keys' hash over key values already gathered (a join scan loads a
+ * row's fact-side keys before its probes and its dim-side keys after them).
+ * The step is written out on the null BIT: through gbd_hash_key's bool the
+ * two LDS-off JOIN instantiations spill two more SGPRs. */
+__device__ __forceinline__ uint64_t gbd_keys_hash(const gbd_args &a,
+                                                  const int64_t (&kv)[GX_GB_MAX_KEYS],
+                                                  unsigned kn)
+{
+    uint64_t h = GBD_HASH_SEED;
+#pragma unroll
+    for (int k = 0; k < GX_GB_MAX_KEYS; k++)
+        if (k < a.nkeys)
+            h = gx_hmix64((h ^ (uint64_t) kv[k]) +
+                          (((kn >> k) & 1u) ? GBD_HASH_NULL : 0ULL));
     return h;
 }
 
@@ -3296,21 +3322,6 @@ __device__ __forceinline__ bool gbd_keys_eq(const gbd_key_join &src, const gbd_a
                                             unsigned kn, int64_t r)
 {
     return gbd_keys_eq(src.of(r), a, kv, kn, r);
-}
-
-/* gbd_row_keys' hash over key values already gathered (a join scan loads a
- * row's fact-side keys before its probes and its dim-side keys after them) */
-__device__ __forceinline__ uint64_t gbd_keys_hash(const gbd_args &a,
-                                                  const int64_t (&kv)[GX_GB_MAX_KEYS],
-                                                  unsigned kn)
-{
-    uint64_t h = 0x9E3779B97F4A7C15ULL;
-#pragma unroll
-    for (int k = 0; k < GX_GB_MAX_KEYS; k++)
-        if (k < a.nkeys)
-            h = gx_hmix64((h ^ (uint64_t) kv[k]) +
-                          (((kn >> k) & 1u) ? 0xD6E8FEB86659FD93ULL : 0ULL));
-    return h;
 }
 
 /* find or claim the global slot of the group of row i (keys kv/kn, hash h);
@@ -3395,53 +3406,31 @@ __device__ __forceinline__ void gbd_accum_col(const gbd_args &a, int j, int64_t 
     atomicAdd(p + 1, 1ULL);
 }
 
+/* the transition of a float8 value v (an expression's) on the first word p
+ * of an aggregate of transition op; the caller has dealt with NULL */
+__device__ __forceinline__ void gbd_accum_f64(int op, double v, unsigned long long *p)
+{
+    if (op == GBD_COUNT) { atomicAdd(p, 1ULL); return; }
+    const uint64_t bits = (uint64_t) __double_as_longlong(v);
+    if (op == GBD_SUM_F64) atomicAdd((double *) p, v);
+    else if (op == GBD_MAX_F64)
+        atomicMax(p, (unsigned long long) gbd_f64_image(bits));
+    else atomicMax(p, (unsigned long long) ~gbd_f64_image(bits));
+    atomicAdd(p + 1, 1ULL);
+}
+
 /* row i's transitions on the accumulator words w of its group; w is an LDS
- * or a global pointer at the two call sites, so each gets its own atomics */
-__device__ __forceinline__ void gbd_accum(const gbd_args &a, int64_t i,
-                                          unsigned long long *w)
-{
-#pragma unroll
-    for (int j = 0; j < GX_GB_MAX_AGGS; j++)
-    {
-        if (j >= a.naggs) continue;
-        gbd_accum_col(a, j, i, w + a.aword[j]);
-    }
-}
-
-/* the same with expression aggregates: aggregate j with aexpr[j] >= 0 takes
- * its float8 input from the row's expression registers ev (bit e of enull:
- * expression e is NULL in this row), every other one from its column */
-__device__ __forceinline__ void gbd_accum_x(const gbd_args &a, const gbd_xargs &x,
-                                            int64_t i, unsigned long long *w,
-                                            const gbd_d8 &ev, unsigned enull)
-{
-#pragma unroll
-    for (int j = 0; j < GX_GB_MAX_AGGS; j++)
-    {
-        if (j >= a.naggs) continue;
-        unsigned long long *p = w + a.aword[j];
-        const int e = x.aexpr[j];
-        if (e < 0) { gbd_accum_col(a, j, i, p); continue; }
-        if ((enull >> e) & 1u) continue;             /* strict transitions */
-        const int op = a.aop[j];
-        if (op == GBD_COUNT) { atomicAdd(p, 1ULL); continue; }
-        const double v = ev[e];
-        const uint64_t bits = (uint64_t) __double_as_longlong(v);
-        if (op == GBD_SUM_F64) atomicAdd((double *) p, v);
-        else if (op == GBD_MAX_F64)
-            atomicMax(p, (unsigned long long) gbd_f64_image(bits));
-        else atomicMax(p, (unsigned long long) ~gbd_f64_image(bits));
-        atomicAdd(p + 1, 1ULL);
-    }
-}
-
-/* the same for a join scan: a column aggregate reads its argument in the
- * table its side names, at fact row i or at the row's matches d0 / d1 */
-template <bool EXPR, typename X>
-__device__ __forceinline__ void gbj_accum(const gbd_args &a, const gbd_jargs &jx,
-                                          const X &x, int64_t i, int64_t d0,
-                                          int64_t d1, unsigned long long *w,
-                                          const gbd_d8 &ev, unsigned enull)
+ * or a global pointer at the two call sites, so each gets its own atomics.
+ * EXPR: aggregate j with aexpr[j] >= 0 takes its float8 input from the row's
+ * expression registers ev (bit e of enull: expression e is NULL in this
+ * row), every other one from its column.  JOIN: a column aggregate reads its
+ * argument in the table its side names, at fact row i or at the row's
+ * matches d0 / d1. */
+template <bool EXPR, bool JOIN, typename X, typename JX>
+__device__ __forceinline__ void gbd_accum(const gbd_args &a, const X &x, const JX &jx,
+                                          int64_t i, int64_t d0, int64_t d1,
+                                          unsigned long long *w, const gbd_d8 &ev,
+                                          unsigned enull)
 {
 #pragma unroll
     for (int j = 0; j < GX_GB_MAX_AGGS; j++)
@@ -3454,20 +3443,17 @@ __device__ __forceinline__ void gbj_accum(const gbd_args &a, const gbd_jargs &jx
             if (e >= 0)
             {
                 if ((enull >> e) & 1u) continue;         /* strict transitions */
-                const int op = a.aop[j];
-                if (op == GBD_COUNT) { atomicAdd(p, 1ULL); continue; }
-                const double v = ev[e];
-                const uint64_t bits = (uint64_t) __double_as_longlong(v);
-                if (op == GBD_SUM_F64) atomicAdd((double *) p, v);
-                else if (op == GBD_MAX_F64)
-                    atomicMax(p, (unsigned long long) gbd_f64_image(bits));
-                else atomicMax(p, (unsigned long long) ~gbd_f64_image(bits));
-                atomicAdd(p + 1, 1ULL);
+                gbd_accum_f64(a.aop[j], ev[e], p);
                 continue;
             }
         }
-        const int side = jx.agg_side[j];
-        gbd_accum_col(a, j, side == 0 ? i : side == 1 ? d0 : d1, p);
+        if constexpr (JOIN)
+        {
+            const int side = jx.agg_side[j];
+            gbd_accum_col(a, j, side == 0 ? i : side == 1 ? d0 : d1, p);
+        }
+        else
+            gbd_accum_col(a, j, i, p);
     }
 }
 
@@ -3644,13 +3630,8 @@ k_groupby_desc(const gbd_args a,
                 }
                 if (done)
                 {
-                    if constexpr (JOIN)
-                        gbj_accum<EXPR>(a, jx, x, i, d0, d1,
-                                        lacc + (size_t) ls * a.awords, ev, enull);
-                    else if constexpr (EXPR)
-                        gbd_accum_x(a, x, i, lacc + (size_t) ls * a.awords, ev, enull);
-                    else
-                        gbd_accum(a, i, lacc + (size_t) ls * a.awords);
+                    gbd_accum<EXPR, JOIN>(a, x, jx, i, d0, d1,
+                                          lacc + (size_t) ls * a.awords, ev, enull);
                     n_lds++;
                 }
                 /* one pair of counter updates per wave and iteration */
@@ -3667,15 +3648,8 @@ k_groupby_desc(const gbd_args a,
         {
             uint64_t slot = gbd_ginsert<ST>(src, a, trow, tmask, h, kv, kn, i, err);
             if (slot != ~0ULL)
-            {
-                if constexpr (JOIN)
-                    gbj_accum<EXPR>(a, jx, x, i, d0, d1, tacc + slot * a.awords, ev,
-                                    enull);
-                else if constexpr (EXPR)
-                    gbd_accum_x(a, x, i, tacc + slot * a.awords, ev, enull);
-                else
-                    gbd_accum(a, i, tacc + slot * a.awords);
-            }
+                gbd_accum<EXPR, JOIN>(a, x, jx, i, d0, d1, tacc + slot * a.awords, ev,
+                                      enull);
         }
     }
     if (LDS)
@@ -8304,17 +8278,42 @@ static gx_status gbj_plan_ext(gx_ctx *ctx, const gx_gb_desc *d,
     return GX_OK;
 }
 
-/* PLAN: validate the descriptor and fill everything of gbd_args that needs
- * no device memory.  t == nullptr (the combine stage over wire rows) checks
- * and reads nkeys, the aggregates' fn / is_f64 and max_groups only.  ext and
- * xp (both or neither; a table is required) add the expression side, jext
- * and jp (both or neither; a table is required) the join side: a key or a
- * column aggregate is then checked against the table its side names. */
-static gx_status gbd_plan(gx_ctx *ctx, const gx_gb_desc *d, const gx_table *t,
-                          gbd_args &a, const gx_gb_ext *ext = nullptr,
-                          gbd_xplan *xp = nullptr,
-                          const gx_gbj_ext *jext = nullptr, gbj_plan *jp = nullptr)
+/* One planned call: the descriptors as the caller gave them and everything
+ * planned from them.  t is the scanned table, nullptr for the combine-only
+ * plan over wire rows (d->t is then never read); ext and jext may be null (a
+ * table is required with either).  Without ext xp.on is false, without jext
+ * jp.on is false and every side is 0, so no reader asks for the pointers. */
+struct gbd_call {
+    const gx_gb_desc *d;
+    const gx_table *t;
+    const gx_gb_ext *ext;
+    const gx_gbj_ext *jext;
+    gbd_args a;
+    gbd_xplan xp;
+    gbj_plan jp;
+    gbd_inputs in;
+    gbd_call(const gx_gb_desc *d_, const gx_table *t_, const gx_gb_ext *ext_,
+             const gx_gbj_ext *jext_) : d(d_), t(t_), ext(ext_), jext(jext_) {}
+    /* the table key k / column aggregate j reads (its side's) */
+    const gx_table *key_table(int k) const { return jp.table(t, jp.jx.key_side[k]); }
+    const gx_table *agg_table(int j) const { return jp.table(t, jp.jx.agg_side[j]); }
+    /* aggregate j takes an expression's value, not a column's */
+    bool agg_is_expr(int j) const { return xp.on && xp.x.aexpr[j] >= 0; }
+    /* aggregate j reads a column that has to be bound */
+    bool agg_reads_col(int j) const
+    { return d->aggs[j].fn != GX_AGG_COUNT_STAR && !agg_is_expr(j); }
+};
+
+/* PLAN: validate the descriptors and fill everything of the call that needs
+ * no device memory.  The combine-only plan checks and reads nkeys, the
+ * aggregates' fn / is_f64 and max_groups only.  With a join, a key or a
+ * column aggregate is checked against the table its side names. */
+static gx_status gbd_plan(gx_ctx *ctx, gbd_call &c)
 {
+    const gx_gb_desc *d = c.d;
+    const gx_table *t = c.t;
+    const gx_gb_ext *ext = c.ext;
+    gbd_args &a = c.a;
     const int ncols = t ? (int) t->cols.size() : 0;
     if (d->nkeys < 0 || d->nkeys > GX_GB_MAX_KEYS)
         return gbd_invalid(ctx, "nkeys %ld outside 0..%ld", d->nkeys, GX_GB_MAX_KEYS);
@@ -8327,12 +8326,12 @@ static gx_status gbd_plan(gx_ctx *ctx, const gx_gb_desc *d, const gx_table *t,
 
     if (ext)
     {
-        gx_status st = gbd_plan_ext(ctx, ext, t, *xp);
+        gx_status st = gbd_plan_ext(ctx, ext, t, c.xp);
         if (st != GX_OK) return st;
     }
-    if (jext)
+    if (c.jext)
     {
-        gx_status st = gbj_plan_ext(ctx, d, jext, *jp);
+        gx_status st = gbj_plan_ext(ctx, d, c.jext, c.jp);
         if (st != GX_OK) return st;
     }
     a = gbd_args{};
@@ -8342,13 +8341,13 @@ static gx_status gbd_plan(gx_ctx *ctx, const gx_gb_desc *d, const gx_table *t,
     /* validate everything before the first flatten launches */
     for (int k = 0; t && k < d->nkeys; k++)
     {
-        int c = d->key_cols[k];
-        const gx_table *kt = jext ? jp->table(t, jext->key_side[k]) : t;
-        if (c < 0 || c >= (int) kt->cols.size())
-            return gbd_invalid(ctx, "key %ld: column %ld out of range", k, c);
-        if (!gbd_int_width(kt->cols[c].m.width))
+        const int col = d->key_cols[k];
+        const gx_table *kt = c.key_table(k);
+        if (col < 0 || col >= (int) kt->cols.size())
+            return gbd_invalid(ctx, "key %ld: column %ld out of range", k, col);
+        if (!gbd_int_width(kt->cols[col].m.width))
             return gbd_invalid(ctx, "key %ld: column width %ld is not 1, 2, 4 or 8",
-                               k, kt->cols[c].m.width);
+                               k, kt->cols[col].m.width);
     }
     int words = 0;
     for (int j = 0; j < d->naggs; j++)
@@ -8365,7 +8364,7 @@ static gx_status gbd_plan(gx_ctx *ctx, const gx_gb_desc *d, const gx_table *t,
                                    ae, ext->nexprs - 1);
             if (ae >= 0 && g.fn == GX_AGG_COUNT_STAR)
                 return gbd_invalid(ctx, "aggregate %ld: agg_expr %ld on COUNT(*)", j, ae);
-            xp->x.aexpr[j] = ae;
+            c.xp.x.aexpr[j] = ae;
         }
         /* an expression aggregate is "float8 of that fn": col is not read */
         if (ae >= 0) g.is_f64 = 1;
@@ -8378,7 +8377,7 @@ static gx_status gbd_plan(gx_ctx *ctx, const gx_gb_desc *d, const gx_table *t,
         int w = ae >= 0 ? 8 : 0;
         if (t && ae < 0)
         {
-            const gx_table *at = jext ? jp->table(t, jext->agg_side[j]) : t;
+            const gx_table *at = c.agg_table(j);
             if (g.col < 0 || g.col >= (int) at->cols.size())
                 return gbd_invalid(ctx, "aggregate %ld: column %ld out of range", j, g.col);
             w = at->cols[g.col].m.width;
@@ -8446,41 +8445,42 @@ extern "C" int64_t gx_gbd_wire_stride(const gx_gb_desc *d)
 }
 
 /* BIND: flatten every column the plan reads */
-static gx_status gbd_bind(gx_ctx *ctx, const gx_gb_desc *d, gbd_inputs &in,
-                          gbd_args &a, gbd_xplan *xp, gbj_plan *jp = nullptr)
+static gx_status gbd_bind(gx_ctx *ctx, gbd_call &c)
 {
-    const gx_table *t = d->t;
-    const bool ex = xp && xp->on;
-    const bool jn = jp && jp->on;
+    const gx_gb_desc *d = c.d;
+    const gx_table *t = c.t;
+    gbd_args &a = c.a;
+    gbj_plan &jp = c.jp;
     gx_status st;
     /* a dim-side key or aggregate binds the dimension's column */
     auto bind_side = [&](int side, int col, gbd_col *out) {
-        return side == 0 ? gbd_bind_col(ctx, t, col, in, out)
-                         : gbd_bind_col(ctx, jp->ext->joins[side - 1].dim, col,
-                                        jp->din[side - 1], out);
+        return side == 0 ? gbd_bind_col(ctx, t, col, c.in, out)
+                         : gbd_bind_col(ctx, jp.ext->joins[side - 1].dim, col,
+                                        jp.din[side - 1], out);
     };
     for (int k = 0; k < d->nkeys; k++)
-        if ((st = bind_side(jn ? jp->jx.key_side[k] : 0, d->key_cols[k],
-                            &a.key[k])) != GX_OK) return st;
-    for (int j = 0; j < d->naggs; j++)
-        if (d->aggs[j].fn != GX_AGG_COUNT_STAR && !(ex && xp->x.aexpr[j] >= 0) &&
-            (st = bind_side(jn ? jp->jx.agg_side[j] : 0, d->aggs[j].col,
-                            &a.agg[j])) != GX_OK) return st;
-    for (int q = 0; q < d->nquals; q++)
-        if ((st = gbd_bind_col(ctx, t, d->quals[q].col, in, &a.qual[q])) != GX_OK) return st;
-    for (int o = 0; ex && o < xp->x.nopnd; o++)
-        if ((st = gbd_bind_col(ctx, t, xp->opnd_col[o], in, &xp->x.opnd[o])) != GX_OK) return st;
-    for (int j = 0; jn && j < jp->jx.njoins; j++)
-    {
-        const gx_gb_join &J = jp->ext->joins[j];
-        if ((st = gbd_bind_col(ctx, t, J.fact_col, in, &jp->jx.j[j].fact)) != GX_OK ||
-            (st = gbd_bind_col(ctx, J.dim, J.dim_key_col, jp->din[j],
-                               &jp->jx.j[j].dkey)) != GX_OK)
+        if ((st = bind_side(jp.jx.key_side[k], d->key_cols[k], &a.key[k])) != GX_OK)
             return st;
-        jp->b[j].key = jp->jx.j[j].dkey;
+    for (int j = 0; j < d->naggs; j++)
+        if (c.agg_reads_col(j) &&
+            (st = bind_side(jp.jx.agg_side[j], d->aggs[j].col, &a.agg[j])) != GX_OK)
+            return st;
+    for (int q = 0; q < d->nquals; q++)
+        if ((st = gbd_bind_col(ctx, t, d->quals[q].col, c.in, &a.qual[q])) != GX_OK) return st;
+    for (int o = 0; c.xp.on && o < c.xp.x.nopnd; o++)
+        if ((st = gbd_bind_col(ctx, t, c.xp.opnd_col[o], c.in, &c.xp.x.opnd[o])) != GX_OK)
+            return st;
+    for (int j = 0; j < jp.jx.njoins; j++)
+    {
+        const gx_gb_join &J = jp.ext->joins[j];
+        if ((st = gbd_bind_col(ctx, t, J.fact_col, c.in, &jp.jx.j[j].fact)) != GX_OK ||
+            (st = gbd_bind_col(ctx, J.dim, J.dim_key_col, jp.din[j],
+                               &jp.jx.j[j].dkey)) != GX_OK)
+            return st;
+        jp.b[j].key = jp.jx.j[j].dkey;
         for (int q = 0; q < J.nquals; q++)
-            if ((st = gbd_bind_col(ctx, J.dim, J.quals[q].col, jp->din[j],
-                                   &jp->b[j].qual[q])) != GX_OK) return st;
+            if ((st = gbd_bind_col(ctx, J.dim, J.quals[q].col, jp.din[j],
+                                   &jp.b[j].qual[q])) != GX_OK) return st;
     }
     return GX_OK;
 }
@@ -8488,30 +8488,31 @@ static gx_status gbd_bind(gx_ctx *ctx, const gx_gb_desc *d, gbd_inputs &in,
 /* bytes a join scan allocates beside the group table: the join tables and the
  * flat copies (value and validity bytes) gbd_bind materialises for format-1
  * dimension columns; for the budget check before anything is bound */
-static uint64_t gbj_bytes(const gx_gb_desc *d, const gbd_xplan *xp, const gbj_plan *jp)
+static uint64_t gbj_bytes(const gbd_call &c)
 {
-    if (!jp || !jp->on) return 0;
+    const gx_gb_desc *d = c.d;
+    const gbj_plan &jp = c.jp;
+    if (!jp.on) return 0;
     uint64_t b = 64;
     std::set<std::pair<int, int>> seen;
-    auto col = [&](int j, int c) {
-        const gx_table *dim = jp->ext->joins[j].dim;
-        if (dim->cols[c].format != 0 && seen.insert({j, c}).second)
+    auto col = [&](int j, int cc) {
+        const gx_table *dim = jp.ext->joins[j].dim;
+        if (dim->cols[cc].format != 0 && seen.insert({j, cc}).second)
             b += GX_AOCS_DATUM_OFF + (uint64_t) std::max<int64_t>(dim->nrows, 1) *
-                                         (uint64_t) (dim->cols[c].m.width + 1);
+                                         (uint64_t) (dim->cols[cc].m.width + 1);
     };
-    for (int j = 0; j < jp->jx.njoins; j++)
+    for (int j = 0; j < jp.jx.njoins; j++)
     {
-        b += jp->nslots[j] * 4;
-        col(j, jp->ext->joins[j].dim_key_col);
-        for (int q = 0; q < jp->ext->joins[j].nquals; q++)
-            col(j, jp->ext->joins[j].quals[q].col);
+        b += jp.nslots[j] * 4;
+        col(j, jp.ext->joins[j].dim_key_col);
+        for (int q = 0; q < jp.ext->joins[j].nquals; q++)
+            col(j, jp.ext->joins[j].quals[q].col);
     }
     for (int k = 0; k < d->nkeys; k++)
-        if (jp->jx.key_side[k]) col(jp->jx.key_side[k] - 1, d->key_cols[k]);
+        if (jp.jx.key_side[k]) col(jp.jx.key_side[k] - 1, d->key_cols[k]);
     for (int j = 0; j < d->naggs; j++)
-        if (jp->jx.agg_side[j] && d->aggs[j].fn != GX_AGG_COUNT_STAR &&
-            !(xp && xp->on && xp->x.aexpr[j] >= 0))
-            col(jp->jx.agg_side[j] - 1, d->aggs[j].col);
+        if (jp.jx.agg_side[j] && c.agg_reads_col(j))
+            col(jp.jx.agg_side[j] - 1, d->aggs[j].col);
     return b;
 }
 
@@ -8566,12 +8567,12 @@ static gx_status gbj_build(gx_ctx *ctx, gbj_plan &jp)
 
 /* bytes gbd_bind materialises for the operand columns (format 1: a flat
  * copy and validity bytes), for the budget check before anything is bound */
-static uint64_t gbd_operand_flat_bytes(const gx_table *t, const gbd_xplan *xp)
+static uint64_t gbd_operand_flat_bytes(const gbd_call &c)
 {
     uint64_t b = 0;
-    for (int o = 0; xp && xp->on && o < xp->x.nopnd; o++)
-        if (t->cols[xp->opnd_col[o]].format != 0)
-            b += GX_AOCS_DATUM_OFF + (uint64_t) std::max<int64_t>(t->nrows, 1) * 9;
+    for (int o = 0; c.xp.on && o < c.xp.x.nopnd; o++)
+        if (c.t->cols[c.xp.opnd_col[o]].format != 0)
+            b += GX_AOCS_DATUM_OFF + (uint64_t) std::max<int64_t>(c.t->nrows, 1) * 9;
     return b;
 }
 
@@ -8584,10 +8585,32 @@ struct gbd_table {
     uint64_t tslots = 0;
     int64_t bound = 0;
     size_t sw = 4;                 /* bytes of the slot word */
+    unsigned long long hm[5] = {}; /* misc on the host: read_stats, then a sync */
     unsigned long long *stat() const { return misc.as<unsigned long long>(); }
     unsigned long long *cursor() const { return stat() + 2; }
     int *err() const { return (int *) (stat() + 3); }
+    /* enqueue the one copy of the stat words a call makes */
+    hipError_t read_stats(hipStream_t s)
+    { return hipMemcpyAsync(hm, misc.p, sizeof hm, hipMemcpyDeviceToHost, s); }
+    int64_t ngroups() const { return (int64_t) hm[2]; }
 };
+
+/* the rule for the slot word: 8 bytes from 2^32 - 1 rows on, or when a test
+ * seam forces it */
+static bool gbd_wide(int64_t nrows, bool force)
+{
+    return force || nrows >= (int64_t) UINT32_MAX;
+}
+
+/* the overflow verdict on a table whose stat words are on the host: the
+ * bounded walk ran out, or the extract counted more groups than the table
+ * was sized for (bound never exceeds a positive max_groups) */
+static gx_status gbd_verdict(gx_ctx *ctx, const gbd_table &T)
+{
+    if (!(T.hm[3] & 1) && T.ngroups() <= T.bound) return GX_OK;
+    set_err(ctx, "groupby_desc: more groups than max_groups%s", "");
+    return GX_ERR_INVALID;
+}
 
 /* HBM budget of a table for up to `bound` groups at a fill of 1/2 at most,
  * plus `extra` bytes the caller allocates beside it */
@@ -8642,46 +8665,58 @@ static void gbd_extract(gx_ctx *ctx, const gbd_args &a, const SRC &src, gbd_tabl
     });
 }
 
+/* what a production entry point and its test seam differ in: the scan
+ * kernel's grid and whether the 8-byte slot word is forced */
+struct gbd_launch {
+    int grid;
+    bool force_wide;
+};
+static const gbd_launch GBD_PRODUCTION = {GRID, false};
+static gbd_launch gbd_test_launch(int grid, int wide_rowid)
+{
+    return gbd_launch{grid == 0 ? GRID : grid, wide_rowid != 0};
+}
+
+static bool gbd_env_lds() { return env_int("GX_GB_LDS", 1) != 0; }
+
 /* SCAN stage of a planned call: budget, bind, table, k_groupby_desc (between
  * e0 and e1 when given), extract.  Enqueue only: the group count and the
  * error word stay on the device (T.misc) until the caller syncs.  extra:
  * bytes the caller allocates beside the table. */
-static gx_status gbd_scan_stage(gx_ctx *ctx, const gx_gb_desc *d, gbd_args &a,
-                                gbd_inputs &in, gbd_table &T, int grid, bool wide,
-                                bool lds, uint64_t extra, hipEvent_t e0,
-                                hipEvent_t e1, gbd_xplan *xp = nullptr,
-                                gbj_plan *jp = nullptr)
+static gx_status gbd_scan_stage(gx_ctx *ctx, gbd_call &c, gbd_table &T,
+                                const gbd_launch &launch, uint64_t extra,
+                                hipEvent_t e0, hipEvent_t e1)
 {
+    const gbd_args &a = c.a;
+    const int grid = launch.grid;
     if (grid < 1) return gbd_invalid(ctx, "grid %ld", grid);
     /* sizing: the table holds up to `bound` groups */
-    const int64_t n = d->t->nrows;
+    const int64_t n = c.t->nrows;
     const int64_t bound = std::max<int64_t>(
-        1, d->max_groups > 0 ? std::min<int64_t>(d->max_groups, n) : n);
-    if (!wide && n >= (int64_t) UINT32_MAX)
-        return gbd_invalid(ctx, "%ld rows need the 8-byte slot word", (long) n);
-    const bool jn = jp && jp->on;
+        1, c.d->max_groups > 0 ? std::min<int64_t>(c.d->max_groups, n) : n);
+    const bool wide = gbd_wide(n, launch.force_wide);
+    const bool lds = gbd_env_lds(), jn = c.jp.on;
     gx_status st = gbd_table_budget(ctx, a, bound, wide,
-                                    extra + gbd_operand_flat_bytes(d->t, xp) +
-                                        gbj_bytes(d, xp, jp),
+                                    extra + gbd_operand_flat_bytes(c) + gbj_bytes(c),
                                     jn ? "groupby_desc table and join tables"
                                        : "groupby_desc table");
     if (st != GX_OK) return st;
-    if ((st = gbd_bind(ctx, d, in, a, xp, jp)) != GX_OK) return st;
-    if (jn && (st = gbj_build(ctx, *jp)) != GX_OK) return st;
+    if ((st = gbd_bind(ctx, c)) != GX_OK) return st;
+    if (jn && (st = gbj_build(ctx, c.jp)) != GX_OK) return st;
     if ((st = gbd_table_alloc(ctx, T, a, bound, wide)) != GX_OK) return st;
     hipStream_t s = ctx->stream;
     const size_t lds_bytes = lds ? (size_t) a.lds_slots * ((size_t) a.awords * 8 + T.sw) : 0;
     if (e0) HIP_CHK(ctx, hipEventRecord(e0, s));
     by_width((int) T.sw, T.trow.p, [&](auto *rows) {
         by_flag(lds, [&](auto use_lds) {
-            by_flag(xp && xp->on, [&](auto use_expr) {
+            by_flag(c.xp.on, [&](auto use_expr) {
                 by_flag(jn, [&](auto use_join) {
                     constexpr bool EX = decltype(use_expr)::value;
                     constexpr bool JN = decltype(use_join)::value;
                     std::conditional_t<EX, gbd_xargs, gbd_noexpr> x{};
                     std::conditional_t<JN, gbd_jargs, gbd_nojoin> jx{};
-                    if constexpr (EX) x = xp->x;
-                    if constexpr (JN) jx = jp->jx;
+                    if constexpr (EX) x = c.xp.x;
+                    if constexpr (JN) jx = c.jp.jx;
                     hipLaunchKernelGGL((k_groupby_desc<std::decay_t<decltype(*rows)>,
                                                        decltype(use_lds)::value, EX, JN>),
                                        dim3(grid), dim3(TPB), lds_bytes, s, a, x, jx,
@@ -8692,7 +8727,7 @@ static gx_status gbd_scan_stage(gx_ctx *ctx, const gx_gb_desc *d, gbd_args &a,
         });
     });
     if (e1) HIP_CHK(ctx, hipEventRecord(e1, s));
-    if (jn) gbd_extract(ctx, a, gbd_key_join_args{jp->jx}, T);
+    if (jn) gbd_extract(ctx, a, gbd_key_join_args{c.jp.jx}, T);
     else gbd_extract(ctx, a, gbd_key_cols{}, T);
     return GX_OK;
 }
@@ -8707,20 +8742,16 @@ struct gbd_host_groups {
 
 /* the table's stat words (one sync), the overflow verdict, then its ng
  * compacted groups */
-static gx_status gbd_fetch(gx_ctx *ctx, const gbd_args &a, const gbd_table &T,
-                           int64_t max_groups, unsigned long long (&hm)[4],
+static gx_status gbd_fetch(gx_ctx *ctx, const gbd_args &a, gbd_table &T,
                            gbd_host_groups &H)
 {
     hipStream_t s = ctx->stream;
-    HIP_CHK(ctx, hipMemcpyAsync(hm, T.misc.p, 32, hipMemcpyDeviceToHost, s));
+    HIP_CHK(ctx, T.read_stats(s));
     HIP_CHK(ctx, hipStreamSynchronize(s));
     HIP_CHK(ctx, hipGetLastError());
-    const int64_t ng = (int64_t) hm[2];
-    if ((hm[3] & 1) || ng > T.bound || (max_groups > 0 && ng > max_groups))
-    {
-        set_err(ctx, "groupby_desc: more groups than max_groups%s", "");
-        return GX_ERR_INVALID;
-    }
+    gx_status st = gbd_verdict(ctx, T);
+    if (st != GX_OK) return st;
+    const int64_t ng = T.ngroups();
     const int nk = a.nkeys, words = a.awords;
     H.ng = ng;
     H.k.resize((size_t) ng * nk);
@@ -8805,103 +8836,6 @@ static gx_status gbd_check_call(gx_ctx *ctx, const gx_gb_desc *d, gx_gb_result *
     return GX_OK;
 }
 
-/* The one-stage plan: plan, bind, scan, extract, finish.  grid and wide come
- * from the caller (production: GRID, nrows >= 2^32 - 1), lds from GX_GB_LDS,
- * so the public call and the test entry run the same launches. */
-static gx_status gbd_run(gx_ctx *ctx, const gx_gb_desc *d, int grid, bool wide,
-                         bool lds, gx_gb_result *out, gx_gbd_stats *stats,
-                         const gx_gb_ext *ext = nullptr,
-                         const gx_gbj_ext *jext = nullptr,
-                         gx_gbj_stats *jstats = nullptr)
-{
-    gx_status st = gbd_check_call(ctx, d, out);
-    if (stats) memset(stats, 0, sizeof *stats);
-    if (jstats) memset(jstats, 0, sizeof *jstats);
-    if (st != GX_OK) return st;
-    gbd_args a;
-    gbd_xplan xp;
-    gbj_plan jp;
-    if ((st = gbd_plan(ctx, d, d->t, a, ext, &xp, jext, &jp)) != GX_OK) return st;
-    gbd_inputs in;
-    gbd_table T;
-    evholder e0, e1;
-    HIP_CHK(ctx, e0.create()); HIP_CHK(ctx, e1.create());
-    st = gbd_scan_stage(ctx, d, a, in, T, grid, wide, lds, 0, e0, e1, &xp, &jp);
-    if (st != GX_OK) return st;
-    const int64_t n = d->t->nrows;
-    unsigned long long hm[4] = {0, 0, 0, 0};
-    gbd_host_groups H;
-    if ((st = gbd_fetch(ctx, a, T, d->max_groups, hm, H)) != GX_OK) return st;
-    if ((st = gbd_finish(a, H, true, out)) != GX_OK) return st;
-    if (stats)
-    {
-        float ms = 0;
-        (void) hipEventElapsedTime(&ms, e0, e1);
-        stats->ms_kernel = (double) ms;
-        stats->rows_in = n;
-        stats->rows_pass = (int64_t) hm[0];
-        stats->rows_lds = (int64_t) hm[1];
-        stats->rows_global = (int64_t) (hm[0] - hm[1]);
-        stats->groups = out->ngroups;
-    }
-    if (jstats)
-    {
-        float ms = 0;
-        (void) hipEventElapsedTime(&ms, e0, e1);
-        /* without a join every row the quals leave "reaches the probes" */
-        unsigned long long probed = hm[0];
-        if (jp.on)
-            HIP_CHK(ctx, hipMemcpy(&probed, T.stat() + 4, 8, hipMemcpyDeviceToHost));
-        jstats->ms_build = jp.ms_build;
-        jstats->ms_kernel = (double) ms;
-        jstats->rows_in = n;
-        jstats->rows_probed = (int64_t) probed;
-        jstats->rows_pass = (int64_t) hm[0];
-        jstats->rows_lds = (int64_t) hm[1];
-        jstats->rows_global = (int64_t) (hm[0] - hm[1]);
-        jstats->groups = out->ngroups;
-        for (int j = 0; j < jp.jx.njoins; j++) jstats->dim_rows[j] = jp.dim_rows[j];
-    }
-    return GX_OK;
-}
-
-static bool gbd_env_lds() { return env_int("GX_GB_LDS", 1) != 0; }
-
-extern "C" gx_status gx_groupby_desc(gx_ctx *ctx, const gx_gb_desc *d,
-                                     gx_gb_result *out, gx_gbd_stats *stats)
-{
-    bool wide = d && d->t && d->t->nrows >= (int64_t) UINT32_MAX;
-    return gbd_run(ctx, d, GRID, wide, gbd_env_lds(), out, stats);
-}
-
-extern "C" gx_status gx_test_groupby_desc(gx_ctx *ctx, const gx_gb_desc *d,
-                                          int grid, int wide_rowid,
-                                          gx_gb_result *out, gx_gbd_stats *stats)
-{
-    bool wide = wide_rowid != 0 ||
-                (d && d->t && d->t->nrows >= (int64_t) UINT32_MAX);
-    return gbd_run(ctx, d, grid == 0 ? GRID : grid, wide, gbd_env_lds(), out, stats);
-}
-
-extern "C" gx_status gx_groupby_expr(gx_ctx *ctx, const gx_gb_desc *d,
-                                     const gx_gb_ext *ext, gx_gb_result *out,
-                                     gx_gbd_stats *stats)
-{
-    bool wide = d && d->t && d->t->nrows >= (int64_t) UINT32_MAX;
-    return gbd_run(ctx, d, GRID, wide, gbd_env_lds(), out, stats, ext);
-}
-
-extern "C" gx_status gx_test_groupby_expr(gx_ctx *ctx, const gx_gb_desc *d,
-                                          const gx_gb_ext *ext, int grid,
-                                          int wide_rowid, gx_gb_result *out,
-                                          gx_gbd_stats *stats)
-{
-    bool wide = wide_rowid != 0 ||
-                (d && d->t && d->t->nrows >= (int64_t) UINT32_MAX);
-    return gbd_run(ctx, d, grid == 0 ? GRID : grid, wide, gbd_env_lds(), out, stats,
-                   ext);
-}
-
 /* the join entry points need their join descriptor */
 static gx_status gbj_check_call(gx_ctx *ctx, const gx_gbj_ext *jext, gx_gb_result *out)
 {
@@ -8911,14 +8845,92 @@ static gx_status gbj_check_call(gx_ctx *ctx, const gx_gbj_ext *jext, gx_gb_resul
     return GX_ERR_INVALID;
 }
 
+/* The one-stage plan: plan, bind, scan, extract, finish.  The public call
+ * and the test entry run the same launches; they differ in `launch` alone.
+ * stats (may be null) is the superset gx_gbj_stats for every family. */
+static gx_status gbd_run(gx_ctx *ctx, const gx_gb_desc *d, const gx_gb_ext *ext,
+                         const gx_gbj_ext *jext, const gbd_launch &launch,
+                         gx_gb_result *out, gx_gbj_stats *stats)
+{
+    gx_status st = gbd_check_call(ctx, d, out);
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (st != GX_OK) return st;
+    gbd_call c(d, d->t, ext, jext);
+    if ((st = gbd_plan(ctx, c)) != GX_OK) return st;
+    gbd_table T;
+    evholder e0, e1;
+    HIP_CHK(ctx, e0.create()); HIP_CHK(ctx, e1.create());
+    if ((st = gbd_scan_stage(ctx, c, T, launch, 0, e0, e1)) != GX_OK) return st;
+    gbd_host_groups H;
+    if ((st = gbd_fetch(ctx, c.a, T, H)) != GX_OK) return st;
+    if ((st = gbd_finish(c.a, H, true, out)) != GX_OK) return st;
+    if (stats)
+    {
+        float ms = 0;
+        (void) hipEventElapsedTime(&ms, e0, e1);
+        stats->ms_build = c.jp.ms_build;
+        stats->ms_kernel = (double) ms;
+        stats->rows_in = c.t->nrows;
+        /* without a join every row the quals leave "reaches the probes" */
+        stats->rows_probed = (int64_t) (c.jp.on ? T.hm[4] : T.hm[0]);
+        stats->rows_pass = (int64_t) T.hm[0];
+        stats->rows_lds = (int64_t) T.hm[1];
+        stats->rows_global = (int64_t) (T.hm[0] - T.hm[1]);
+        stats->groups = out->ngroups;
+        for (int j = 0; j < c.jp.jx.njoins; j++) stats->dim_rows[j] = c.jp.dim_rows[j];
+    }
+    return GX_OK;
+}
+
+/* gbd_run for the join-less families, whose gx_gbd_stats is the part of
+ * gx_gbj_stats that needs no join */
+static gx_status gbd_run_nojoin(gx_ctx *ctx, const gx_gb_desc *d, const gx_gb_ext *ext,
+                                const gbd_launch &launch, gx_gb_result *out,
+                                gx_gbd_stats *stats)
+{
+    gx_gbj_stats js;
+    gx_status st = gbd_run(ctx, d, ext, nullptr, launch, out, &js);
+    if (stats)
+        *stats = gx_gbd_stats{js.ms_kernel, js.rows_in, js.rows_pass, js.rows_lds,
+                              js.rows_global, js.groups};
+    return st;
+}
+
+extern "C" gx_status gx_groupby_desc(gx_ctx *ctx, const gx_gb_desc *d,
+                                     gx_gb_result *out, gx_gbd_stats *stats)
+{
+    return gbd_run_nojoin(ctx, d, nullptr, GBD_PRODUCTION, out, stats);
+}
+
+extern "C" gx_status gx_test_groupby_desc(gx_ctx *ctx, const gx_gb_desc *d,
+                                          int grid, int wide_rowid,
+                                          gx_gb_result *out, gx_gbd_stats *stats)
+{
+    return gbd_run_nojoin(ctx, d, nullptr, gbd_test_launch(grid, wide_rowid), out, stats);
+}
+
+extern "C" gx_status gx_groupby_expr(gx_ctx *ctx, const gx_gb_desc *d,
+                                     const gx_gb_ext *ext, gx_gb_result *out,
+                                     gx_gbd_stats *stats)
+{
+    return gbd_run_nojoin(ctx, d, ext, GBD_PRODUCTION, out, stats);
+}
+
+extern "C" gx_status gx_test_groupby_expr(gx_ctx *ctx, const gx_gb_desc *d,
+                                          const gx_gb_ext *ext, int grid,
+                                          int wide_rowid, gx_gb_result *out,
+                                          gx_gbd_stats *stats)
+{
+    return gbd_run_nojoin(ctx, d, ext, gbd_test_launch(grid, wide_rowid), out, stats);
+}
+
 extern "C" gx_status gx_groupby_join(gx_ctx *ctx, const gx_gb_desc *d,
                                      const gx_gbj_ext *jext, const gx_gb_ext *ext,
                                      gx_gb_result *out, gx_gbj_stats *stats)
 {
     gx_status st = gbj_check_call(ctx, jext, out);
     if (st != GX_OK) return st;
-    bool wide = d && d->t && d->t->nrows >= (int64_t) UINT32_MAX;
-    return gbd_run(ctx, d, GRID, wide, gbd_env_lds(), out, nullptr, ext, jext, stats);
+    return gbd_run(ctx, d, ext, jext, GBD_PRODUCTION, out, stats);
 }
 
 extern "C" gx_status gx_test_groupby_join(gx_ctx *ctx, const gx_gb_desc *d,
@@ -8929,10 +8941,7 @@ extern "C" gx_status gx_test_groupby_join(gx_ctx *ctx, const gx_gb_desc *d,
 {
     gx_status st = gbj_check_call(ctx, jext, out);
     if (st != GX_OK) return st;
-    bool wide = wide_rowid != 0 ||
-                (d && d->t && d->t->nrows >= (int64_t) UINT32_MAX);
-    return gbd_run(ctx, d, grid == 0 ? GRID : grid, wide, gbd_env_lds(), out, nullptr,
-                   ext, jext, stats);
+    return gbd_run(ctx, d, ext, jext, gbd_test_launch(grid, wide_rowid), out, stats);
 }
 
 /* ---- two-stage descriptor GROUP BY: host side ----
@@ -8940,15 +8949,11 @@ extern "C" gx_status gx_test_groupby_join(gx_ctx *ctx, const gx_gb_desc *d,
 
 /* bit k set: key column k is 8 bytes wide (hashint8; the others hashint4); a
  * dim-side key takes its width from the dimension's column */
-static unsigned gbd_wide_mask(const gx_gb_desc *d, const gx_gbj_ext *jext = nullptr)
+static unsigned gbd_wide_mask(const gbd_call &c)
 {
     unsigned m = 0;
-    for (int k = 0; k < d->nkeys; k++)
-    {
-        const gx_table *kt = jext && jext->key_side[k] > 0
-                                 ? jext->joins[jext->key_side[k] - 1].dim : d->t;
-        if (kt->cols[d->key_cols[k]].m.width == 8) m |= 1u << k;
-    }
+    for (int k = 0; k < c.d->nkeys; k++)
+        if (c.key_table(k)->cols[c.d->key_cols[k]].m.width == 8) m |= 1u << k;
     return m;
 }
 
@@ -8957,41 +8962,63 @@ static int64_t gbd_wire_words(const gbd_args &a)
     return a.nkeys + (a.nkeys ? 1 : 0) + a.awords;
 }
 
-/* grid of the partition kernels: they walk at most T.bound groups */
-static int gbd_part_grid(const gbd_table &T)
+/* PARTITION stage over the compacted groups of a scan table, shared by the
+ * two-stage call and its test seam: the buffers, the histogram launch, and
+ * the emit from the send offsets the caller derives from the histogram(s).
+ * Both walk at most T.bound groups.  Enqueue only. */
+struct gbd_partition {
+    devbuf hist, cur, dest, send;
+    int nsegs = 0;
+    unsigned long long *dhist() const { return hist.as<unsigned long long>(); }
+};
+
+static gx_status gbd_part_hist(gx_ctx *ctx, const gbd_call &c, const gbd_table &T,
+                               int nsegs, gbd_partition &P)
 {
-    return (int) std::min<int64_t>(GRID, (T.bound + TPB - 1) / TPB);
+    hipStream_t s = ctx->stream;
+    P.nsegs = nsegs;
+    HIP_CHK(ctx, P.hist.alloc((size_t) nsegs * 8));
+    HIP_CHK(ctx, P.cur.alloc((size_t) nsegs * 8));
+    HIP_CHK(ctx, P.dest.alloc((size_t) T.bound * 2));
+    HIP_CHK(ctx, hipMemsetAsync(P.hist.p, 0, (size_t) nsegs * 8, s));
+    const int grid = (int) std::min<int64_t>(GRID, (T.bound + TPB - 1) / TPB);
+    hipLaunchKernelGGL(k_gbd_part_hist, dim3(grid), dim3(TPB), (size_t) nsegs * 4, s,
+                       T.okeys.as<int64_t>(), T.oknull.as<uint8_t>(), T.stat(),
+                       T.bound, c.a.nkeys, gbd_wide_mask(c), nsegs,
+                       P.dest.as<uint16_t>(), P.dhist());
+    return GX_OK;
 }
 
-static void gbd_part_hist(gx_ctx *ctx, const gbd_args &a, const gbd_table &T,
-                          unsigned wide, int nsegs, uint16_t *ddest,
-                          unsigned long long *dhist)
+/* send_off[r]: the wire row in P.send where destination r's rows start; e0
+ * (optional) is recorded in front of the kernel */
+static gx_status gbd_part_emit(gx_ctx *ctx, const gbd_call &c, const gbd_table &T,
+                               gbd_partition &P, const unsigned long long *send_off,
+                               uint64_t send_rows, hipEvent_t e0)
 {
-    hipLaunchKernelGGL(k_gbd_part_hist, dim3(gbd_part_grid(T)), dim3(TPB),
-                       (size_t) nsegs * 4, ctx->stream, T.okeys.as<int64_t>(),
-                       T.oknull.as<uint8_t>(), T.stat(), T.bound, a.nkeys, wide,
-                       nsegs, ddest, dhist);
-}
-
-static void gbd_part_emit(gx_ctx *ctx, const gbd_args &a, const gbd_table &T,
-                          int nsegs, const uint16_t *ddest,
-                          unsigned long long *dcur, void *dsend)
-{
-    hipLaunchKernelGGL(k_gbd_part_emit, dim3(gbd_part_grid(T)), dim3(TPB),
-                       (size_t) nsegs * 12, ctx->stream, T.okeys.as<int64_t>(),
-                       T.oknull.as<uint8_t>(), T.oacc.as<unsigned long long>(),
-                       T.stat(), T.bound, a.nkeys, a.awords, nsegs, ddest, dcur,
-                       (unsigned long long *) dsend);
+    hipStream_t s = ctx->stream;
+    HIP_CHK(ctx, P.send.alloc(send_rows * (size_t) gbd_wire_words(c.a) * 8));
+    HIP_CHK(ctx, hipMemcpyAsync(P.cur.p, send_off, (size_t) P.nsegs * 8,
+                                hipMemcpyHostToDevice, s));
+    if (e0) HIP_CHK(ctx, hipEventRecord(e0, s));
+    const int grid = (int) std::min<int64_t>(GRID, (T.bound + TPB - 1) / TPB);
+    hipLaunchKernelGGL(k_gbd_part_emit, dim3(grid), dim3(TPB), (size_t) P.nsegs * 12, s,
+                       T.okeys.as<int64_t>(), T.oknull.as<uint8_t>(),
+                       T.oacc.as<unsigned long long>(), T.stat(), T.bound, c.a.nkeys,
+                       c.a.awords, P.nsegs, P.dest.as<uint16_t>(),
+                       P.cur.as<unsigned long long>(),
+                       P.send.as<unsigned long long>());
+    return GX_OK;
 }
 
 /* COMBINE stage over n device-resident wire rows: budget, table, merge,
  * extract, finish.  ev_done (optional) is recorded after the last kernel. */
-static gx_status gbd_combine(gx_ctx *ctx, const gbd_args &a, int64_t max_groups,
-                             const void *drows, int64_t n, bool wide,
-                             hipEvent_t ev_done, gx_gb_result *out)
+static gx_status gbd_combine(gx_ctx *ctx, const gbd_call &c, const void *drows,
+                             int64_t n, bool force_wide, hipEvent_t ev_done,
+                             gx_gb_result *out)
 {
-    if (!wide && n >= (int64_t) UINT32_MAX)
-        return gbd_invalid(ctx, "%ld rows need the 8-byte slot word", (long) n);
+    const gbd_args &a = c.a;
+    const int64_t max_groups = c.d->max_groups;
+    const bool wide = gbd_wide(n, force_wide);
     /* the table is pow2 >= 2 * recv_rows; the groups are bounded by the
      * rows and by the planner's bound */
     gbd_table T;
@@ -9014,27 +9041,19 @@ static gx_status gbd_combine(gx_ctx *ctx, const gbd_args &a, int64_t max_groups,
         gbd_extract(ctx, a, src, T);
     }
     if (ev_done) HIP_CHK(ctx, hipEventRecord(ev_done, ctx->stream));
-    unsigned long long hm[4] = {0, 0, 0, 0};
     gbd_host_groups H;
-    if ((st = gbd_fetch(ctx, a, T, max_groups, hm, H)) != GX_OK) return st;
+    if ((st = gbd_fetch(ctx, a, T, H)) != GX_OK) return st;
     return gbd_finish(a, H, false, out);
 }
 
-static gx_status gbd_partial_failed(gx_ctx *ctx)
-{
-    set_err(ctx, "groupby_desc: more groups than max_groups%s", "");
-    return GX_ERR_INVALID;
-}
-
-static gx_status gbd_run_dist(gx_ctx *ctx, const gx_gb_desc *d,
-                              const gx_gb_ext *ext, gx_gb_result *out,
-                              gx_gb_stats *stats, const gx_gbj_ext *jext = nullptr)
+static gx_status gbd_run_dist(gx_ctx *ctx, const gx_gb_desc *d, const gx_gb_ext *ext,
+                              const gx_gbj_ext *jext, gx_gb_result *out,
+                              gx_gb_stats *stats)
 {
     gx_status st = gbd_check_call(ctx, d, out);
     if (stats) memset(stats, 0, sizeof *stats);
     if (st != GX_OK) return st;
     const gx_table *t = d->t;
-    const bool wide = t->nrows >= (int64_t) UINT32_MAX;
     gx_gb_stats S{};
     S.rows_in = t->nrows;
     /* one-stage plan: nothing to redistribute on a single segment.
@@ -9042,18 +9061,16 @@ static gx_status gbd_run_dist(gx_ctx *ctx, const gx_gb_desc *d,
      * exchange branch, as in gx_groupby_dist. */
     if (ctx->nsegs == 1 && env_int("GX_FORCE_MOTION", 0) == 0)
     {
-        gx_gbd_stats one{};
-        st = gbd_run(ctx, d, GRID, wide, gbd_env_lds(), out, &one, ext, jext);
+        gx_gbj_stats one;
+        st = gbd_run(ctx, d, ext, jext, GBD_PRODUCTION, out, &one);
         if (st != GX_OK) return st;
         S.ms_partial = one.ms_kernel;
         S.partial_groups = S.final_groups = out->ngroups;
         if (stats) *stats = S;
         return GX_OK;
     }
-    gbd_args a;
-    gbd_xplan xp;
-    gbj_plan jp;
-    if ((st = gbd_plan(ctx, d, t, a, ext, &xp, jext, &jp)) != GX_OK) return st;
+    gbd_call c(d, t, ext, jext);
+    if ((st = gbd_plan(ctx, c)) != GX_OK) return st;
     if (!ctx->comm)
     { set_err(ctx, "nsegs>1 but gx_comm_init not called%s", ""); return GX_ERR_STATE; }
     const int n = ctx->nsegs;
@@ -9071,68 +9088,55 @@ static gx_status gbd_run_dist(gx_ctx *ctx, const gx_gb_desc *d,
 
     /* stage 1: partial agg; the groups, their count and the error word stay
      * on the device */
-    gbd_inputs in;
     gbd_table T;
     const uint64_t side = (uint64_t) std::max<int64_t>(t->nrows, 1) * 2 +
                           (uint64_t) n * (n + 2) * 8;
-    st = gbd_scan_stage(ctx, d, a, in, T, GRID, wide, gbd_env_lds(), side, ev[0],
-                        nullptr, &xp, &jp);
+    st = gbd_scan_stage(ctx, c, T, GBD_PRODUCTION, side, ev[0], nullptr);
     if (st != GX_OK) return st;
     HIP_CHK(ctx, hipEventRecord(ev[1], s));
 
     /* stage 2: partition.  The per-destination histogram goes straight into
      * the all-gather, so ONE host sync yields this rank's send layout, every
      * peer's counts, the partial group count and the error word. */
-    devbuf hist_b, cur_b, all_b, dest_b;
-    HIP_CHK(ctx, hist_b.alloc((size_t) n * 8));
-    HIP_CHK(ctx, cur_b.alloc((size_t) n * 8));
+    gbd_partition P;
+    devbuf all_b;
     HIP_CHK(ctx, all_b.alloc((size_t) n * n * 8));
-    HIP_CHK(ctx, dest_b.alloc((size_t) T.bound * 2));
-    unsigned long long *dhist = hist_b.as<unsigned long long>();
-    HIP_CHK(ctx, hipMemsetAsync(dhist, 0, (size_t) n * 8, s));
-    gbd_part_hist(ctx, a, T, gbd_wide_mask(d, jext), n, dest_b.as<uint16_t>(), dhist);
+    if ((st = gbd_part_hist(ctx, c, T, n, P)) != GX_OK) return st;
     HIP_CHK(ctx, hipEventRecord(ev[2], s));
-    RCCL_CHK(ctx, ncclAllGather(dhist, all_b.p, n, ncclUint64, ctx->comm, s));
+    RCCL_CHK(ctx, ncclAllGather(P.dhist(), all_b.p, n, ncclUint64, ctx->comm, s));
     std::vector<unsigned long long> cnts_all((size_t) n * n);
-    unsigned long long hm[4] = {0, 0, 0, 0};
     HIP_CHK(ctx, hipMemcpyAsync(cnts_all.data(), all_b.p, (size_t) n * n * 8,
                                 hipMemcpyDeviceToHost, s));
-    HIP_CHK(ctx, hipMemcpyAsync(hm, T.misc.p, 32, hipMemcpyDeviceToHost, s));
+    HIP_CHK(ctx, T.read_stats(s));
     HIP_CHK(ctx, hipStreamSynchronize(s));
     HIP_CHK(ctx, hipGetLastError());
-    const bool failed = (hm[3] & 1) || (int64_t) hm[2] > T.bound;
     const gx_mlayout L = m_exchange_layout(cnts_all.data(), n, ctx->seg);
     const unsigned long long send_n = L.send_n, recv_n = L.recv_n;
-    const size_t stride = (size_t) gbd_wire_words(a) * 8;
+    const size_t stride = (size_t) gbd_wire_words(c.a) * 8;
     st = hbm_budget_check(ctx, (send_n + recv_n) * stride + 64,
                           "groupby_desc exchange buffers");
     if (st != GX_OK) return st;
-    devbuf send_b, recv_b;
-    HIP_CHK(ctx, send_b.alloc(send_n * stride));
+    devbuf recv_b;
     HIP_CHK(ctx, recv_b.alloc(recv_n * stride));
-    HIP_CHK(ctx, hipMemcpyAsync(cur_b.p, L.soff.data(), (size_t) n * 8,
-                                hipMemcpyHostToDevice, s));
-    HIP_CHK(ctx, hipEventRecord(ev[3], s));
-    gbd_part_emit(ctx, a, T, n, dest_b.as<uint16_t>(),
-                  cur_b.as<unsigned long long>(), send_b.p);
+    st = gbd_part_emit(ctx, c, T, P, L.soff.data(), send_n, ev[3]);
+    if (st != GX_OK) return st;
     HIP_CHK(ctx, hipEventRecord(ev[4], s));
 
     /* stage 3: exchange */
-    st = m_exchange_payload(ctx, s, send_b.p, recv_b.p, L, stride);
+    st = m_exchange_payload(ctx, s, P.send.p, recv_b.p, L, stride);
     if (st != GX_OK) return st;
     HIP_CHK(ctx, hipEventRecord(ev[5], s));
     /* a failed partial stage sent no rows and is reported only now, after
      * this rank's sends and receives are enqueued, so the peers' matching
      * calls still complete */
-    if (failed)
+    if ((st = gbd_verdict(ctx, T)) != GX_OK)
     {
         HIP_CHK(ctx, hipStreamSynchronize(s));
-        return gbd_partial_failed(ctx);
+        return st;
     }
 
     /* stage 4: combine agg over the received partial states */
-    st = gbd_combine(ctx, a, d->max_groups, recv_b.p, (int64_t) recv_n,
-                     recv_n >= (unsigned long long) UINT32_MAX, ev[6], out);
+    st = gbd_combine(ctx, c, recv_b.p, (int64_t) recv_n, false, ev[6], out);
     if (st != GX_OK) return st;
 
     S.ms_partial = ms_between(ev[0], ev[1]);
@@ -9149,14 +9153,14 @@ static gx_status gbd_run_dist(gx_ctx *ctx, const gx_gb_desc *d,
 extern "C" gx_status gx_groupby_desc_dist(gx_ctx *ctx, const gx_gb_desc *d,
                                           gx_gb_result *out, gx_gb_stats *stats)
 {
-    return gbd_run_dist(ctx, d, nullptr, out, stats);
+    return gbd_run_dist(ctx, d, nullptr, nullptr, out, stats);
 }
 
 extern "C" gx_status gx_groupby_expr_dist(gx_ctx *ctx, const gx_gb_desc *d,
                                           const gx_gb_ext *ext, gx_gb_result *out,
                                           gx_gb_stats *stats)
 {
-    return gbd_run_dist(ctx, d, ext, out, stats);
+    return gbd_run_dist(ctx, d, ext, nullptr, out, stats);
 }
 
 extern "C" gx_status gx_groupby_join_dist(gx_ctx *ctx, const gx_gb_desc *d,
@@ -9166,11 +9170,11 @@ extern "C" gx_status gx_groupby_join_dist(gx_ctx *ctx, const gx_gb_desc *d,
 {
     gx_status st = gbj_check_call(ctx, jext, out);
     if (st != GX_OK) return st;
-    return gbd_run_dist(ctx, d, ext, out, stats, jext);
+    return gbd_run_dist(ctx, d, ext, jext, out, stats);
 }
 
-/* Test ABI: partial agg + partition kernels on one GPU for a given nsegs,
- * through the launch helpers of gx_groupby_desc_dist; jext: the join form */
+/* Test ABI: partial agg + partition on one GPU for a given nsegs, through
+ * the scan and partition stages of gbd_run_dist; jext: the join form */
 static gx_status gbd_test_partial(gx_ctx *ctx, const gx_gb_desc *d,
                                   const gx_gbj_ext *jext, int nsegs,
                                   int64_t *out_counts, void *out_rows,
@@ -9182,49 +9186,36 @@ static gx_status gbd_test_partial(gx_ctx *ctx, const gx_gb_desc *d,
     if (!d->t) { set_err(ctx, "groupby_desc: no table%s", ""); return GX_ERR_INVALID; }
     if (nsegs < 1 || nsegs > GB_MAX_SEGS)
         return gbd_invalid(ctx, "nsegs %ld outside 1..%ld", nsegs, GB_MAX_SEGS);
-    gbd_args a;
-    gbj_plan jp;
-    gx_status st = gbd_plan(ctx, d, d->t, a, nullptr, nullptr, jext, &jp);
+    gbd_call c(d, d->t, nullptr, jext);
+    gx_status st = gbd_plan(ctx, c);
     if (st != GX_OK) return st;
     hipStream_t s = ctx->stream;
-    const bool wide = d->t->nrows >= (int64_t) UINT32_MAX;
-    gbd_inputs in;
     gbd_table T;
     const uint64_t side = (uint64_t) std::max<int64_t>(d->t->nrows, 1) * 2 +
                           (uint64_t) nsegs * 16;
-    st = gbd_scan_stage(ctx, d, a, in, T, GRID, wide, gbd_env_lds(), side, nullptr,
-                        nullptr, nullptr, &jp);
+    st = gbd_scan_stage(ctx, c, T, GBD_PRODUCTION, side, nullptr, nullptr);
     if (st != GX_OK) return st;
-    devbuf hist_b, cur_b, dest_b, send_b;
-    HIP_CHK(ctx, hist_b.alloc((size_t) nsegs * 8));
-    HIP_CHK(ctx, cur_b.alloc((size_t) nsegs * 8));
-    HIP_CHK(ctx, dest_b.alloc((size_t) T.bound * 2));
-    HIP_CHK(ctx, hipMemsetAsync(hist_b.p, 0, (size_t) nsegs * 8, s));
-    gbd_part_hist(ctx, a, T, gbd_wide_mask(d, jext), nsegs, dest_b.as<uint16_t>(),
-                  hist_b.as<unsigned long long>());
+    gbd_partition P;
+    if ((st = gbd_part_hist(ctx, c, T, nsegs, P)) != GX_OK) return st;
     std::vector<unsigned long long> h(nsegs), off(nsegs + 1, 0);
-    unsigned long long hm[4] = {0, 0, 0, 0};
-    HIP_CHK(ctx, hipMemcpyAsync(h.data(), hist_b.p, (size_t) nsegs * 8,
+    HIP_CHK(ctx, hipMemcpyAsync(h.data(), P.hist.p, (size_t) nsegs * 8,
                                 hipMemcpyDeviceToHost, s));
-    HIP_CHK(ctx, hipMemcpyAsync(hm, T.misc.p, 32, hipMemcpyDeviceToHost, s));
+    HIP_CHK(ctx, T.read_stats(s));
     HIP_CHK(ctx, hipStreamSynchronize(s));
     HIP_CHK(ctx, hipGetLastError());
-    if ((hm[3] & 1) || (int64_t) hm[2] > T.bound) return gbd_partial_failed(ctx);
+    if ((st = gbd_verdict(ctx, T)) != GX_OK) return st;
     for (int i = 0; i < nsegs; i++) off[i + 1] = off[i] + h[i];
     const int64_t total = (int64_t) off[nsegs];
     if (total > cap_rows)
     { set_err(ctx, "gbd_partial: output capacity too small%s", ""); return GX_ERR_INVALID; }
-    const size_t stride = (size_t) gbd_wire_words(a) * 8;
+    const size_t stride = (size_t) gbd_wire_words(c.a) * 8;
     st = hbm_budget_check(ctx, (uint64_t) total * stride + 64,
                           "groupby_desc exchange buffers");
     if (st != GX_OK) return st;
-    HIP_CHK(ctx, send_b.alloc((size_t) total * stride));
-    HIP_CHK(ctx, hipMemcpyAsync(cur_b.p, off.data(), (size_t) nsegs * 8,
-                                hipMemcpyHostToDevice, s));
-    gbd_part_emit(ctx, a, T, nsegs, dest_b.as<uint16_t>(),
-                  cur_b.as<unsigned long long>(), send_b.p);
+    st = gbd_part_emit(ctx, c, T, P, off.data(), (uint64_t) total, nullptr);
+    if (st != GX_OK) return st;
     if (total)
-        HIP_CHK(ctx, hipMemcpyAsync(out_rows, send_b.p, (size_t) total * stride,
+        HIP_CHK(ctx, hipMemcpyAsync(out_rows, P.send.p, (size_t) total * stride,
                                     hipMemcpyDeviceToHost, s));
     HIP_CHK(ctx, hipStreamSynchronize(s));
     HIP_CHK(ctx, hipGetLastError());
@@ -9253,17 +9244,15 @@ extern "C" gx_status gx_test_gbj_partial(gx_ctx *ctx, const gx_gb_desc *d,
                             out_total);
 }
 
-/* Test ABI: the combine stage over host-supplied wire rows */
-extern "C" gx_status gx_test_gbd_combine(gx_ctx *ctx, const gx_gb_desc *d,
-                                         const void *rows, int64_t n,
-                                         int wide_rowid, gx_gb_result *out)
+/* Test ABI: the combine stage over host-supplied wire rows (the combine-only
+ * plan: no table) */
+static gx_status gbd_test_combine(gx_ctx *ctx, const gx_gb_desc *d, const void *rows,
+                                  int64_t n, bool force_wide, gx_gb_result *out)
 {
-    if (!ctx || !d || !out || n < 0 || (n > 0 && !rows)) return GX_ERR_INVALID;
-    memset(out, 0, sizeof *out);
-    gbd_args a;
-    gx_status st = gbd_plan(ctx, d, nullptr, a);
+    gbd_call c(d, nullptr, nullptr, nullptr);
+    gx_status st = gbd_plan(ctx, c);
     if (st != GX_OK) return st;
-    const size_t stride = (size_t) gbd_wire_words(a) * 8;
+    const size_t stride = (size_t) gbd_wire_words(c.a) * 8;
     st = hbm_budget_check(ctx, (uint64_t) n * stride + 64,
                           "groupby_desc exchange buffers");
     if (st != GX_OK) return st;
@@ -9272,9 +9261,18 @@ extern "C" gx_status gx_test_gbd_combine(gx_ctx *ctx, const gx_gb_desc *d,
     if (n)
         HIP_CHK(ctx, hipMemcpyAsync(rows_b.p, rows, (size_t) n * stride,
                                     hipMemcpyHostToDevice, ctx->stream));
-    return gbd_combine(ctx, a, d->max_groups, rows_b.p, n,
-                       wide_rowid != 0 || n >= (int64_t) UINT32_MAX, nullptr, out);
+    return gbd_combine(ctx, c, rows_b.p, n, force_wide, nullptr, out);
 }
+
+extern "C" gx_status gx_test_gbd_combine(gx_ctx *ctx, const gx_gb_desc *d,
+                                         const void *rows, int64_t n,
+                                         int wide_rowid, gx_gb_result *out)
+{
+    if (!ctx || !d || !out || n < 0 || (n > 0 && !rows)) return GX_ERR_INVALID;
+    memset(out, 0, sizeof *out);
+    return gbd_test_combine(ctx, d, rows, n, wide_rowid != 0, out);
+}
+
 
 extern "C" int gx_selftest_gbd_route(const int64_t *keys, const uint8_t *key_null,
                                      const int32_t *widths, int nkeys, int64_t n,

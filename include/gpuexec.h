@@ -682,8 +682,8 @@ gx_status gx_groupby_join_dist(gx_ctx *, const gx_gb_desc *, const gx_gbj_ext *,
                                gx_gb_result *out, gx_gb_stats * /* may be NULL */);
 
 /* ---- test-only entry points (parity harness; not part of the drop-in) ---- */
-/* gx_groupby_desc through the same launch helper with the scan grid and the
- * slot word chosen by the caller: grid = 0 is production (2048 workgroups),
+/* gx_groupby_desc through the same planned call (gbd_run) with the scan grid
+ * and the slot word chosen by the caller: grid = 0 is production (2048 workgroups),
  * 1 or 3 make a workgroup see enough of a test-sized input to fill and
  * merge its LDS table; wide_rowid = 1 forces the 8-byte slot word. */
 gx_status gx_test_groupby_desc(gx_ctx *, const gx_gb_desc *, int grid,

@@ -1,5 +1,5 @@
 """GPU tests of the descriptor-form GROUP BY (pytest -m gpu, real MI355X):
-gx_groupby_desc and its test seam against a numpy group-by written here
+gx_groupby_desc and its test seam against the numpy group-by of gb_ref
 (np.unique over a structured (null, value) view plus masked reductions), and
 against gx_groupby / gx_q1, which stay as they are.
 
@@ -8,6 +8,10 @@ integer-valued and small, so every summation order is exact and sums are
 asserted bit-equal."""
 import numpy as np
 import pytest
+
+import gb_ref as G
+from gb_ref import (ref as _ref, same as _same, stream as _stream,
+                    sorted_nulls_last as _sorted_nulls_last)
 
 pytestmark = pytest.mark.gpu
 
@@ -29,116 +33,11 @@ def orc():
     return pyapi
 
 
-# ---------------- binding and the numpy reference ----------------
-
-def _stream(orc, vals, nulls=None, rle=False):
-    """one column as a bind() spec: format 0 when NOT NULL and bindable so
-    (widths 1/4/8), Orig-with-NULLs (format 1) otherwise"""
-    vals = np.ascontiguousarray(vals)
-    n, w = len(vals), vals.itemsize
-    if n == 0:
-        return (b"", w, 0, 1)
-    if rle:
-        assert nulls is None
-        return (orc.aocs_encode_rle(vals), w, n, 1)
-    if nulls is None and w != 2:
-        return (orc.aocs_encode(vals), w, n, 0)
-    if nulls is None:
-        nulls = np.zeros(n, np.bool_)
-    return (orc.aocs_encode_orig_nulls(vals, nulls), w, n, 1)
-
+# ---------------- binding (the numpy reference: gb_ref) ----------------
 
 def _bind(ctx, orc, cols, hidden=None):
-    """cols: list of (values, nulls or None)"""
-    t = ctx.bind([_stream(orc, v, nl) for v, nl in cols])
-    if hidden is not None:
-        t.set_visimap(hidden)
-    return t
-
-
-def _nulls(col):
-    v, nl = col
-    return np.zeros(len(v), np.bool_) if nl is None else np.asarray(nl, np.bool_)
-
-
-def _ref(cols, keys, aggs, mask=None):
-    """numpy GROUP BY over the rows of mask.  cols as for _bind; keys = column
-    indexes; aggs = (fn, col[, is_f64]) as for Context.groupby_desc.  Returns
-    the dict shape groupby_desc returns: groups in np.unique's order over the
-    (null, value) fields, column by column = lexicographic, NULLS LAST."""
-    n = len(cols[0][0]) if cols else 0
-    rows = np.arange(n) if mask is None else np.nonzero(mask)[0]
-    nk = len(keys)
-    if nk:
-        rec = np.zeros(len(rows), [(f"{'nv'[f]}{k}", (np.uint8, np.int64)[f])
-                                   for k in range(nk) for f in (0, 1)])
-        for k, c in enumerate(keys):
-            nl = _nulls(cols[c])[rows]
-            rec[f"n{k}"] = nl
-            rec[f"v{k}"] = np.where(nl, 0, cols[c][0][rows].astype(np.int64))
-        uniq, inv = np.unique(rec, return_inverse=True)
-        inv = inv.reshape(-1)
-        ng = len(uniq)
-        kout = np.stack([uniq[f"v{k}"] for k in range(nk)], axis=1).reshape(ng, nk)
-        knull = np.stack([uniq[f"n{k}"] for k in range(nk)], axis=1).reshape(ng, nk)
-    else:
-        ng, inv = 1, np.zeros(len(rows), np.int64)
-        kout, knull = np.zeros((1, 0), np.int64), np.zeros((1, 0), np.uint8)
-    acols, anull = [], np.zeros((ng, len(aggs)), np.bool_)
-    for j, spec in enumerate(aggs):
-        fn, c = spec[0], spec[1]
-        f64 = len(spec) > 2 and spec[2]
-        if fn == "count*":
-            acols.append(np.bincount(inv, minlength=ng).astype(np.int64))
-            continue
-        ok = ~_nulls(cols[c])[rows]
-        g, v = inv[ok], cols[c][0][rows][ok]
-        cnt = np.bincount(g, minlength=ng).astype(np.int64)
-        if fn == "count":
-            acols.append(cnt)
-            continue
-        anull[:, j] = cnt == 0
-        if fn == "sum":
-            out = np.zeros(ng, np.float64 if f64 else np.int64)
-            np.add.at(out, g, v.astype(out.dtype))
-        elif not f64:
-            v = v.astype(np.int64)
-            out = np.full(ng, INT64_MIN if fn == "max" else INT64_MAX, np.int64)
-            (np.maximum if fn == "max" else np.minimum).at(out, g, v)
-        else:
-            # float8_cmp_internal's order: every NaN equal, above +inf
-            isnan = np.isnan(v)
-            nnan = np.bincount(g[isnan], minlength=ng)
-            out = np.full(ng, -np.inf if fn == "max" else np.inf)
-            (np.maximum if fn == "max" else np.minimum).at(out, g[~isnan], v[~isnan])
-            if fn == "max":
-                out[nnan > 0] = np.nan
-            else:
-                out[(nnan > 0) & (nnan == cnt)] = np.nan
-        out[cnt == 0] = 0
-        acols.append(out)
-    return {"ngroups": ng, "keys": kout, "key_null": knull.astype(np.bool_),
-            "aggs": acols, "agg_null": anull}
-
-
-def _same(a, b):
-    """bit-for-bit equality of two results (NaN payloads excepted)"""
-    assert a["ngroups"] == b["ngroups"]
-    np.testing.assert_array_equal(a["keys"], b["keys"])
-    np.testing.assert_array_equal(a["key_null"], b["key_null"])
-    np.testing.assert_array_equal(a["agg_null"], b["agg_null"])
-    assert len(a["aggs"]) == len(b["aggs"])
-    for x, y in zip(a["aggs"], b["aggs"]):
-        assert x.dtype == y.dtype
-        np.testing.assert_array_equal(x, y)      # NaN == NaN here; -0 == +0
-
-
-def _sorted_nulls_last(res):
-    k, nl = res["keys"], res["key_null"]
-    cols = []
-    for c in range(k.shape[1] - 1, -1, -1):
-        cols += [k[:, c], nl[:, c]]
-    return (np.lexsort(cols) == np.arange(len(k))).all() if cols else True
+    """cols: list of (values, nulls or None); an empty visimap is set too"""
+    return G.bind(ctx, orc, cols, hidden, empty_hidden=True)
 
 
 # ---------------- (1) key shapes, (6) the 8-byte slot word ----------------

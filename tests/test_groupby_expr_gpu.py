@@ -1,7 +1,7 @@
 """GPU tests of the descriptor GROUP BY's float8 expression aggregates and
 float8 quals (pytest -m gpu, real MI355X): gx_groupby_expr, its test seam and
-gx_groupby_expr_dist against a numpy group-by written here (the reference of
-test_groupby_desc_gpu.py, extended by expression columns and float8 quals),
+gx_groupby_expr_dist against the numpy group-by of gb_ref (with expression
+columns and float8 quals),
 against gx_groupby_desc and against gx_q1.
 
 Summed inputs are quarter- and eighth-valued (price = k / 4, disc in {0, .25,
@@ -13,6 +13,10 @@ import os
 
 import numpy as np
 import pytest
+
+import gb_ref as G
+from gb_ref import (bind as _bind, expr_col as _expr_col, fq_mask as _fq_mask,
+                    ref as _ref, same as _same, stream as _stream)
 
 pytestmark = pytest.mark.gpu
 
@@ -32,151 +36,6 @@ def ctx():
 def orc():
     from oracle import pyapi
     return pyapi
-
-
-# ---------------- binding and the numpy reference ----------------
-
-def _stream(orc, vals, nulls=None, rle=False):
-    """one column as a bind() spec: format 0 when NOT NULL and bindable so
-    (widths 1/4/8), Orig-with-NULLs (format 1) otherwise"""
-    vals = np.ascontiguousarray(vals)
-    n, w = len(vals), vals.itemsize
-    if n == 0:
-        return (b"", w, 0, 1)
-    if rle:
-        assert nulls is None
-        return (orc.aocs_encode_rle(vals), w, n, 1)
-    if nulls is None and w != 2:
-        return (orc.aocs_encode(vals), w, n, 0)
-    if nulls is None:
-        nulls = np.zeros(n, np.bool_)
-    return (orc.aocs_encode_orig_nulls(vals, nulls), w, n, 1)
-
-
-def _bind(ctx, orc, cols, rle=()):
-    """cols: list of (values, nulls or None); rle: column indexes bound RLE"""
-    return ctx.bind([_stream(orc, v, nl, rle=i in rle)
-                     for i, (v, nl) in enumerate(cols)])
-
-
-def _nulls(col):
-    v, nl = col
-    return np.zeros(len(v), np.bool_) if nl is None else np.asarray(nl, np.bool_)
-
-
-def _expr_col(cols, factors):
-    """(values, nulls) of ((f0 * f1) * f2), one numpy double operation a step;
-    NULL where any factor's column is"""
-    v, nl = None, np.zeros(len(cols[0][0]), np.bool_)
-    with np.errstate(all="ignore"):
-        for f in factors:
-            form, c = f if isinstance(f, tuple) else ("", f)
-            x = cols[c][0].astype(np.float64)
-            x = {"": x, "1-": 1.0 - x, "1+": 1.0 + x}[form]
-            v = x if v is None else v * x
-            nl = nl | _nulls(cols[c])
-    return v, nl
-
-
-def _f8cmp(x, lit):
-    """float8_cmp_internal(x, lit) per element: NaNs equal, above everything"""
-    xn = np.isnan(x)
-    with np.errstate(invalid="ignore"):
-        c = np.where(x > lit, 1, np.where(x < lit, -1, 0))
-    return np.where(xn, 0, -1) if np.isnan(lit) else np.where(xn, 1, c)
-
-
-_OPS = {"<": lambda c: c < 0, ">": lambda c: c > 0, "==": lambda c: c == 0,
-        "!=": lambda c: c != 0, "<=": lambda c: c <= 0, ">=": lambda c: c >= 0}
-
-
-def _fq_mask(cols, fquals):
-    """rows the AND-ed float8 quals pass; a NULL input fails the row"""
-    m = np.ones(len(cols[0][0]), np.bool_)
-    for c, op, lit in fquals:
-        m &= ~_nulls(cols[c]) & _OPS[op](_f8cmp(cols[c][0].astype(np.float64), lit))
-    return m
-
-
-def _ref(cols, keys, aggs, mask=None):
-    """numpy GROUP BY over the rows of mask.  cols as for _bind; keys = column
-    indexes; aggs = (fn, col[, is_f64]) as for Context.groupby_expr, col a
-    list of factors for an expression aggregate (float8).  Returns the dict
-    shape groupby_desc returns: groups in np.unique's order over the (null,
-    value) fields, column by column = lexicographic, NULLS LAST."""
-    n = len(cols[0][0]) if cols else 0
-    rows = np.arange(n) if mask is None else np.nonzero(mask)[0]
-    nk = len(keys)
-    if nk:
-        rec = np.zeros(len(rows), [(f"{'nv'[f]}{k}", (np.uint8, np.int64)[f])
-                                   for k in range(nk) for f in (0, 1)])
-        for k, c in enumerate(keys):
-            nl = _nulls(cols[c])[rows]
-            rec[f"n{k}"] = nl
-            rec[f"v{k}"] = np.where(nl, 0, cols[c][0][rows].astype(np.int64))
-        uniq, inv = np.unique(rec, return_inverse=True)
-        inv = inv.reshape(-1)
-        ng = len(uniq)
-        kout = np.stack([uniq[f"v{k}"] for k in range(nk)], axis=1).reshape(ng, nk)
-        knull = np.stack([uniq[f"n{k}"] for k in range(nk)], axis=1).reshape(ng, nk)
-    else:
-        ng, inv = 1, np.zeros(len(rows), np.int64)
-        kout, knull = np.zeros((1, 0), np.int64), np.zeros((1, 0), np.uint8)
-    acols, anull = [], np.zeros((ng, len(aggs)), np.bool_)
-    for j, spec in enumerate(aggs):
-        fn, c = spec[0], spec[1]
-        f64 = len(spec) > 2 and spec[2]
-        if fn == "count*":
-            acols.append(np.bincount(inv, minlength=ng).astype(np.int64))
-            continue
-        if isinstance(c, (list, tuple)):
-            col, f64 = _expr_col(cols, c), True
-        else:
-            col = cols[c]
-        ok = ~_nulls(col)[rows]
-        g, v = inv[ok], col[0][rows][ok]
-        cnt = np.bincount(g, minlength=ng).astype(np.int64)
-        if fn == "count":
-            acols.append(cnt)
-            continue
-        anull[:, j] = cnt == 0
-        if fn == "sum":
-            out = np.zeros(ng, np.float64 if f64 else np.int64)
-            np.add.at(out, g, v.astype(out.dtype))
-        elif not f64:
-            v = v.astype(np.int64)
-            out = np.full(ng, INT64_MIN if fn == "max" else INT64_MAX, np.int64)
-            (np.maximum if fn == "max" else np.minimum).at(out, g, v)
-        else:
-            # float8_cmp_internal's order: every NaN equal, above +inf
-            isnan = np.isnan(v)
-            nnan = np.bincount(g[isnan], minlength=ng)
-            out = np.full(ng, -np.inf if fn == "max" else np.inf)
-            (np.maximum if fn == "max" else np.minimum).at(out, g[~isnan], v[~isnan])
-            if fn == "max":
-                out[nnan > 0] = np.nan
-            else:
-                out[(nnan > 0) & (nnan == cnt)] = np.nan
-        out[cnt == 0] = 0
-        acols.append(out)
-    return {"ngroups": ng, "keys": kout, "key_null": knull.astype(np.bool_),
-            "aggs": acols, "agg_null": anull}
-
-
-def _same(a, b):
-    """equality of two results: keys, NULL flags, dtypes and values (NaN equal
-    to NaN, -0 to +0); float8 values that are neither are compared bit for bit"""
-    assert a["ngroups"] == b["ngroups"]
-    np.testing.assert_array_equal(a["keys"], b["keys"])
-    np.testing.assert_array_equal(a["key_null"], b["key_null"])
-    np.testing.assert_array_equal(a["agg_null"], b["agg_null"])
-    assert len(a["aggs"]) == len(b["aggs"])
-    for x, y in zip(a["aggs"], b["aggs"]):
-        assert x.dtype == y.dtype
-        np.testing.assert_array_equal(x, y)
-        if x.dtype == np.float64:
-            m = ~np.isnan(y) & (y != 0)
-            np.testing.assert_array_equal(x.view(np.uint64)[m], y.view(np.uint64)[m])
 
 
 # ---------------- the Q1 / Q6 input ----------------
@@ -571,12 +430,7 @@ def test_matches_gx_q1_revenue(ctx):
 
 def _forced(ctx, t, keys, aggs, **kw):
     """groupby_expr_dist through the FULL exchange branch by self-exchange"""
-    ctx.comm_init(ctx.comm_unique_id())
-    os.environ["GX_FORCE_MOTION"] = "1"
-    try:
-        return ctx.groupby_expr_dist(t, keys, aggs, stats=True, **kw)
-    finally:
-        del os.environ["GX_FORCE_MOTION"]
+    return G.forced(ctx, lambda: ctx.groupby_expr_dist(t, keys, aggs, stats=True, **kw))
 
 
 def test_two_stage_form(ctx, li):

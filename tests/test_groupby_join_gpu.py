@@ -6,8 +6,6 @@ materialises the joined columns and runs the numpy group-by of gb_ref.
 Every float8 measure is a small integer (or a multiple of 0.25 in the
 expression test), so every summation order is exact and results are asserted
 bit-equal."""
-import os
-
 import numpy as np
 import pytest
 
@@ -533,16 +531,6 @@ def test_hbm_budget_counts_the_join_table(ctx, orc, data, monkeypatch):
 
 # ---------------- 12. two-stage form ----------------
 
-def _forced(ctx, call):
-    """through the FULL exchange branch by self-exchange"""
-    ctx.comm_init(ctx.comm_unique_id())
-    os.environ["GX_FORCE_MOTION"] = "1"
-    try:
-        return call()
-    finally:
-        del os.environ["GX_FORCE_MOTION"]
-
-
 def test_two_stage_form(ctx, data):
     fact, d0, d1, t = data
     # key 0: fact column 1 (int64); key 1: dim0 column 1 (int32) -- the FACT
@@ -575,8 +563,8 @@ def test_two_stage_form(ctx, data):
     np.testing.assert_array_equal(d8, np.repeat(np.arange(3), c2))
     assert (gx.gbd_route(r2["keys"], r2["key_null"], [4], 3) != d8).any()
     G.same(ctx.test_gbd_combine(rows, [0, 0], plain), ref)
-    got, st = _forced(ctx, lambda: ctx.groupby_join_dist(t["fact"], keys, aggs, J,
-                                                         stats=True))
+    got, st = G.forced(ctx, lambda: ctx.groupby_join_dist(t["fact"], keys, aggs, J,
+                                                          stats=True))
     G.same(got, want)
     assert st["rows_in"] == len(ok)
     assert (st["sent_rows"] == st["recv_rows"] == st["partial_groups"]
