@@ -98,14 +98,36 @@ static constexpr int TPB = 256;          /* threads per block (4 waves) */
 static constexpr int GRID = 2048;        /* grid-stride grid (fills 256 CUs) */
 static constexpr int ORDERS_GRID = 32768; /* k_orders_build: measured optimum */
 
-/* RAII for TEMPORARY device buffers: early returns (HIP_CHK/RCCL_CHK) free
- * them automatically.  Long-lived state stays owned by gx_table / gx_q3. */
+/* Owning device buffer, move-only.  As a local, early returns
+ * (HIP_CHK/RCCL_CHK) free it; as a member of gx_q3 it is the run state, freed
+ * with the q.  alloc replaces what the buffer held; reserve only ever grows
+ * it (contents are not kept). */
 struct devbuf {
     void *p = nullptr;
-    ~devbuf() { if (p) (void) (void) hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
+    size_t cap = 0;
+    devbuf() = default;
+    devbuf(const devbuf &) = delete;
+    devbuf &operator=(const devbuf &) = delete;
+    devbuf(devbuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    devbuf &operator=(devbuf &&o) noexcept
+    {
+        if (this != &o) { reset(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~devbuf() { reset(); }
+    void reset() { if (p) (void) hipFree(p); p = nullptr; cap = 0; }
+    hipError_t alloc(size_t bytes)
+    {
+        reset();
+        hipError_t e = hipMalloc(&p, bytes ? bytes : 1);
+        if (e == hipSuccess) cap = bytes ? bytes : 1;
+        else p = nullptr;
+        return e;
+    }
+    hipError_t reserve(size_t bytes) { return bytes <= cap ? hipSuccess : alloc(bytes); }
     template <typename T> T *as() const { return (T *) p; }
 };
+static_assert(!std::is_copy_constructible<devbuf>::value, "devbuf owns its allocation");
 
 /* RAII for HIP events: early returns (HIP_CHK/RCCL_CHK/OOM) destroy them
  * automatically instead of accumulating across repeated failing steps */
@@ -3968,92 +3990,175 @@ struct gx_table {
     uint8_t *dvmap = nullptr;    /* device visimap (1 bit/row, ON = hidden) */
 };
 
+/* The device structures of a Q3 run.  Each group below is what a launch
+ * helper takes whole; production (gx_q3) and the test entry points of the
+ * Motion stages hold the same structs, sized by the same rules. */
+
+/* named scratch words, read back on the host after a launch.  Each word has
+ * a 128-byte line of its own: the kernels commit to them with one atomic per
+ * wave, and words that share a line make those atomics queue behind each
+ * other. */
+struct q3_scratch {
+    enum { GROUPS, HITS, ERR, COUNT, KMAX, KMIN, NWORDS };
+    static constexpr int STRIDE = 16;            /* u64 words per line */
+    devbuf buf;
+    hipError_t ensure() { return buf.reserve(NWORDS * STRIDE * 8); }
+    unsigned long long *word(int w) const
+    {
+        return buf.as<unsigned long long>() + w * STRIDE;
+    }
+};
+
+/* what a counting pass leaves in the {COUNT, KMAX, KMIN} words, in that
+ * order; kmin is ~0 when nothing was counted */
+struct q3_keystats {
+    unsigned long long count, kmax, kmin;
+};
+
+/* Clear the {count, kmax, kmin} triple on s, run launch(count, kmax, kmin),
+ * and bring the triple back: one copy (of the span its three lines cover),
+ * one sync. */
+template <typename F>
+static gx_status q3_read_keystats(gx_ctx *ctx, hipStream_t s, const q3_scratch &sc,
+                                  q3_keystats &out, F &&launch)
+{
+    constexpr int ST = q3_scratch::STRIDE;
+    static_assert(q3_scratch::KMAX == q3_scratch::COUNT + 1 &&
+                  q3_scratch::KMIN == q3_scratch::COUNT + 2, "triple is contiguous");
+    unsigned long long *t = sc.word(q3_scratch::COUNT);
+    unsigned long long h[2 * ST + 1];
+    HIP_CHK(ctx, hipMemsetAsync(t, 0, 2 * ST * 8, s));
+    HIP_CHK(ctx, hipMemsetAsync(t + 2 * ST, 0xFF, 8, s));
+    launch(t, t + ST, t + 2 * ST);
+    HIP_CHK(ctx, hipMemcpyAsync(h, t, sizeof h, hipMemcpyDeviceToHost, s));
+    HIP_CHK(ctx, hipStreamSynchronize(s));
+    out = {h[0], h[ST], h[2 * ST]};
+    return GX_OK;
+}
+
+/* dimension membership: hash set + blocked bloom, and for dense keys on a
+ * single segment the exact bitmap over [kmin, kmin+range) as well.  The local
+ * path reads the bitmap INSTEAD of set+bloom; the Motion path keeps
+ * set+bloom, so each run builds only the one its path reads. */
+struct q3_dimset {
+    devbuf set;                      /* u32 or u64 slots, see width */
+    devbuf bloom, bits;
+    int width = 8;
+    uint64_t cmask = 0, bwmask = 0;  /* set slot mask, bloom word-index mask */
+    uint64_t kmin = 0, range = 0;
+    int bitmap = 0;                  /* decided at sizing */
+    gx_dimbits dimbits() const { return {bits.as<unsigned long long>(), kmin, range}; }
+};
+
+/* hash form of the join/agg table.  attrs/aggs: claimed slots only, never
+ * memset — see gx_aggslot */
+struct q3_hashtbl {
+    devbuf keys, attrs, aggs;
+    int width = 8;                   /* key bytes, 4 or 8 */
+    uint64_t mask = 0;
+    gx_slotmap smap{};               /* slot mapping (interpolation or hash) */
+    uint64_t slots() const { return mask + 1; }
+};
+
+/* rank form of the join/agg table (gx_rankview): chosen per run when sizing
+ * found the qualifying mid keys dense (ok); each part is allocated by the
+ * first run that takes it */
+struct q3_ranktbl {
+    int ok = 0, kw = 8;
+    uint64_t kmin = 0, range = 0;
+    devbuf ent;                      /* ulonglong2 {bits, base} per 64 keys */
+    devbuf blk;                      /* u32 per-scan-block popcounts */
+    devbuf dkey, dattr, dagg;        /* dense arrays, one slot per qualifying row */
+    devbuf rowmask;                  /* two-pass orders stage: per mid row */
+    devbuf stage, stage_cur;         /* staged orders stage: records and
+                                        {record cursor, mid-loop flush count} */
+    uint64_t nwords() const { return (range + 63) / 64; }
+    gx_rankview view(int64_t qual) const
+    {
+        return {ent.as<ulonglong2>(), kmin, range, (uint64_t) qual};
+    }
+};
+
+/* LEFT OUTER: unmatched-row aggregation table (biased keys); empty (all
+ * null) for an inner join */
+struct q3_unmatched {
+    devbuf key, rev, cnt;
+    uint64_t mask = 0;
+    int64_t cap = 0;                 /* bound on unmatched groups */
+    hipError_t clear(hipStream_t s) const
+    {
+        hipError_t e = hipMemsetAsync(key.p, 0, (mask + 1) * 8, s);
+        if (e == hipSuccess) e = hipMemsetAsync(rev.p, 0, (mask + 1) * 8, s);
+        if (e == hipSuccess) e = hipMemsetAsync(cnt.p, 0, (mask + 1) * 8, s);
+        return e;
+    }
+};
+
+/* result (device SoA), cap rows */
+struct q3_results {
+    devbuf okey, odate, oprio, rev, cnt;
+    devbuf flags;                    /* per-group key/attr NULL flags */
+    int64_t cap = 0;
+    hipError_t alloc(int64_t rows)
+    {
+        cap = 0;
+        hipError_t e = okey.alloc(rows * 8);
+        if (e == hipSuccess) e = odate.alloc(rows * 4);
+        if (e == hipSuccess) e = oprio.alloc(rows * 4);
+        if (e == hipSuccess) e = rev.alloc(rows * 8);
+        if (e == hipSuccess) e = cnt.alloc(rows * 8);
+        if (e == hipSuccess) e = flags.alloc(rows);
+        if (e == hipSuccess) cap = rows;
+        return e;
+    }
+};
+
 struct gx_q3 {
     gx_ctx *ctx = nullptr;
     gx_table *cust = nullptr, *ord = nullptr, *li = nullptr;
     gx_q3_desc desc{};          /* column roles + filters (plan descriptor) */
     /* run state (device) — allocated on first run, reused across steps
-     * (a re-run rebuilds every table; only the ALLOCATIONS persist) */
+     * (a re-run rebuilds every table; only the ALLOCATIONS persist).  A
+     * sizing that was refused leaves sized false; the next run sizes again
+     * and every buffer replaces what it held. */
     bool sized = false;
-    void *cset = nullptr;            /* u32 or u64 slots, see cset_width */
-    int cset_width = 8;
-    uint64_t cmask = 0;
-    unsigned long long *bloom = nullptr;   /* blocked bloom over cset keys */
-    uint64_t bwmask = 0;                   /* bloom word-index mask */
-    /* exact bitmap over [dim_kmin, dim_kmin+dim_range): allocated when the
-     * dim keys are dense enough (dim_bitmap, decided at sizing); the local
-     * path then builds and reads it INSTEAD of cset+bloom */
-    unsigned long long *dbits = nullptr;
-    uint64_t dim_kmin = 0, dim_range = 0;
-    int dim_bitmap = 0;
+    q3_scratch sc;
+    q3_dimset dim;
     int dim_mode = 0;                /* form the last run's filter read */
-    void *tkey = nullptr;            /* u32 or u64 slots, see key_width */
-    int key_width = 8;
-    gx_slotmap smap{};               /* slot mapping (interpolation or hash) */
-    gx_attrpair *tattr = nullptr;    /* claimed slots only — see gx_aggslot */
-    gx_aggslot *tagg = nullptr;      /* claimed slots only, never memset */
-    uint64_t tmask = 0;
+    q3_hashtbl tbl;
     uint64_t hash_tslots = 0;        /* local path: slots sizing wants; the
                                         hash table itself is allocated by the
                                         first run that needs it */
     int64_t local_qual = 0;          /* sizing's qualifying mid rows (local) */
-    /* rank form of the join/agg table (gx_rankview): chosen per run when
-     * sizing found the qualifying mid keys dense (rank_ok); its storage is
-     * allocated by the first run that takes it */
-    int rank_ok = 0, rank_kw = 8;
+    q3_ranktbl rank;
     int table_mode = 0;              /* form the last run used: 0 hash, 1 rank */
-    uint64_t rank_kmin = 0, rank_range = 0;
-    ulonglong2 *rent = nullptr;            /* {bits, base} per 64 keys */
-    uint32_t *rblk = nullptr;              /* per-scan-block popcounts */
-    unsigned long long *rowmask = nullptr; /* per mid row: qualifies this run
-                                              (two-pass orders stage only) */
-    /* staged orders stage (k_orders_mark<STAGE>): local_qual records and
-     * {record cursor, mid-loop flush count}, allocated by the first run
-     * that takes the form */
-    ulonglong2 *stage = nullptr;
-    unsigned long long *stage_cur = nullptr;
     int orders_mode = 0;             /* form the last rank-form run's orders
                                         stage took: 0 two-pass, 1 staged */
     int64_t test_orders_grid = 0;    /* gx_q3_test_set_orders_grid; 0 = rule */
     int64_t stage_blocks = 0;        /* mark grid of the last staged run */
-    void *dkey = nullptr;                 /* dense arrays, local_qual slots */
-    gx_attrpair *dattr = nullptr;
-    gx_aggslot *dagg = nullptr;
-    unsigned long long *dcount = nullptr, *dhits = nullptr, *dmin = nullptr;
-    /* motion-path exchange state (nsegs>1), cached across steps */
-    unsigned long long *m_hist = nullptr, *m_cur = nullptr;
-    unsigned long long *m_bloom_all = nullptr;   /* all ranks' dim blooms */
-    unsigned long long *m_cnts_mine = nullptr, *m_cnts_all = nullptr;
-    gx_ord_row *m_send1 = nullptr, *m_recv1 = nullptr;
-    gx_qual_row *m_send2 = nullptr, *m_recv2 = nullptr;
-    uint64_t m_send1_cap = 0, m_recv1_cap = 0, m_send2_cap = 0, m_recv2_cap = 0;
-    uint8_t *dtext = nullptr;          /* device dim TEXT literal (texteq) */
-    uint8_t *dmask = nullptr;          /* per-row texteq result (built once
-                                          at prepare over the varlena col) */
+    /* motion-path exchange state (nsegs>1), cached across steps; the
+     * send/recv buffers only grow */
+    devbuf m_hist, m_cur, m_cnts_all;
+    devbuf m_bloom_all;              /* all ranks' dim blooms */
+    devbuf m_send1, m_recv1;         /* gx_ord_row */
+    devbuf m_send2, m_recv2;         /* gx_qual_row */
+    devbuf dtext;                    /* device dim TEXT literal (texteq) */
+    devbuf dmask;                    /* per-row texteq result (built once
+                                        at prepare over the varlena col) */
     /* extra AND-ed quals folded at prepare into per-table HIDDEN bitmaps
      * (combined with the table visimap); kernels read them through the
      * existing visibility parameter — execScan.c:241 qual-list semantics */
-    uint8_t *qvm_dim = nullptr, *qvm_mid = nullptr, *qvm_fact = nullptr;
+    devbuf qvm_dim, qvm_mid, qvm_fact;
     /* flat materializations of null-bearing / RLE role columns (built at
      * prepare; strict-NULL reject folds their validity into the qvm masks) */
     std::map<std::pair<const gx_table *, int>, gx_col> mat;
-    std::vector<void *> mat_mem;
-    /* result (device SoA) */
-    int64_t *r_okey = nullptr;
-    int32_t *r_odate = nullptr, *r_oprio = nullptr;
-    double *r_rev = nullptr;
-    int64_t *r_cnt = nullptr;
-    uint8_t *r_flags = nullptr;      /* per-group key/attr NULL flags */
-    /* LEFT OUTER: unmatched-row aggregation table (biased keys) */
-    unsigned long long *ukey = nullptr, *ucnt_u = nullptr;
-    double *urev = nullptr;
-    uint64_t umask = 0;
-    int64_t u_cap = 0;               /* bound on unmatched groups */
+    std::vector<devbuf> mat_mem;
+    q3_results res;
+    q3_unmatched un;
     int numeric = 0;                 /* numeric(15,2) scaled-i64 measures */
     int empty = 0;                   /* LASJ_NOTIN with a NULL dim key:
                                         the whole result is empty
                                         (nodeHashjoin.c:442) */
-    int64_t rescap = 0;
     int64_t ngroups = 0;
     int64_t qual_orders = 0;
     gx_q3_stats stats{};
@@ -5829,12 +5934,13 @@ static gx_status q3_build_text_mask(gx_ctx *ctx, gx_q3 *q)
     HIP_CHK(ctx, derrb.alloc(4));
     int *derr = derrb.as<int>();
     HIP_CHK(ctx, hipMemsetAsync(derr, 0, 4, s));
-    HIP_CHK(ctx, hipMalloc(&q->dmask, std::max<int64_t>(n, 1)));
+    HIP_CHK(ctx, q->dmask.alloc((size_t) n));
     /* single pass, one texteq per RLE run — no payload materialization
      * (the r1 path decoded the whole column first: 510 ms at SF100) */
     hipLaunchKernelGGL(k_texteq_mask_blocks, dim3(GRID), dim3(64), 0, s,
                        cm.dstream, cm.ddir, cm.nblocks, n,
-                       q->dtext, q->desc.dim_text_len, q->dmask, derr);
+                       q->dtext.as<uint8_t>(), q->desc.dim_text_len,
+                       q->dmask.as<uint8_t>(), derr);
     int herr = 0;
     HIP_CHK(ctx, hipMemcpyAsync(&herr, derr, 4, hipMemcpyDeviceToHost, s));
     HIP_CHK(ctx, hipStreamSynchronize(s));
@@ -5855,7 +5961,7 @@ static inline const gx_col &q3_col(const gx_q3 *q, const gx_table *t, int c)
 }
 
 /* ensure a per-table hidden bitmap exists (seeded from the visimap) */
-static gx_status q3_ensure_hidden(gx_ctx *ctx, gx_table *t, uint8_t **hidden);
+static gx_status q3_ensure_hidden(gx_ctx *ctx, gx_table *t, devbuf *hidden);
 
 /* Decode a Dense/RLE (possibly null-bearing) ROLE column once at prepare
  * into a flat device array readable through the standard gx_col_get
@@ -5864,7 +5970,7 @@ static gx_status q3_ensure_hidden(gx_ctx *ctx, gx_table *t, uint8_t **hidden);
  * join keys (nodeHash.c:2168-2181), NULL-qual filtering for filter columns
  * (execScan.c:241).  The per-step kernels run unchanged. */
 static gx_status q3_materialize_col(gx_ctx *ctx, gx_q3 *q, gx_table *t,
-                                    int cidx, uint8_t **hidden,
+                                    int cidx, devbuf *hidden,
                                     bool fold_nulls = true,
                                     devbuf *val_out = nullptr)
 {
@@ -5909,7 +6015,7 @@ static gx_status q3_materialize_col(gx_ctx *ctx, gx_q3 *q, gx_table *t,
         gx_status rs = q3_ensure_hidden(ctx, t, hidden);
         if (rs != GX_OK) return rs;
         hipLaunchKernelGGL(k_validity_or_hidden, dim3(GRID), dim3(TPB), 0, st,
-                           val.as<uint8_t>(), n, *hidden);
+                           val.as<uint8_t>(), n, hidden->as<uint8_t>());
         HIP_CHK(ctx, hipStreamSynchronize(st));
         HIP_CHK(ctx, hipGetLastError());
     }
@@ -5924,13 +6030,9 @@ static gx_status q3_materialize_col(gx_ctx *ctx, gx_q3 *q, gx_table *t,
     oc.format = 0;
     oc.has_null = c.has_null;    /* sizing consults this (NOTIN emptiness) */
     q->mat[std::make_pair((const gx_table *) t, cidx)] = oc;
-    q->mat_mem.push_back(flat.p);
-    flat.p = nullptr;            /* ownership moves to gx_q3 */
+    q->mat_mem.push_back(std::move(flat));
     if (val_out)                 /* the caller wants the per-row validity */
-    {
-        val_out->p = val.p;
-        val.p = nullptr;
-    }
+        *val_out = std::move(val);
     return GX_OK;
 }
 
@@ -5972,10 +6074,11 @@ static gx_status q3_check_outer_fact_keys(gx_ctx *ctx, gx_q3 *q,
 
 /* fold an AND-ed extra-qual list into a device HIDDEN bitmap (combined with
  * the table's visimap); runs once at prepare — the per-step kernels then
- * read one bit per row through the existing visibility path */
+ * read one bit per row through the existing visibility path.  q resolves the
+ * quals' columns (q3_col) and may be null only when nq == 0. */
 static gx_status q3_build_qualmask(gx_ctx *ctx, gx_q3 *q, gx_table *t,
                                    const gx_filter *quals, int nq,
-                                   uint8_t **out)
+                                   devbuf *out)
 {
     gx_qualargs qa{};
     qa.n = nq;
@@ -6002,42 +6105,24 @@ static gx_status q3_build_qualmask(gx_ctx *ctx, gx_q3 *q, gx_table *t,
         qa.op[i] = quals[i].op;
         qa.lit[i] = quals[i].literal;
     }
-    if (*out != nullptr)
-    {
-        /* a hidden mask already exists (NULL folds from materialization):
-         * AND the quals in, IN PLACE (seed == output is element-aliased) */
-        hipLaunchKernelGGL(k_qualmask, dim3(GRID), dim3(TPB), 0, ctx->stream,
-                           qa, *out, t->nrows, *out);
-        HIP_CHK(ctx, hipStreamSynchronize(ctx->stream));
-        HIP_CHK(ctx, hipGetLastError());
-        return GX_OK;
-    }
-    int64_t nbytes = (t->nrows + 7) >> 3;
-    devbuf mb;
-    HIP_CHK(ctx, mb.alloc((size_t) std::max<int64_t>(nbytes, 1)));
+    /* a hidden mask may already exist (NULL folds from materialization):
+     * the quals are then AND-ed in, IN PLACE (seed == output is
+     * element-aliased); otherwise the visimap seeds a new one */
+    const uint8_t *seed = out->p ? out->as<uint8_t>() : t->dvmap;
+    if (!out->p)
+        HIP_CHK(ctx, out->alloc((size_t) ((t->nrows + 7) >> 3)));
     hipLaunchKernelGGL(k_qualmask, dim3(GRID), dim3(TPB), 0, ctx->stream,
-                       qa, t->dvmap, t->nrows, mb.as<uint8_t>());
+                       qa, seed, t->nrows, out->as<uint8_t>());
     HIP_CHK(ctx, hipStreamSynchronize(ctx->stream));
     HIP_CHK(ctx, hipGetLastError());
-    *out = mb.as<uint8_t>();
-    mb.p = nullptr;              /* ownership moves to gx_q3 */
     return GX_OK;
 }
 
-static gx_status q3_ensure_hidden(gx_ctx *ctx, gx_table *t, uint8_t **hidden)
+static gx_status q3_ensure_hidden(gx_ctx *ctx, gx_table *t, devbuf *hidden)
 {
-    if (*hidden) return GX_OK;
-    int64_t nbytes = (t->nrows + 7) >> 3;
-    devbuf mb;
-    HIP_CHK(ctx, mb.alloc((size_t) std::max<int64_t>(nbytes, 1)));
-    gx_qualargs qa{};            /* n = 0: copies the visimap (or zeros) */
-    hipLaunchKernelGGL(k_qualmask, dim3(GRID), dim3(TPB), 0, ctx->stream,
-                       qa, t->dvmap, t->nrows, mb.as<uint8_t>());
-    HIP_CHK(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_CHK(ctx, hipGetLastError());
-    *hidden = mb.as<uint8_t>();
-    mb.p = nullptr;
-    return GX_OK;
+    if (hidden->p) return GX_OK;
+    /* no quals: copies the visimap (or zeros); q is not needed then */
+    return q3_build_qualmask(ctx, nullptr, t, nullptr, 0, hidden);
 }
 
 extern "C" gx_status gx_q3_prepare_desc(gx_ctx *ctx, const gx_q3_desc *desc,
@@ -6146,17 +6231,14 @@ extern "C" gx_status gx_q3_prepare_desc(gx_ctx *ctx, const gx_q3_desc *desc,
     }
     if (dim_text)
     {
-        hipError_t e = hipMalloc(&q->dtext,
-                                 std::max(desc->dim_text_len, 1));
+        hipError_t e = q->dtext.alloc(desc->dim_text_len);
+        if (e == hipSuccess)
+            e = hipMemcpy(q->dtext.p, desc->dim_text, desc->dim_text_len,
+                          hipMemcpyHostToDevice);
         if (e != hipSuccess) { delete q; return GX_ERR_OOM; }
-        e = hipMemcpy(q->dtext, desc->dim_text, desc->dim_text_len,
-                      hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void) hipFree(q->dtext); delete q; return GX_ERR_OOM; }
         gx_status st = q3_build_text_mask(ctx, q);
         if (st != GX_OK)
         {
-            (void) hipFree(q->dtext);
-            if (q->dmask) (void) hipFree(q->dmask);
             delete q;
             return st;
         }
@@ -6171,7 +6253,7 @@ extern "C" gx_status gx_q3_prepare_desc(gx_ctx *ctx, const gx_q3_desc *desc,
         gx_q3_free(q);
         return GX_ERR_INVALID;
     }
-    struct { gx_table *t; const gx_filter *qs; int nq; uint8_t **dst; } ex[3] = {
+    struct { gx_table *t; const gx_filter *qs; int nq; devbuf *dst; } ex[3] = {
         {customer, desc->dim_extra, desc->n_dim_extra, &q->qvm_dim},
         {orders, desc->mid_extra, desc->n_mid_extra, &q->qvm_mid},
         {lineitem, desc->fact_extra, desc->n_fact_extra, &q->qvm_fact},
@@ -6270,30 +6352,6 @@ extern "C" gx_status gx_q3_prepare(gx_ctx *ctx, gx_table *customer, gx_table *or
     return gx_q3_prepare_desc(ctx, &d, out);
 }
 
-static void q3_free_runstate(gx_q3 *q)
-{
-    auto fr = [](auto *&p) { if (p) { (void) hipFree(p); p = nullptr; } };
-    fr(q->cset); fr(q->bloom); fr(q->dbits); fr(q->tkey); fr(q->tattr); fr(q->tagg);
-    fr(q->rent); fr(q->rblk); fr(q->rowmask);
-    fr(q->stage); fr(q->stage_cur);
-    fr(q->dkey); fr(q->dattr); fr(q->dagg);
-    fr(q->r_okey); fr(q->r_odate); fr(q->r_oprio); fr(q->r_rev); fr(q->r_cnt);
-    fr(q->r_flags);
-    fr(q->ukey); fr(q->ucnt_u); fr(q->urev);
-    fr(q->dcount); fr(q->dhits); fr(q->dmin);
-    fr(q->m_hist); fr(q->m_cur); fr(q->m_cnts_mine); fr(q->m_cnts_all);
-    fr(q->m_bloom_all);
-    fr(q->m_send1); fr(q->m_recv1); fr(q->m_send2); fr(q->m_recv2);
-    fr(q->dtext);
-    fr(q->dmask);
-    fr(q->qvm_dim); fr(q->qvm_mid); fr(q->qvm_fact);
-    for (void *pm : q->mat_mem) (void) hipFree(pm);
-    q->mat_mem.clear();
-    q->mat.clear();
-    q->m_send1_cap = q->m_recv1_cap = q->m_send2_cap = q->m_recv2_cap = 0;
-    q->sized = false;
-}
-
 /* HBM-budget guard: the reference batches/spills when the
  * build side exceeds its memory budget (ExecChooseHashTableSize nodeHash.c:812,
  * batch split nodeHashjoin.c:1355); the GPU path instead sizes up front and
@@ -6324,79 +6382,79 @@ static gx_status hbm_budget_check(gx_ctx *ctx, uint64_t want, const char *what)
 /* The customer scans, as the Q3 run and the test entry points launch them.
  * dmask != nullptr selects the flat-mask row predicate, otherwise the int8
  * compare <op, literal> on column cm. */
+struct q3_dimscan {
+    const gx_col &ck, &cm;           /* key column, filter column */
+    const uint8_t *dmask;
+    int32_t op;
+    int64_t literal;
+    const uint8_t *cvm;              /* effective visibility */
+};
+
 template <typename F>
-static inline void by_dim_pred(const uint8_t *dmask, const gx_col &cm,
-                               int32_t op, int64_t literal, F &&f)
+static inline void by_dim_pred(const q3_dimscan &sc, F &&f)
 {
-    if (dmask) f(gx_dim_pred_mask{dmask});
-    else f(gx_dim_pred_cmp{cm.dstream, cm.m, op, (int8_t) literal});
+    if (sc.dmask) f(gx_dim_pred_mask{sc.dmask});
+    else f(gx_dim_pred_cmp{sc.cm.dstream, sc.cm.m, sc.op, (int8_t) sc.literal});
 }
 
-static void dim_launch_count(hipStream_t s, const gx_col &ck,
-                             const uint8_t *dmask, const gx_col &cm,
-                             int32_t op, int64_t literal, const uint8_t *cvm,
+static void dim_launch_count(hipStream_t s, const q3_dimscan &sc,
                              unsigned long long *count,
                              unsigned long long *maxkey,
                              unsigned long long *minkey)
 {
-    by_dim_pred(dmask, cm, op, literal, [&](auto pred) {
+    by_dim_pred(sc, [&](auto pred) {
         hipLaunchKernelGGL(k_cust_count<decltype(pred)>,
                            dim3(GRID), dim3(TPB), 0, s,
-                           ck.dstream, ck.m, pred, cvm, count, maxkey, minkey);
+                           sc.ck.dstream, sc.ck.m, pred, sc.cvm, count, maxkey,
+                           minkey);
     });
 }
 
-/* bits != nullptr fills the bitmap (no key set: one set-width instantiation),
- * otherwise bloom + the cset_width-byte key set */
-static void dim_launch_build(hipStream_t s, const gx_col &ck,
-                             const uint8_t *dmask, const gx_col &cm,
-                             int32_t op, int64_t literal, const uint8_t *cvm,
-                             void *cset, int cset_width, uint64_t cmask,
-                             unsigned long long *bloom, uint64_t bwmask,
-                             unsigned long long *bits, uint64_t kmin,
-                             uint64_t range)
+/* Clear and fill the membership structure the caller's path reads: the
+ * bitmap (no key set: one set-width instantiation), or bloom + the
+ * width-byte key set.  Only that one is touched; the other keeps whatever
+ * it held. */
+static gx_status dim_launch_build(gx_ctx *ctx, hipStream_t s,
+                                  const q3_dimscan &sc, const q3_dimset &ds,
+                                  bool bitmap)
 {
-    by_dim_pred(dmask, cm, op, literal, [&](auto pred) {
+    if (bitmap)
+        HIP_CHK(ctx, hipMemsetAsync(ds.bits.p, 0, (ds.range + 63) / 64 * 8, s));
+    else
+    {
+        HIP_CHK(ctx, hipMemsetAsync(ds.set.p, 0, (ds.cmask + 1) * ds.width, s));
+        HIP_CHK(ctx, hipMemsetAsync(ds.bloom.p, 0, (ds.bwmask + 1) * 8, s));
+    }
+    by_dim_pred(sc, [&](auto pred) {
         auto go = [&](auto *cs, auto bmode) {
             hipLaunchKernelGGL((k_cust_build<std::decay_t<decltype(*cs)>,
                                              decltype(bmode)::value,
                                              decltype(pred)>),
                                dim3(GRID), dim3(TPB), 0, s,
-                               ck.dstream, ck.m, pred, cvm, cs, cmask,
-                               bloom, bwmask, bits, kmin, range);
+                               sc.ck.dstream, sc.ck.m, pred, sc.cvm, cs, ds.cmask,
+                               ds.bloom.as<unsigned long long>(), ds.bwmask,
+                               bitmap ? ds.bits.as<unsigned long long>() : nullptr,
+                               ds.kmin, ds.range);
         };
-        if (bits)
+        if (bitmap)
             go((unsigned int *) nullptr, std::true_type{});
         else
-            by_width(cset_width, cset,
+            by_width(ds.width, ds.set.p,
                      [&](auto *cs) { go(cs, std::false_type{}); });
     });
+    return GX_OK;
 }
 
-/* stage 1 of every run (and once at sizing): clear and fill the dimension
- * membership structure the caller's path reads — the bitmap, or set+bloom.
- * Only that one is touched; the other keeps whatever it held. */
-static gx_status q3_build_dim(gx_q3 *q, bool bitmap)
+/* the dim scan of a q: its role columns, filter and effective visibility
+ * (the extra-qual mask already holds the visimap) */
+static q3_dimscan q3_dim_scan(const gx_q3 *q)
 {
-    gx_ctx *ctx = q->ctx;
-    hipStream_t s = ctx->stream;
     const gx_q3_desc &D = q->desc;
-    const gx_col &ck = q3_col(q, q->cust, D.dim_key_col),
-                 &cm = q3_col(q, q->cust, D.dim_filter.col);
-    const uint8_t *cvm = q->qvm_dim ? q->qvm_dim : q->cust->dvmap;
-    if (bitmap)
-        HIP_CHK(ctx, hipMemsetAsync(q->dbits, 0,
-                                    (q->dim_range + 63) / 64 * 8, s));
-    else
-    {
-        HIP_CHK(ctx, hipMemsetAsync(q->cset, 0, (q->cmask + 1) * q->cset_width, s));
-        HIP_CHK(ctx, hipMemsetAsync(q->bloom, 0, (q->bwmask + 1) * 8, s));
-    }
-    dim_launch_build(s, ck, D.dim_text_len > 0 ? q->dmask : nullptr, cm,
-                     D.dim_filter.op, D.dim_filter.literal, cvm,
-                     q->cset, q->cset_width, q->cmask, q->bloom, q->bwmask,
-                     bitmap ? q->dbits : nullptr, q->dim_kmin, q->dim_range);
-    return GX_OK;
+    return {q3_col(q, q->cust, D.dim_key_col),
+            q3_col(q, q->cust, D.dim_filter.col),
+            D.dim_text_len > 0 ? q->dmask.as<uint8_t>() : nullptr,
+            D.dim_filter.op, D.dim_filter.literal,
+            q->qvm_dim.p ? q->qvm_dim.as<uint8_t>() : q->cust->dvmap};
 }
 
 /* Bound on the LEFT-OUTER unmatched groups of a fact key column with nrows
@@ -6415,17 +6473,17 @@ static uint64_t q3_unmatched_bound(int64_t nrows, uint64_t lmin, uint64_t lmax)
 }
 
 /* (Re)allocate the hash-form join/agg table of tslots slots of
- * q->key_width-byte keys and the result arrays for qual groups plus the
+ * q->tbl.width-byte keys and the result arrays for qual groups plus the
  * LEFT-OUTER bound, freeing what was there.  The Motion path calls it at its
  * first run and whenever a run's exchanged counts outgrow the cached table;
  * the local path allocates the two halves separately (results at sizing, the
  * table at the first hash-form run). */
 static gx_status q3_alloc_results(gx_q3 *q, int64_t qual);
-static gx_status q3_alloc_hash(gx_q3 *q, uint64_t tslots);
+static gx_status q3_alloc_hash(gx_ctx *ctx, q3_hashtbl &t, uint64_t tslots);
 
 static gx_status q3_alloc_table(gx_q3 *q, uint64_t tslots, int64_t qual)
 {
-    gx_status st = q3_alloc_hash(q, tslots);
+    gx_status st = q3_alloc_hash(q->ctx, q->tbl, tslots);
     if (st != GX_OK) return st;
     return q3_alloc_results(q, qual);
 }
@@ -6435,34 +6493,24 @@ static gx_status q3_alloc_table(gx_q3 *q, uint64_t tslots, int64_t qual)
  * re-allocation by the Motion path leaves a later local run valid. */
 static gx_status q3_alloc_results(gx_q3 *q, int64_t qual)
 {
-    gx_ctx *ctx = q->ctx;
-    auto fr = [](auto *&p) { if (p) { (void) hipFree(p); p = nullptr; } };
-    fr(q->r_okey); fr(q->r_odate); fr(q->r_oprio); fr(q->r_rev); fr(q->r_cnt);
-    fr(q->r_flags);
-    q->rescap = std::max<int64_t>(std::max(qual, q->local_qual) + q->u_cap, 1);
-    HIP_CHK(ctx, hipMalloc(&q->r_okey, q->rescap * 8));
-    HIP_CHK(ctx, hipMalloc(&q->r_odate, q->rescap * 4));
-    HIP_CHK(ctx, hipMalloc(&q->r_oprio, q->rescap * 4));
-    HIP_CHK(ctx, hipMalloc(&q->r_rev, q->rescap * 8));
-    HIP_CHK(ctx, hipMalloc(&q->r_cnt, q->rescap * 8));
-    HIP_CHK(ctx, hipMalloc(&q->r_flags, q->rescap));
+    HIP_CHK(q->ctx, q->res.alloc(std::max<int64_t>(
+                        std::max(qual, q->local_qual) + q->un.cap, 1)));
     return GX_OK;
 }
 
-/* the hash form's storage: tslots slots of q->key_width-byte keys */
-static gx_status q3_alloc_hash(gx_q3 *q, uint64_t tslots)
+/* the hash form's storage: tslots slots of t.width-byte keys, replacing what
+ * t held */
+static gx_status q3_alloc_hash(gx_ctx *ctx, q3_hashtbl &t, uint64_t tslots)
 {
-    gx_ctx *ctx = q->ctx;
-    auto fr = [](auto *&p) { if (p) { (void) hipFree(p); p = nullptr; } };
-    fr(q->tkey); fr(q->tattr); fr(q->tagg);
+    t.keys.reset(); t.attrs.reset(); t.aggs.reset();
     gx_status st = hbm_budget_check(
-        ctx, tslots * (q->key_width + sizeof(gx_attrpair) + sizeof(gx_aggslot)),
+        ctx, tslots * (t.width + sizeof(gx_attrpair) + sizeof(gx_aggslot)),
         "join/agg table");
     if (st != GX_OK) return st;
-    HIP_CHK(ctx, hipMalloc(&q->tkey, tslots * q->key_width));
-    HIP_CHK(ctx, hipMalloc(&q->tattr, tslots * sizeof(gx_attrpair)));
-    HIP_CHK(ctx, hipMalloc(&q->tagg, tslots * sizeof(gx_aggslot)));
-    q->tmask = tslots - 1;
+    HIP_CHK(ctx, t.keys.alloc(tslots * t.width));
+    HIP_CHK(ctx, t.attrs.alloc(tslots * sizeof(gx_attrpair)));
+    HIP_CHK(ctx, t.aggs.alloc(tslots * sizeof(gx_aggslot)));
+    t.mask = tslots - 1;
     return GX_OK;
 }
 
@@ -6521,26 +6569,23 @@ static int64_t q3_stage_grid(int64_t qual, int64_t nrows)
 /* first rank-form run of a q: allocate the rank storage.  What only one
  * form of the orders stage needs (rowmask; staging records) is allocated by
  * that form's first run. */
-static gx_status q3_alloc_rank(gx_q3 *q)
+static gx_status q3_alloc_rank(gx_ctx *ctx, q3_ranktbl &r, uint64_t qual)
 {
-    gx_ctx *ctx = q->ctx;
-    uint64_t nwords = (q->rank_range + 63) / 64;
+    uint64_t nwords = r.nwords();
     uint64_t nblk = (nwords + GX_RANK_SCAN_WORDS - 1) / GX_RANK_SCAN_WORDS;
-    uint64_t qual = (uint64_t) q->local_qual;
-    auto fr = [](auto *&p) { if (p) { (void) hipFree(p); p = nullptr; } };
-    fr(q->rent); fr(q->rblk);                   /* a failed earlier try */
-    fr(q->dkey); fr(q->dattr); fr(q->dagg);
+    r.ent.reset(); r.blk.reset();               /* a failed earlier try */
+    r.dkey.reset(); r.dattr.reset(); r.dagg.reset();
     gx_status st = hbm_budget_check(
         ctx,
         nwords * 16 + nblk * 4 +
-            qual * (q->rank_kw + sizeof(gx_attrpair) + sizeof(gx_aggslot)),
+            qual * (r.kw + sizeof(gx_attrpair) + sizeof(gx_aggslot)),
         "rank join/agg table");
     if (st != GX_OK) return st;
-    HIP_CHK(ctx, hipMalloc(&q->rent, nwords * sizeof(ulonglong2)));
-    HIP_CHK(ctx, hipMalloc(&q->rblk, nblk * 4));
-    HIP_CHK(ctx, hipMalloc(&q->dkey, qual * q->rank_kw));
-    HIP_CHK(ctx, hipMalloc(&q->dattr, qual * sizeof(gx_attrpair)));
-    HIP_CHK(ctx, hipMalloc(&q->dagg, qual * sizeof(gx_aggslot)));
+    HIP_CHK(ctx, r.ent.alloc(nwords * sizeof(ulonglong2)));
+    HIP_CHK(ctx, r.blk.alloc(nblk * 4));
+    HIP_CHK(ctx, r.dkey.alloc(qual * r.kw));
+    HIP_CHK(ctx, r.dattr.alloc(qual * sizeof(gx_attrpair)));
+    HIP_CHK(ctx, r.dagg.alloc(qual * sizeof(gx_aggslot)));
     return GX_OK;
 }
 
@@ -6551,7 +6596,7 @@ static gx_status q3_alloc_rowmask(gx_q3 *q)
     uint64_t mwords = ((uint64_t) q->ord->nrows + 63) / 64;
     gx_status st = hbm_budget_check(ctx, mwords * 8, "orders row mask");
     if (st != GX_OK) return st;
-    HIP_CHK(ctx, hipMalloc(&q->rowmask, std::max<uint64_t>(mwords, 1) * 8));
+    HIP_CHK(ctx, q->rank.rowmask.alloc(mwords * 8));
     return GX_OK;
 }
 
@@ -6562,15 +6607,182 @@ static gx_status q3_alloc_stage(gx_q3 *q)
 {
     gx_ctx *ctx = q->ctx;
     uint64_t cap = (uint64_t) q->local_qual;
-    auto fr = [](auto *&p) { if (p) { (void) hipFree(p); p = nullptr; } };
-    fr(q->stage); fr(q->stage_cur);             /* a failed earlier try */
+    q->rank.stage.reset(); q->rank.stage_cur.reset();   /* a failed earlier try */
     gx_status st = hbm_budget_check(ctx, cap * sizeof(ulonglong2) + 16,
                                     "orders staging records");
     if (st != GX_OK) return st;
-    HIP_CHK(ctx, hipMalloc(&q->stage, std::max<uint64_t>(cap, 1) * sizeof(ulonglong2)));
-    HIP_CHK(ctx, hipMalloc(&q->stage_cur, 16));
+    HIP_CHK(ctx, q->rank.stage.alloc(cap * sizeof(ulonglong2)));
+    HIP_CHK(ctx, q->rank.stage_cur.alloc(16));
     return GX_OK;
 }
+
+/* max over ranks of one word; v is left alone on a single segment */
+static gx_status comm_max_u64(gx_ctx *ctx, hipStream_t s, uint64_t &v)
+{
+    if (!(ctx->nsegs > 1 && ctx->comm)) return GX_OK;
+    devbuf w;
+    HIP_CHK(ctx, w.alloc(8));
+    unsigned long long hv = v;
+    HIP_CHK(ctx, hipMemcpyAsync(w.p, &hv, 8, hipMemcpyHostToDevice, s));
+    RCCL_CHK(ctx, ncclAllReduce(w.p, w.p, 1, ncclUint64, ncclMax, ctx->comm, s));
+    HIP_CHK(ctx, hipMemcpyAsync(&hv, w.p, 8, hipMemcpyDeviceToHost, s));
+    HIP_CHK(ctx, hipStreamSynchronize(s));
+    v = hv;
+    return GX_OK;
+}
+
+/* Dimension set layout for n_building filtered rows whose keys span
+ * [cmin, cmax] (pure host): 4-byte set slots when every key fits, two slots
+ * per key, 8 bloom bits per key (at least 4096 words).  Dense keys (range
+ * <= 64 per qualifying key: the bitmap is then never larger than the 8 B/key
+ * u32 set) on a single segment get the exact bitmap as well, unless the
+ * switch is off. */
+struct gx_dim_layout {
+    int width;
+    uint64_t cslots, bwords;
+    int bitmap;
+    uint64_t kmin, range;
+};
+
+static gx_dim_layout q3_dim_layout(uint64_t n_building, uint64_t cmin,
+                                   uint64_t cmax, int nsegs, bool bitmap_on)
+{
+    gx_dim_layout L;
+    L.width = (cmax < (1ULL << 32)) ? 4 : 8;
+    L.cslots = (uint64_t) pow2_at_least((int64_t) n_building * 2);
+    L.bwords = (uint64_t) pow2_at_least(
+        std::max<int64_t>((int64_t) n_building * 8 / 64, 4096));
+    uint64_t drange = (n_building > 0 && cmax >= cmin) ? cmax - cmin + 1 : 0;
+    L.bitmap = nsegs == 1 && drange > 0 && drange <= 64 * n_building && bitmap_on;
+    L.kmin = L.bitmap ? cmin : 0;
+    L.range = L.bitmap ? drange : 0;
+    return L;
+}
+
+/* Count the filtered dim rows, check key 0, size, allocate and build the
+ * membership structures: what sizing does for a q and what the test entry
+ * points do for one rank's dim set.  bwords_fixed != 0 stands in for the
+ * bloom size the ranks would agree on.  state: 0 built, 1 empty (NOTIN with
+ * a NULL inner key, nodeHashjoin.c:442; nothing is allocated).  At nsegs>1
+ * the key-0 / NOTIN-NULL / over-budget verdict must be GLOBAL and agreed by
+ * every rank BEFORE any early return — a lone rank bailing out of sizing
+ * while its peers continue into the collectives would hang the job. */
+static gx_status q3_dim_size_build(gx_ctx *ctx, hipStream_t s,
+                                   const q3_scratch &sc, const q3_dimscan &scan,
+                                   bool notin_null, bool bitmap_on,
+                                   uint64_t bwords_fixed, q3_dimset &ds,
+                                   int *state, int64_t *nsel = nullptr)
+{
+    q3_keystats ks;
+    gx_status st = q3_read_keystats(
+        ctx, s, sc, ks, [&](auto *count, auto *kmax, auto *kmin) {
+            dim_launch_count(s, scan, count, kmax, kmin);
+        });
+    if (st != GX_OK) return st;
+    /* 2: invalid (real key 0 vs the slot sentinel) */
+    uint64_t verdict = 0;
+    if (ks.count > 0 && ks.kmin == 0) verdict = notin_null ? 1 : 2;
+    const gx_dim_layout L = q3_dim_layout(ks.count, ks.kmin, ks.kmax,
+                                          ctx->nsegs, bitmap_on);
+    const uint64_t want = L.cslots * L.width + L.bwords * 8 +
+                          (L.range + 63) / 64 * 8;
+    if (verdict == 0 &&
+        hbm_budget_check(ctx, want, "dim semijoin set") != GX_OK)
+        verdict = 3;                   /* over budget — agree collectively */
+    st = comm_max_u64(ctx, s, verdict);
+    if (st != GX_OK) return st;
+    *state = (int) verdict;
+    if (verdict == 1) return GX_OK;
+    if (verdict == 2)
+    {
+        /* slot value 0 is the empty-slot sentinel (keys start at 1 in every
+         * PG sequence-keyed table); a real key 0 would be silently dropped.
+         * All ranks agree on this verdict, so everyone errors together. */
+        set_err(ctx, "dim join key 0 found: 0 is reserved as the empty-slot "
+                     "sentinel (gpuexec.h gx_q3_prepare_desc)%s", "");
+        return GX_ERR_INVALID;
+    }
+    if (verdict == 3)
+    {
+        /* re-derive the message on every rank (the verdict is global) */
+        st = hbm_budget_check(ctx, want, "dim semijoin set");
+        if (st != GX_OK) return st;
+        set_err(ctx, "dim semijoin set over HBM budget on a peer rank%s", "");
+        return GX_ERR_OOM;
+    }
+    if (nsel) *nsel = (int64_t) ks.count;
+    ds.width = L.width;
+    ds.bitmap = L.bitmap;
+    ds.kmin = L.kmin;
+    ds.range = L.range;
+    HIP_CHK(ctx, ds.set.alloc(L.cslots * L.width));
+    ds.cmask = L.cslots - 1;
+    /* the Motion-1 destination-bloom prefilter all-gathers every rank's
+     * bloom — sizes must agree: take the max over ranks */
+    uint64_t bwords = bwords_fixed ? bwords_fixed : L.bwords;
+    st = comm_max_u64(ctx, s, bwords);
+    if (st != GX_OK) return st;
+    HIP_CHK(ctx, ds.bloom.alloc(bwords * 8));
+    ds.bwmask = bwords - 1;
+    ds.bits.reset();
+    if (L.bitmap)
+        HIP_CHK(ctx, ds.bits.alloc((L.range + 63) / 64 * 8));
+    return dim_launch_build(ctx, s, scan, ds, L.bitmap != 0);
+}
+
+/* Slot map of a join/agg table of `slots` slots over qual keys in
+ * [kmin,kmax]: order-preserving interpolation when their density over the
+ * range is high enough that runs stay short (at least one key per 64,
+ * relaxed by nsegs on the Motion path since each rank holds ~1/nsegs of a
+ * globally dense key range), otherwise multiplicative hashing (scale < 0). */
+static gx_slotmap q3_slotmap(int64_t qual, unsigned long long kmin,
+                             unsigned long long kmax, int nsegs, uint64_t slots)
+{
+    gx_slotmap sm;
+    sm.mask = slots - 1;
+    sm.kmin = (int64_t) kmin;
+    sm.scale = -1.0;
+    if (qual > 0 && kmax >= kmin)
+    {
+        double range = (double) (kmax - kmin) + 1.0;
+        if ((double) qual >= range / ((double) nsegs * 64.0))
+            sm.scale = (double) slots / range;
+    }
+    return sm;
+}
+
+/* Hash-form table layout for qual keys in [kmin,kmax] (pure host), the one
+ * rule of the local path (nsegs 1) and the Motion path: 4-byte keys when
+ * every key fits, slots = qual * tf_pct/100 pow2-rounded and always > qual
+ * (an open-addressing table with no free slot would never terminate an
+ * insert), slot map for exactly that many slots.  Whether a larger cached
+ * table is reused instead is the caller's decision; it then re-derives the
+ * slot map with q3_slotmap for the slots it really has.
+ * Fill factor: the r2 sweep (profiles/rocprof_r2_kernels.txt) took the probe
+ * 4.86 -> 4.43 ms and the whole step 8.21 -> 8.07 ms at tf=300 (2^26 slots
+ * at SF100, load factor 0.19).  Re-swept with the single-read extract
+ * (profiles/aggslot_kernels.txt): tf>=600 still gains 0.38 ms of probe and
+ * the extract gives 0.38-0.45 ms of it back (twice the key array to
+ * stream), stage sum 7.66-7.70 against 7.59-7.60 at tf=300 — 300 stays. */
+struct gx_tbl_layout {
+    int key_width;
+    uint64_t slots;
+    gx_slotmap smap;
+};
+
+static gx_tbl_layout q3_table_layout(int64_t qual, unsigned long long kmin,
+                                     unsigned long long kmax, int nsegs,
+                                     int tf_pct)
+{
+    gx_tbl_layout L;
+    L.key_width = (kmax < (1ULL << 32)) ? 4 : 8;
+    L.slots = (uint64_t) pow2_at_least(
+        std::max<int64_t>(qual * tf_pct / 100, qual) + 1);
+    L.smap = q3_slotmap(qual, kmin, kmax, nsegs, L.slots);
+    return L;
+}
+
+static inline int q3_table_factor() { return env_int("GX_TABLE_FACTOR_PCT", 300); }
 
 /* first run only: size the dimension membership structures and join/agg
  * table from counting passes; allocate the dimension structures and the
@@ -6583,130 +6795,32 @@ static gx_status q3_size_and_alloc(gx_q3 *q)
     gx_ctx *ctx = q->ctx;
     hipStream_t s = ctx->stream;
     const gx_q3_desc &D = q->desc;
-    const gx_col &ckk = q3_col(q, q->cust, D.dim_key_col);
-    const gx_col &cm = q3_col(q, q->cust, D.dim_filter.col);
     const gx_col &oc = q3_col(q, q->ord, D.mid_fk_col),
                  &od = q3_col(q, q->ord, D.mid_filter.col);
     /* effective visibility = extra-qual mask (already OR-combined with the
      * table visimap at prepare) or the bare visimap */
-    const uint8_t *cvm = q->qvm_dim ? q->qvm_dim : q->cust->dvmap;
-    const uint8_t *ovm = q->qvm_mid ? q->qvm_mid : q->ord->dvmap;
+    const uint8_t *ovm = q->qvm_mid.p ? q->qvm_mid.as<uint8_t>() : q->ord->dvmap;
 
-    HIP_CHK(ctx, hipMalloc(&q->dcount, 8));
-    HIP_CHK(ctx, hipMalloc(&q->dhits, 8));
-    HIP_CHK(ctx, hipMalloc(&q->dmin, 8));
-
-    HIP_CHK(ctx, hipMemsetAsync(q->dcount, 0, 8, s));
-    HIP_CHK(ctx, hipMemsetAsync(q->dhits, 0, 8, s));   /* borrowed for max custkey */
-    HIP_CHK(ctx, hipMemsetAsync(q->dmin, 0xFF, 8, s)); /* borrowed for min custkey */
-    dim_launch_count(s, ckk, D.dim_text_len > 0 ? q->dmask : nullptr, cm,
-                     D.dim_filter.op, D.dim_filter.literal, cvm,
-                     q->dcount, q->dhits, q->dmin);
-    unsigned long long n_building = 0, cmax = 0, cmin = 0;
-    HIP_CHK(ctx, hipMemcpyAsync(&n_building, q->dcount, 8, hipMemcpyDeviceToHost, s));
-    HIP_CHK(ctx, hipMemcpyAsync(&cmax, q->dhits, 8, hipMemcpyDeviceToHost, s));
-    HIP_CHK(ctx, hipMemcpyAsync(&cmin, q->dmin, 8, hipMemcpyDeviceToHost, s));
-    HIP_CHK(ctx, hipStreamSynchronize(s));
-    /* key-0 / NOTIN-NULL state.  At nsegs>1 the verdict must be GLOBAL and
-     * agreed by every rank BEFORE any early return — a lone rank bailing
-     * out of sizing while its peers continue into the collectives below
-     * would hang the job.  state: 0 ok, 1 empty (NOTIN NULL inner key,
-     * nodeHashjoin.c:442), 2 invalid (real key 0 vs the slot sentinel). */
+    HIP_CHK(ctx, q->sc.ensure());
+    /* GX_DIM_BITMAP=0 forces the hash form (A/B in one binary).  The orders
+     * count below reads the bitmap when there is one. */
     int dim_state = 0;
-    if (n_building > 0 && cmin == 0)
-        dim_state = (D.dim_join == 2 &&
-                     q3_col(q, q->cust, D.dim_key_col).has_null) ? 1 : 2;
-    q->cset_width = (cmax < (1ULL << 32)) ? 4 : 8;
-    uint64_t cslots = (uint64_t) pow2_at_least((int64_t) n_building * 2);
-    uint64_t bwords0 = (uint64_t) pow2_at_least(
-        std::max<int64_t>((int64_t) n_building * 8 / 64, 4096));
-    /* dense keys (range <= 64 per qualifying key: the bitmap is then never
-     * larger than the 8 B/key u32 set) get the exact bitmap as well; the
-     * local path reads it instead of set+bloom.  The Motion path keeps
-     * set+bloom, so both are allocated and each run builds only its own.
-     * GX_DIM_BITMAP=0 forces the hash form (A/B in one binary). */
-    uint64_t drange = (n_building > 0 && cmax >= cmin) ? cmax - cmin + 1 : 0;
-    q->dim_bitmap = ctx->nsegs == 1 && drange > 0 &&
-                    drange <= 64 * (uint64_t) n_building &&
-                    env_int("GX_DIM_BITMAP", 1) != 0;
-    q->dim_kmin = q->dim_bitmap ? cmin : 0;
-    q->dim_range = q->dim_bitmap ? drange : 0;
-    uint64_t dwords = (q->dim_range + 63) / 64;
-    if (dim_state == 0 &&
-        hbm_budget_check(ctx, cslots * q->cset_width + bwords0 * 8 + dwords * 8,
-                         "dim semijoin set") != GX_OK)
-        dim_state = 3;                 /* over budget — agree collectively */
-    if (ctx->nsegs > 1 && ctx->comm)
     {
-        devbuf stb;
-        HIP_CHK(ctx, stb.alloc(8));
-        unsigned long long hv = (unsigned long long) dim_state;
-        HIP_CHK(ctx, hipMemcpyAsync(stb.p, &hv, 8, hipMemcpyHostToDevice, s));
-        RCCL_CHK(ctx, ncclAllReduce(stb.p, stb.p, 1, ncclUint64, ncclMax,
-                                    ctx->comm, s));
-        HIP_CHK(ctx, hipMemcpyAsync(&hv, stb.p, 8, hipMemcpyDeviceToHost, s));
-        HIP_CHK(ctx, hipStreamSynchronize(s));
-        dim_state = (int) hv;
+        gx_status st = q3_dim_size_build(
+            ctx, s, q->sc, q3_dim_scan(q),
+            D.dim_join == 2 && q3_col(q, q->cust, D.dim_key_col).has_null,
+            env_int("GX_DIM_BITMAP", 1) != 0, 0, q->dim, &dim_state);
+        if (st != GX_OK) return st;
     }
     if (dim_state == 1)
     {
         /* NOT IN with a NULL key on the inner side anywhere: the whole
          * join yields nothing (nodeHashjoin.c:442 hs_hashkeys_null) */
         q->empty = 1;
-        q->rescap = 1;
-        HIP_CHK(ctx, hipMalloc(&q->r_okey, 8));
-        HIP_CHK(ctx, hipMalloc(&q->r_odate, 4));
-        HIP_CHK(ctx, hipMalloc(&q->r_oprio, 4));
-        HIP_CHK(ctx, hipMalloc(&q->r_rev, 8));
-        HIP_CHK(ctx, hipMalloc(&q->r_cnt, 8));
+        gx_status st = q3_alloc_results(q, 0);
+        if (st != GX_OK) return st;
         q->sized = true;
         return GX_OK;
-    }
-    if (dim_state == 2)
-    {
-        /* slot value 0 is the empty-slot sentinel (keys start at 1 in every
-         * PG sequence-keyed table); a real key 0 would be silently dropped.
-         * All ranks agree on this verdict, so everyone errors together. */
-        set_err(ctx, "dim join key 0 found: 0 is reserved as the empty-slot "
-                     "sentinel (gpuexec.h gx_q3_prepare_desc)%s", "");
-        return GX_ERR_INVALID;
-    }
-    if (dim_state == 3)
-    {
-        /* re-derive the message on every rank (the verdict is global) */
-        gx_status st = hbm_budget_check(ctx,
-                                        cslots * q->cset_width + bwords0 * 8 +
-                                            dwords * 8,
-                                        "dim semijoin set");
-        if (st != GX_OK) return st;
-        set_err(ctx, "dim semijoin set over HBM budget on a peer rank%s", "");
-        return GX_ERR_OOM;
-    }
-    HIP_CHK(ctx, hipMalloc(&q->cset, cslots * q->cset_width));
-    q->cmask = cslots - 1;
-    uint64_t bwords = bwords0;
-    if (ctx->nsegs > 1 && ctx->comm)
-    {
-        /* the Motion-1 destination-bloom prefilter all-gathers every
-         * rank's bloom — sizes must agree: take the max over ranks */
-        devbuf bw;
-        HIP_CHK(ctx, bw.alloc(8));
-        unsigned long long hv = bwords;
-        HIP_CHK(ctx, hipMemcpyAsync(bw.p, &hv, 8, hipMemcpyHostToDevice, s));
-        RCCL_CHK(ctx, ncclAllReduce(bw.p, bw.p, 1, ncclUint64, ncclMax,
-                                    ctx->comm, s));
-        HIP_CHK(ctx, hipMemcpyAsync(&hv, bw.p, 8, hipMemcpyDeviceToHost, s));
-        HIP_CHK(ctx, hipStreamSynchronize(s));
-        bwords = hv;
-    }
-    HIP_CHK(ctx, hipMalloc(&q->bloom, bwords * 8));
-    q->bwmask = bwords - 1;
-    if (q->dim_bitmap)
-        HIP_CHK(ctx, hipMalloc(&q->dbits, dwords * 8));
-    /* the orders count below reads the bitmap when there is one */
-    {
-        gx_status st = q3_build_dim(q, q->dim_bitmap != 0);
-        if (st != GX_OK) return st;
     }
 
     if (D.fact_join == 1)
@@ -6716,26 +6830,24 @@ static gx_status q3_size_and_alloc(gx_q3 *q)
          * which stays a valid bound).  Sized here for
          * BOTH the local and Motion paths — the unmatched side is always
          * this rank's local fact shard. */
-        const gx_q3_desc &DD = q->desc;
-        const gx_col &lkc = q3_col(q, q->li, DD.fact_key_col);
-        HIP_CHK(ctx, hipMemsetAsync(q->dhits, 0, 8, s));
-        HIP_CHK(ctx, hipMemsetAsync(q->dmin, 0xFF, 8, s));
-        hipLaunchKernelGGL(k_col_minmax, dim3(GRID), dim3(TPB), 0, s,
-                           lkc.dstream, lkc.m, q->dhits, q->dmin);
-        unsigned long long lmax = 0, lmin = 0;
-        HIP_CHK(ctx, hipMemcpyAsync(&lmax, q->dhits, 8, hipMemcpyDeviceToHost, s));
-        HIP_CHK(ctx, hipMemcpyAsync(&lmin, q->dmin, 8, hipMemcpyDeviceToHost, s));
-        HIP_CHK(ctx, hipStreamSynchronize(s));
-        uint64_t bound = q3_unmatched_bound(q->li->nrows, lmin, lmax);
+        const gx_col &lkc = q3_col(q, q->li, D.fact_key_col);
+        q3_keystats ls;
+        gx_status st = q3_read_keystats(
+            ctx, s, q->sc, ls, [&](auto *, auto *kmax, auto *kmin) {
+                hipLaunchKernelGGL(k_col_minmax, dim3(GRID), dim3(TPB), 0, s,
+                                   lkc.dstream, lkc.m, kmax, kmin);
+            });
+        if (st != GX_OK) return st;
+        uint64_t bound = q3_unmatched_bound(q->li->nrows, ls.kmin, ls.kmax);
         uint64_t uslots = (uint64_t) pow2_at_least((int64_t) bound * 2);
-        gx_status bs = hbm_budget_check(
+        st = hbm_budget_check(
             ctx, uslots * 24 + (bound + 1) * 33, "left-outer unmatched table");
-        if (bs != GX_OK) return bs;
-        HIP_CHK(ctx, hipMalloc(&q->ukey, uslots * 8));
-        HIP_CHK(ctx, hipMalloc(&q->urev, uslots * 8));
-        HIP_CHK(ctx, hipMalloc(&q->ucnt_u, uslots * 8));
-        q->umask = uslots - 1;
-        q->u_cap = (int64_t) bound;
+        if (st != GX_OK) return st;
+        HIP_CHK(ctx, q->un.key.alloc(uslots * 8));
+        HIP_CHK(ctx, q->un.rev.alloc(uslots * 8));
+        HIP_CHK(ctx, q->un.cnt.alloc(uslots * 8));
+        q->un.mask = uslots - 1;
+        q->un.cap = (int64_t) bound;
     }
 
     /* local qualifying-order count bounds the table for BOTH paths: at
@@ -6743,14 +6855,11 @@ static gx_status q3_size_and_alloc(gx_q3 *q)
      * qualifying count is conserved by the Motions, and each rank's received
      * share ~ 1/nsegs of it.  To stay safe under skew we still size from
      * the exchanged counts in the motion path (re-alloc if bigger). */
-    int64_t qual = 0;
     if (ctx->nsegs == 1)
     {
-        HIP_CHK(ctx, hipMemsetAsync(q->dcount, 0, 8, s));
-        HIP_CHK(ctx, hipMemsetAsync(q->dhits, 0, 8, s));   /* borrowed for maxkey */
-        HIP_CHK(ctx, hipMemsetAsync(q->dmin, 0xFF, 8, s)); /* minkey = ~0 */
-        gx_dimbits dbm = {q->dbits, q->dim_kmin, q->dim_range};
-        auto launch_ocount = [&](auto *cs, auto bmode) {
+        const q3_dimset &ds = q->dim;
+        auto launch_ocount = [&](auto *cs, auto bmode, auto *count, auto *kmax,
+                                 auto *kmin) {
             by_flag(D.dim_join != 0, [&](auto anti) {
                 hipLaunchKernelGGL((k_orders_count<std::decay_t<decltype(*cs)>,
                                                    decltype(anti)::value,
@@ -6761,41 +6870,33 @@ static gx_status q3_size_and_alloc(gx_q3 *q)
                                    od.dstream, od.m, oc.dstream, oc.m,
                                    ovm,
                                    D.mid_filter.op, (int32_t) D.mid_filter.literal,
-                                   cs, q->cmask,
-                                   q->bloom, q->bwmask, dbm, q->dcount,
-                                   q->dhits, q->dmin);
+                                   cs, ds.cmask,
+                                   ds.bloom.as<unsigned long long>(), ds.bwmask,
+                                   ds.dimbits(), count, kmax, kmin);
             });
         };
-        if (q->dim_bitmap)  /* no key set: one set-width instantiation */
-            launch_ocount((const unsigned int *) nullptr, std::true_type{});
-        else
-            by_width(q->cset_width, (const void *) q->cset, [&](auto *cs) {
-                launch_ocount(cs, std::false_type{});
+        q3_keystats ks;
+        gx_status st = q3_read_keystats(
+            ctx, s, q->sc, ks, [&](auto *count, auto *kmax, auto *kmin) {
+                if (ds.bitmap)  /* no key set: one set-width instantiation */
+                    launch_ocount((const unsigned int *) nullptr,
+                                  std::true_type{}, count, kmax, kmin);
+                else
+                    by_width(ds.width, (const void *) ds.set.p, [&](auto *cs) {
+                        launch_ocount(cs, std::false_type{}, count, kmax, kmin);
+                    });
             });
-        unsigned long long nq = 0, kmax = 0, kmin = 0;
-        HIP_CHK(ctx, hipMemcpyAsync(&nq, q->dcount, 8, hipMemcpyDeviceToHost, s));
-        HIP_CHK(ctx, hipMemcpyAsync(&kmax, q->dhits, 8, hipMemcpyDeviceToHost, s));
-        HIP_CHK(ctx, hipMemcpyAsync(&kmin, q->dmin, 8, hipMemcpyDeviceToHost, s));
-        HIP_CHK(ctx, hipStreamSynchronize(s));
-        qual = (int64_t) nq;
-        if (qual > 0 && kmin == 0)
+        if (st != GX_OK) return st;
+        const int64_t qual = (int64_t) ks.count;
+        if (qual > 0 && ks.kmin == 0)
         {
             set_err(ctx, "mid join key 0 found among qualifying rows: 0 is "
                          "the empty-slot sentinel (gpuexec.h "
                          "gx_q3_prepare_desc)%s", "");
             return GX_ERR_INVALID;
         }
-        q->key_width = (kmax < (1ULL << 32)) ? 4 : 8;
-        /* fill factor: slots = qual * tf/100, pow2-rounded.  r2 sweep
-         * (profiles/rocprof_r2_kernels.txt): tf=300 (2^26 slots at SF100,
-         * load factor 0.19) takes the probe 4.86 -> 4.43 ms and the whole
-         * step 8.21 -> 8.07 ms.  Re-swept with the single-read extract
-         * (profiles/aggslot_kernels.txt): tf>=600 still gains 0.38 ms of
-         * probe and the extract gives 0.38-0.45 ms of it back (twice the
-         * key array to stream), stage sum 7.66-7.70 against 7.59-7.60 at
-         * tf=300 — 300 stays. */
-        int tf = env_int("GX_TABLE_FACTOR_PCT", 300);
-        uint64_t tslots = (uint64_t) pow2_at_least(qual * tf / 100 + 1);
+        const gx_tbl_layout TL = q3_table_layout(qual, ks.kmin, ks.kmax, 1,
+                                                 q3_table_factor());
         /* Dense keys also get the rank form (gx_rankview): a run on the
          * local f64 path over a plain fact key then resolves a key with one
          * load instead of the open-addressing walk, into qual dense slots
@@ -6807,43 +6908,28 @@ static gx_status q3_size_and_alloc(gx_q3 *q)
          * budget-checked, by the first run that uses it (q3_orders_local,
          * q3_orders_rank, q3_orders_motion), so a rank-form q never holds
          * the hash table. */
-        q->rank_ok = q3_rank_eligible(qual, kmin, kmax,
+        q->rank.ok = q3_rank_eligible(qual, ks.kmin, ks.kmax,
                                       env_int("GX_RANK_TABLE", 1) != 0);
-        q->rank_kmin = q->rank_ok ? kmin : 0;
-        q->rank_range = q->rank_ok ? kmax - kmin + 1 : 0;
-        q->rank_kw = q->key_width;
+        q->rank.kmin = q->rank.ok ? ks.kmin : 0;
+        q->rank.range = q->rank.ok ? ks.kmax - ks.kmin + 1 : 0;
+        q->rank.kw = q->tbl.width = TL.key_width;
+        q->tbl.smap = TL.smap;
         q->local_qual = qual;
-        q->hash_tslots = tslots;
+        q->hash_tslots = TL.slots;
         /* Admission stays what it was: the q is refused here unless the
          * hash form (the larger one) and the result arrays fit the budget,
          * even when its first run will take the rank form — set_numeric or
          * a forced Motion may move a later run of the same q to the hash
          * form, and a q that ran must not start failing for memory.  The
          * allocations themselves are checked again where they happen. */
-        {
-            gx_status st = hbm_budget_check(
-                ctx,
-                tslots * (q->key_width + 4 + 4 + 8 + 8) +
-                    (uint64_t) std::max<int64_t>(qual, 1) * (8 + 4 + 4 + 8 + 8),
-                "join/agg table");
-            if (st != GX_OK) return st;
-        }
-        /* order-preserving interpolation layout when the qualifying keys'
-         * density over [kmin,kmax] is high enough that runs stay short;
-         * otherwise multiplicative hashing */
-        q->smap.mask = tslots - 1;
-        q->smap.kmin = (int64_t) kmin;
-        q->smap.scale = -1.0;
-        if (qual > 0 && kmax >= kmin)
-        {
-            double range = (double) (kmax - kmin) + 1.0;
-            if ((double) qual >= range / 64.0)
-                q->smap.scale = (double) tslots / range;
-        }
-        {
-            gx_status st = q3_alloc_results(q, qual);
-            if (st != GX_OK) return st;
-        }
+        st = hbm_budget_check(
+            ctx,
+            TL.slots * (TL.key_width + 4 + 4 + 8 + 8) +
+                (uint64_t) std::max<int64_t>(qual, 1) * (8 + 4 + 4 + 8 + 8),
+            "join/agg table");
+        if (st != GX_OK) return st;
+        st = q3_alloc_results(q, qual);
+        if (st != GX_OK) return st;
     }
     HIP_CHK(ctx, hipStreamSynchronize(s));
     q->sized = true;
@@ -6852,10 +6938,13 @@ static gx_status q3_size_and_alloc(gx_q3 *q)
 
 /* ================= Motion stage seams =================
  * Everything of the nsegs>1 branch of gx_q3_run that is not an RCCL call
- * lives in the helpers below.  They take all inputs as arguments and never
- * reach into gx_q3, so the test-only entry points at the end of this file
- * drive the very same launches, dispatch and layout rules with any nsegs on
- * one GPU ("Test seams of the Motion path"). */
+ * lives in the helpers below and in the sizing functions above
+ * (q3_dim_size_build, q3_table_layout).  They take the run-state structs
+ * (q3_dimset, q3_hashtbl, q3_unmatched, q3_results, q3_scratch) as arguments
+ * and never reach into gx_q3, so the test-only entry points at the end of
+ * this file hold the same structs and drive the very same launches,
+ * dispatch, sizing and layout rules with any nsegs on one GPU (DESIGN.md,
+ * "Test seams of the Motion path"). */
 
 /* the destination-bloom prefilter of Motion 1 applies to the semi join only:
  * for the anti joins non-membership is the keep condition */
@@ -6895,90 +6984,69 @@ static void m1_launch_emit(hipStream_t s, const gx_col &ok, const gx_col &oc,
  * emit by route(mid key).  Dispatch on the dim-set width (4 or 8 bytes) and
  * on semi (dim_join == 0) against anti. */
 static void m2_launch_hist(hipStream_t s, const gx_ord_row *recv, int64_t n,
-                           const void *cset, int cset_width, uint64_t cmask,
-                           const unsigned long long *bloom, uint64_t bwmask,
-                           int dim_join, int nsegs, unsigned long long *dhist)
+                           const q3_dimset &ds, int dim_join, int nsegs,
+                           unsigned long long *dhist)
 {
-    by_width(cset_width, cset, [&](auto *cs) {
+    by_width(ds.width, (const void *) ds.set.p, [&](auto *cs) {
         by_flag(dim_join != 0, [&](auto anti) {
             hipLaunchKernelGGL((k_qual_hist<std::decay_t<decltype(*cs)>,
                                             decltype(anti)::value>),
                                dim3(GRID), dim3(TPB), 0, s,
-                               recv, n, cs, cmask, bloom, bwmask, nsegs, dhist);
+                               recv, n, cs, ds.cmask,
+                               ds.bloom.as<const unsigned long long>(),
+                               ds.bwmask, nsegs, dhist);
         });
     });
 }
 
 static void m2_launch_emit(hipStream_t s, const gx_ord_row *recv, int64_t n,
-                           const void *cset, int cset_width, uint64_t cmask,
-                           const unsigned long long *bloom, uint64_t bwmask,
-                           int dim_join, int nsegs, unsigned long long *dcur,
-                           gx_qual_row *send)
+                           const q3_dimset &ds, int dim_join, int nsegs,
+                           unsigned long long *dcur, gx_qual_row *send)
 {
-    by_width(cset_width, cset, [&](auto *cs) {
+    by_width(ds.width, (const void *) ds.set.p, [&](auto *cs) {
         by_flag(dim_join != 0, [&](auto anti) {
             hipLaunchKernelGGL((k_qual_emit<std::decay_t<decltype(*cs)>,
                                             decltype(anti)::value>),
                                dim3(GRID), dim3(TPB), 0, s,
-                               recv, n, cs, cmask, bloom, bwmask, nsegs, dcur, send);
+                               recv, n, cs, ds.cmask,
+                               ds.bloom.as<const unsigned long long>(),
+                               ds.bwmask, nsegs, dcur, send);
         });
     });
 }
 
-/* Slot map of a join/agg table of `slots` slots over the received keys:
- * order-preserving interpolation when their density over [kmin,kmax] is
- * high enough that runs stay short (the local rule, relaxed by nsegs since
- * each rank holds ~1/nsegs of a globally dense key range), otherwise
- * multiplicative hashing (scale < 0). */
-static gx_slotmap m3_slotmap(int64_t qual, unsigned long long kmin,
-                             unsigned long long kmax, int nsegs, uint64_t slots)
+/* Key stats of the received qualifying rows, the key-0 check and the table
+ * layout they get (nsegs from ctx): the Motion run and its test entry point
+ * size the join/agg table from this */
+static gx_status m3_recv_layout(gx_ctx *ctx, hipStream_t s, const q3_scratch &sc,
+                                const gx_qual_row *rows, int64_t n,
+                                q3_keystats &ks, gx_tbl_layout &TL)
 {
-    gx_slotmap sm;
-    sm.mask = slots - 1;
-    sm.kmin = (int64_t) kmin;
-    sm.scale = -1.0;
-    if (qual > 0 && kmax >= kmin)
+    gx_status st = q3_read_keystats(
+        ctx, s, sc, ks, [&](auto *, auto *kmax, auto *kmin) {
+            hipLaunchKernelGGL(k_rows_minmax, dim3(GRID), dim3(TPB), 0, s,
+                               rows, n, kmax, kmin);
+        });
+    if (st != GX_OK) return st;
+    if (n > 0 && ks.kmin == 0)
     {
-        double range = (double) (kmax - kmin) + 1.0;
-        if ((double) qual >= range / ((double) nsegs * 64.0))
-            sm.scale = (double) slots / range;
+        set_err(ctx, "mid join key 0 received: 0 is the empty-slot "
+                     "sentinel (gpuexec.h gx_q3_prepare_desc)%s", "");
+        return GX_ERR_INVALID;
     }
-    return sm;
-}
-
-/* Table layout from the received rows (pure host): 4-byte keys when every
- * key fits, slots = qual * tf_pct/100 pow2-rounded and always > qual (an
- * open-addressing table with no free slot would never terminate an insert),
- * slot map for exactly that many slots.  Whether a larger cached table is
- * reused instead is the caller's decision; it then re-derives the slot map
- * with m3_slotmap for the slots it really has. */
-struct gx_tbl_layout {
-    int key_width;
-    uint64_t slots;
-    gx_slotmap smap;
-};
-
-static gx_tbl_layout m3_table_layout(int64_t qual, unsigned long long kmin,
-                                     unsigned long long kmax, int nsegs,
-                                     int tf_pct)
-{
-    gx_tbl_layout L;
-    L.key_width = (kmax < (1ULL << 32)) ? 4 : 8;
-    L.slots = (uint64_t) pow2_at_least(
-        std::max<int64_t>(qual * tf_pct / 100, qual) + 1);
-    L.smap = m3_slotmap(qual, kmin, kmax, nsegs, L.slots);
-    return L;
+    TL = q3_table_layout(n, ks.kmin, ks.kmax, ctx->nsegs, q3_table_factor());
+    return GX_OK;
 }
 
 /* Build the join/agg table from packed qualifying rows */
 static void m3_launch_build(hipStream_t s, const gx_qual_row *rows, int64_t n,
-                            int key_width, void *tkey, gx_attrpair *tattr,
-                            gx_aggslot *tagg, gx_slotmap smap)
+                            const q3_hashtbl &t)
 {
-    by_width(key_width, tkey, [&](auto *tk) {
+    by_width(t.width, t.keys.p, [&](auto *tk) {
         hipLaunchKernelGGL(k_build_from_rows<std::decay_t<decltype(*tk)>>,
                            dim3(GRID), dim3(TPB), 0, s, rows, n,
-                           tk, tattr, tagg, smap);
+                           tk, t.attrs.as<gx_attrpair>(),
+                           t.aggs.as<gx_aggslot>(), t.smap);
     });
 }
 
@@ -6988,13 +7056,10 @@ static void q3_launch_probe(hipStream_t s,
                             const gx_col &lk, const gx_col &lp,
                             const gx_col &ld, const gx_col &ls,
                             const uint8_t *lvm, int32_t fop, int32_t flit,
-                            int key_width, const void *tkey,
-                            gx_aggslot *tagg, gx_slotmap smap,
-                            unsigned long long *dhits, bool outer,
-                            unsigned long long *ukey, double *urev,
-                            unsigned long long *ucnt_u, uint64_t umask)
+                            const q3_hashtbl &t, unsigned long long *dhits,
+                            bool outer, const q3_unmatched &un)
 {
-    by_width(key_width, tkey, [&](auto *keys) {
+    by_width(t.width, (const void *) t.keys.p, [&](auto *keys) {
         by_flag(lvm != nullptr, [&](auto vm) {
             by_flag(outer, [&](auto ou) {
                 hipLaunchKernelGGL((k_li_probe_agg_t<std::decay_t<decltype(*keys)>,
@@ -7003,8 +7068,11 @@ static void q3_launch_probe(hipStream_t s,
                                    dim3(GRID), dim3(TPB), 0, s,
                                    lk.dstream, lk.m, lp.dstream, lp.m,
                                    ld.dstream, ld.m, ls.dstream, ls.m, lvm,
-                                   fop, flit, keys, tagg, smap, dhits,
-                                   ukey, urev, ucnt_u, umask);
+                                   fop, flit, keys, t.aggs.as<gx_aggslot>(),
+                                   t.smap, dhits,
+                                   un.key.as<unsigned long long>(),
+                                   un.rev.as<double>(),
+                                   un.cnt.as<unsigned long long>(), un.mask);
             });
         });
     });
@@ -7018,8 +7086,7 @@ static void q3_launch_probe_rank(hipStream_t s,
                                  const uint8_t *lvm, int32_t fop, int32_t flit,
                                  gx_rankview rv, gx_aggslot *dagg,
                                  unsigned long long *dhits, bool outer,
-                                 unsigned long long *ukey, double *urev,
-                                 unsigned long long *ucnt_u, uint64_t umask)
+                                 const q3_unmatched &un)
 {
     by_flag(lvm != nullptr, [&](auto vm) {
         by_flag(outer, [&](auto ou) {
@@ -7030,7 +7097,9 @@ static void q3_launch_probe_rank(hipStream_t s,
                                ld.dstream, ld.m, ls.dstream, ls.m, lvm,
                                fop, flit, (const uint32_t *) nullptr, dagg,
                                gx_slotmap{}, dhits,
-                               ukey, urev, ucnt_u, umask, rv);
+                               un.key.as<unsigned long long>(),
+                               un.rev.as<double>(),
+                               un.cnt.as<unsigned long long>(), un.mask, rv);
         });
     });
 }
@@ -7039,9 +7108,7 @@ static void q3_launch_probe_rank(hipStream_t s,
 static gx_status q3_launch_extract(gx_ctx *ctx, hipStream_t s, int key_width,
                                    const void *tkey, const gx_attrpair *tattr,
                                    const gx_aggslot *tagg, uint64_t tslots,
-                                   int numeric, int64_t *r_okey,
-                                   int32_t *r_odate, int32_t *r_oprio,
-                                   double *r_rev, int64_t *r_cnt,
+                                   int numeric, const q3_results &r,
                                    unsigned long long *dcount)
 {
     uint64_t etiles = (tslots + GX_EXTRACT_TILE - 1) / GX_EXTRACT_TILE;
@@ -7054,7 +7121,9 @@ static gx_status q3_launch_extract(gx_ctx *ctx, hipStream_t s, int key_width,
         hipLaunchKernelGGL(k_extract<std::decay_t<decltype(*keys)>>,
                            dim3((unsigned) etiles), dim3(TPB), 0, s,
                            keys, tattr, tagg, tslots, numeric,
-                           r_okey, r_odate, r_oprio, r_rev, r_cnt, dcount);
+                           r.okey.as<int64_t>(), r.odate.as<int32_t>(),
+                           r.oprio.as<int32_t>(), r.rev.as<double>(),
+                           r.cnt.as<int64_t>(), dcount);
     });
     return GX_OK;
 }
@@ -7103,10 +7172,11 @@ extern "C" gx_status gx_q3_orders_stage_claims(gx_q3 *q, int64_t *blocks,
                                                int64_t *flushes, int64_t *records)
 {
     if (!q || !blocks || !flushes || !records) return GX_ERR_INVALID;
-    if (!q->ran || q->table_mode != 1 || q->orders_mode != 1 || !q->stage_cur)
+    if (!q->ran || q->table_mode != 1 || q->orders_mode != 1 ||
+        !q->rank.stage_cur.p)
         return GX_ERR_STATE;
     unsigned long long cur[2] = {0, 0};
-    HIP_CHK(q->ctx, hipMemcpy(cur, q->stage_cur, sizeof cur, hipMemcpyDeviceToHost));
+    HIP_CHK(q->ctx, hipMemcpy(cur, q->rank.stage_cur.p, sizeof cur, hipMemcpyDeviceToHost));
     *blocks = q->stage_blocks;
     *flushes = (int64_t) cur[1];
     *records = (int64_t) cur[0];
@@ -7136,21 +7206,17 @@ static gx_status q3_orders_local(gx_q3 *q, const q3_runcols &C, bool use_bitmap)
     hipStream_t s = ctx->stream;
     const gx_q3_desc &D = q->desc;
     const gx_col &ok = C.ok, &oc = C.oc, &od = C.od, &op = C.op;
-    if (q->tkey == nullptr)     /* first hash-form run of this q */
+    const q3_dimset &ds = q->dim;
+    q3_hashtbl &t = q->tbl;
+    if (!t.keys.p)              /* first hash-form run of this q */
     {
-        gx_status st = q3_alloc_hash(q, q->hash_tslots);
+        gx_status st = q3_alloc_hash(ctx, t, q->hash_tslots);
         if (st != GX_OK) return st;
     }
-    uint64_t tslots = q->tmask + 1;
     /* keys only: agg/attr slots are initialised at claim (gx_aggslot) */
-    HIP_CHK(ctx, hipMemsetAsync(q->tkey, 0, tslots * q->key_width, s));
+    HIP_CHK(ctx, hipMemsetAsync(t.keys.p, 0, t.slots() * t.width, s));
     if (D.fact_join == 1)
-    {
-        HIP_CHK(ctx, hipMemsetAsync(q->ukey, 0, (q->umask + 1) * 8, s));
-        HIP_CHK(ctx, hipMemsetAsync(q->urev, 0, (q->umask + 1) * 8, s));
-        HIP_CHK(ctx, hipMemsetAsync(q->ucnt_u, 0, (q->umask + 1) * 8, s));
-    }
-    gx_dimbits dbm = {q->dbits, q->dim_kmin, q->dim_range};
+        HIP_CHK(ctx, q->un.clear(s));
     auto launch_build = [&](auto *tk, auto *cs, auto bmode) {
         by_flag(C.ovm != nullptr, [&](auto vm) {
             by_flag(D.dim_join != 0, [&](auto anti) {
@@ -7162,26 +7228,22 @@ static gx_status q3_orders_local(gx_q3 *q, const q3_runcols &C, bool use_bitmap)
                                    dim3(ORDERS_GRID), dim3(TPB), 0, s,
                                    ok.dstream, ok.m, oc.dstream, oc.m, od.dstream, od.m,
                                    op.dstream, op.m, C.ovm, D.mid_filter.op,
-                                   (int32_t) D.mid_filter.literal, cs, q->cmask,
-                                   q->bloom, q->bwmask, dbm,
-                                   tk, q->tattr, q->tagg, q->smap);
+                                   (int32_t) D.mid_filter.literal, cs, ds.cmask,
+                                   ds.bloom.as<unsigned long long>(), ds.bwmask,
+                                   ds.dimbits(), tk, t.attrs.as<gx_attrpair>(),
+                                   t.aggs.as<gx_aggslot>(), t.smap);
             });
         });
     };
-    by_width(q->key_width, q->tkey, [&](auto *tk) {
+    by_width(t.width, t.keys.p, [&](auto *tk) {
         if (use_bitmap)     /* no key set: one set-width instantiation */
             launch_build(tk, (const unsigned int *) nullptr, std::true_type{});
         else
-            by_width(q->cset_width, (const void *) q->cset, [&](auto *cs) {
+            by_width(ds.width, (const void *) ds.set.p, [&](auto *cs) {
                 launch_build(tk, cs, std::false_type{});
             });
     });
     return GX_OK;
-}
-
-static inline gx_rankview q3_rankview(const gx_q3 *q)
-{
-    return {q->rent, q->rank_kmin, q->rank_range, (uint64_t) q->local_qual};
 }
 
 /* Stage 2, single segment, rank form: mark the qualifying keys' bits and the
@@ -7195,25 +7257,27 @@ static gx_status q3_orders_rank(gx_q3 *q, const q3_runcols &C, bool use_bitmap)
     hipStream_t s = ctx->stream;
     const gx_q3_desc &D = q->desc;
     const gx_col &ok = C.ok, &oc = C.oc, &od = C.od, &op = C.op;
-    if (q->dagg == nullptr)     /* first rank-form run of this q */
+    const q3_dimset &ds = q->dim;
+    q3_ranktbl &r = q->rank;
+    if (!r.dagg.p)              /* first rank-form run of this q */
     {
-        gx_status st = q3_alloc_rank(q);
+        gx_status st = q3_alloc_rank(ctx, r, (uint64_t) q->local_qual);
         if (st != GX_OK) return st;
     }
     const bool staged = q3_orders_staged(q->local_qual, ok.m.nrows,
                                          env_int("GX_ORDERS_STAGED", -1));
     q->orders_mode = staged ? 1 : 0;
-    if (staged && q->stage_cur == nullptr)      /* first staged run */
+    if (staged && !r.stage_cur.p)               /* first staged run */
     {
         gx_status st = q3_alloc_stage(q);
         if (st != GX_OK) return st;
     }
-    if (!staged && q->rowmask == nullptr)       /* first two-pass run */
+    if (!staged && !r.rowmask.p)                /* first two-pass run */
     {
         gx_status st = q3_alloc_rowmask(q);
         if (st != GX_OK) return st;
     }
-    uint64_t nwords = (q->rank_range + 63) / 64;
+    uint64_t nwords = r.nwords();
     uint64_t nblk = (nwords + GX_RANK_SCAN_WORDS - 1) / GX_RANK_SCAN_WORDS;
     if (nblk > 0x7FFFFFFFULL)
     {
@@ -7223,19 +7287,14 @@ static gx_status q3_orders_rank(gx_q3 *q, const q3_runcols &C, bool use_bitmap)
     /* the entries (their bit words), and the dense keys so that extract emits no slot past
      * this run's distinct qualifying keys; dattr/dagg are initialised by the
      * fill kernel where a key lands (gx_aggslot) */
-    HIP_CHK(ctx, hipMemsetAsync(q->rent, 0, nwords * sizeof(ulonglong2), s));
-    HIP_CHK(ctx, hipMemsetAsync(q->dkey, 0,
-                                (uint64_t) q->local_qual * q->rank_kw, s));
+    HIP_CHK(ctx, hipMemsetAsync(r.ent.p, 0, nwords * sizeof(ulonglong2), s));
+    HIP_CHK(ctx, hipMemsetAsync(r.dkey.p, 0,
+                                (uint64_t) q->local_qual * r.kw, s));
     if (staged)
-        HIP_CHK(ctx, hipMemsetAsync(q->stage_cur, 0, 16, s));
+        HIP_CHK(ctx, hipMemsetAsync(r.stage_cur.p, 0, 16, s));
     if (D.fact_join == 1)
-    {
-        HIP_CHK(ctx, hipMemsetAsync(q->ukey, 0, (q->umask + 1) * 8, s));
-        HIP_CHK(ctx, hipMemsetAsync(q->urev, 0, (q->umask + 1) * 8, s));
-        HIP_CHK(ctx, hipMemsetAsync(q->ucnt_u, 0, (q->umask + 1) * 8, s));
-    }
-    gx_dimbits dbm = {q->dbits, q->dim_kmin, q->dim_range};
-    const gx_rankview rv = q3_rankview(q);
+        HIP_CHK(ctx, q->un.clear(s));
+    const gx_rankview rv = r.view(q->local_qual);
     const uint64_t cap = (uint64_t) q->local_qual;
     /* two-pass: the grid k_orders_build measured best.  staged: sized from
      * the selectivity (q3_stage_grid), or the caller's in tests. */
@@ -7259,11 +7318,14 @@ static gx_status q3_orders_rank(gx_q3 *q, const q3_runcols &C, bool use_bitmap)
                                        dim3((unsigned) mark_grid), dim3(TPB), 0, s,
                                        ok.dstream, ok.m, oc.dstream, oc.m,
                                        od.dstream, od.m, C.ovm, D.mid_filter.op,
-                                       (int32_t) D.mid_filter.literal, cs, q->cmask,
-                                       q->bloom, q->bwmask, dbm,
-                                       q->rent, q->rank_kmin, q->rank_range,
-                                       q->rowmask, op.dstream, op.m,
-                                       q->stage, q->stage_cur, cap);
+                                       (int32_t) D.mid_filter.literal, cs, ds.cmask,
+                                       ds.bloom.as<unsigned long long>(),
+                                       ds.bwmask, ds.dimbits(),
+                                       r.ent.as<ulonglong2>(), r.kmin, r.range,
+                                       r.rowmask.as<unsigned long long>(),
+                                       op.dstream, op.m,
+                                       r.stage.as<ulonglong2>(),
+                                       r.stage_cur.as<unsigned long long>(), cap);
                 });
             });
         });
@@ -7271,16 +7333,16 @@ static gx_status q3_orders_rank(gx_q3 *q, const q3_runcols &C, bool use_bitmap)
     if (use_bitmap)     /* no key set: one set-width instantiation */
         launch_mark((const unsigned int *) nullptr, std::true_type{});
     else
-        by_width(q->cset_width, (const void *) q->cset, [&](auto *cs) {
+        by_width(ds.width, (const void *) ds.set.p, [&](auto *cs) {
             launch_mark(cs, std::false_type{});
         });
     hipLaunchKernelGGL(k_rank_blocksum, dim3((unsigned) nblk), dim3(TPB), 0, s,
-                       q->rent, nwords, q->rblk);
+                       r.ent.as<ulonglong2>(), nwords, r.blk.as<uint32_t>());
     hipLaunchKernelGGL(k_rank_topscan, dim3(1), dim3(TPB), 0, s,
-                       q->rblk, (int) nblk);
+                       r.blk.as<uint32_t>(), (int) nblk);
     hipLaunchKernelGGL(k_rank_localscan, dim3((unsigned) nblk), dim3(TPB), 0, s,
-                       q->rent, nwords, q->rblk);
-    by_width(q->rank_kw, q->dkey, [&](auto *dk) {
+                       r.ent.as<ulonglong2>(), nwords, r.blk.as<uint32_t>());
+    by_width(r.kw, r.dkey.p, [&](auto *dk) {
         if (staged)
         {
             /* the record count is on the device: grid from the capacity */
@@ -7288,15 +7350,17 @@ static gx_status q3_orders_rank(gx_q3 *q, const q3_runcols &C, bool use_bitmap)
                 std::max<uint64_t>((cap + TPB - 1) / TPB, 1), ORDERS_GRID);
             hipLaunchKernelGGL(k_orders_fill_staged<std::decay_t<decltype(*dk)>>,
                                dim3((unsigned) fb), dim3(TPB), 0, s,
-                               q->stage, q->stage_cur, cap, rv, dk,
-                               q->dattr, q->dagg);
+                               r.stage.as<ulonglong2>(),
+                               r.stage_cur.as<unsigned long long>(), cap, rv, dk,
+                               r.dattr.as<gx_attrpair>(), r.dagg.as<gx_aggslot>());
         }
         else
             hipLaunchKernelGGL(k_orders_fill<std::decay_t<decltype(*dk)>>,
                                dim3(ORDERS_GRID), dim3(TPB), 0, s,
                                ok.dstream, ok.m, od.dstream, od.m,
-                               op.dstream, op.m, q->rowmask, rv, dk,
-                               q->dattr, q->dagg);
+                               op.dstream, op.m,
+                               r.rowmask.as<unsigned long long>(), rv, dk,
+                               r.dattr.as<gx_attrpair>(), r.dagg.as<gx_aggslot>());
     });
     return GX_OK;
 }
@@ -7325,31 +7389,17 @@ static gx_status q3_orders_motion(gx_q3 *q, const q3_runcols &C,
     HIP_CHK(ctx, hipEventRecord(mev0, ms));
 
     /* Motion 1: filtered orders by route(o_custkey).  Exchange buffers
-     * are cached in gx_q3 (grow-only) — per-step hipMalloc would
+     * are cached in gx_q3 (grow-only) — per-step allocation would
      * dominate at high rank counts. */
-    auto grow = [&](auto *&p, uint64_t &cap, uint64_t want) -> gx_status {
-        if (want <= cap) return GX_OK;
-        if (p) (void) hipFree(p);
-        p = nullptr;
-        cap = 0;
-        hipError_t e = hipMalloc(&p, std::max<uint64_t>(want, 1) *
-                                      sizeof(**(&p)));
-        if (e != hipSuccess) return GX_ERR_OOM;
-        cap = want;
-        return GX_OK;
-    };
-    if (!q->m_hist)
-    {
-        HIP_CHK(ctx, hipMalloc(&q->m_hist, n * 8));
-        HIP_CHK(ctx, hipMalloc(&q->m_cur, n * 8));
-        HIP_CHK(ctx, hipMalloc(&q->m_cnts_mine, n * 8));
-        HIP_CHK(ctx, hipMalloc(&q->m_cnts_all, (int64_t) n * n * 8));
-    }
+    const q3_dimset &ds = q->dim;
+    HIP_CHK(ctx, q->m_hist.reserve(n * 8));
+    HIP_CHK(ctx, q->m_cur.reserve(n * 8));
+    HIP_CHK(ctx, q->m_cnts_all.reserve((int64_t) n * n * 8));
     /* Motion-1 count exchange: the per-dest histogram goes straight
      * into the all-gather, so ONE host sync yields both this rank's
      * send layout (its own row) and every peer's counts (r2: the two
      * separate count syncs were ~half the fixed motion latency) */
-    unsigned long long *dhist = q->m_hist;
+    unsigned long long *dhist = q->m_hist.as<unsigned long long>();
     /* destination-aware bloom prefilter (semi join only): all-gather
      * every rank's dim bloom, then only ship orders whose fk passes
      * the DESTINATION's bloom — the runtime filter pushed across the
@@ -7357,20 +7407,18 @@ static gx_status q3_orders_motion(gx_q3 *q, const q3_runcols &C,
     const unsigned long long *bloom_all = nullptr;
     if (m1_prefilter_on(D.dim_join))
     {
-        uint64_t bwords = q->bwmask + 1;
-        if (!q->m_bloom_all)
-            HIP_CHK(ctx, hipMalloc(&q->m_bloom_all,
-                                   (uint64_t) n * bwords * 8));
+        uint64_t bwords = ds.bwmask + 1;
+        HIP_CHK(ctx, q->m_bloom_all.reserve((uint64_t) n * bwords * 8));
         HIP_CHK(ctx, hipStreamWaitEvent(ms, dim_done, 0));
-        RCCL_CHK(ctx, ncclAllGather(q->bloom, q->m_bloom_all, bwords,
+        RCCL_CHK(ctx, ncclAllGather(ds.bloom.p, q->m_bloom_all.p, bwords,
                                     ncclUint64, ctx->comm, ms));
-        bloom_all = q->m_bloom_all;
+        bloom_all = q->m_bloom_all.as<unsigned long long>();
     }
     HIP_CHK(ctx, hipMemsetAsync(dhist, 0, n * 8, ms));
     m1_launch_hist(ms, od, oc, C.ovm, D.mid_filter.op,
                    (int32_t) D.mid_filter.literal, n, D.dim_join,
-                   bloom_all, q->bwmask, dhist);
-    unsigned long long *dcnts_all = q->m_cnts_all;
+                   bloom_all, ds.bwmask, dhist);
+    unsigned long long *dcnts_all = q->m_cnts_all.as<unsigned long long>();
     double t_counts = 0;
     auto now_ms = []() {
         return (double) std::chrono::duration_cast<std::chrono::nanoseconds>(
@@ -7385,16 +7433,18 @@ static gx_status q3_orders_motion(gx_q3 *q, const q3_runcols &C,
     HIP_CHK(ctx, hipStreamSynchronize(ms));
     t_counts += now_ms() - tc0;
     const gx_mlayout L1 = m_exchange_layout(cnts_all.data(), n, ctx->seg);
-    if (grow(q->m_send1, q->m_send1_cap, L1.send_n) != GX_OK) return GX_ERR_OOM;
-    gx_ord_row *send1 = q->m_send1;
-    unsigned long long *dcur = q->m_cur;
+    if (q->m_send1.reserve(L1.send_n * sizeof(gx_ord_row)) != hipSuccess)
+        return GX_ERR_OOM;
+    gx_ord_row *send1 = q->m_send1.as<gx_ord_row>();
+    unsigned long long *dcur = q->m_cur.as<unsigned long long>();
     HIP_CHK(ctx, hipMemcpyAsync(dcur, L1.soff.data(), n * 8, hipMemcpyHostToDevice, ms));
     m1_launch_emit(ms, ok, oc, od, op, C.ovm, D.mid_filter.op,
                    (int32_t) D.mid_filter.literal, n, D.dim_join,
-                   bloom_all, q->bwmask, dcur, send1);
+                   bloom_all, ds.bwmask, dcur, send1);
     unsigned long long recv1_n = L1.recv_n;
-    if (grow(q->m_recv1, q->m_recv1_cap, recv1_n) != GX_OK) return GX_ERR_OOM;
-    gx_ord_row *recv1 = q->m_recv1;
+    if (q->m_recv1.reserve(recv1_n * sizeof(gx_ord_row)) != hipSuccess)
+        return GX_ERR_OOM;
+    gx_ord_row *recv1 = q->m_recv1.as<gx_ord_row>();
     evholder pev0, pev1, pev2, pev3;
     HIP_CHK(ctx, pev0.create()); HIP_CHK(ctx, pev1.create());
     HIP_CHK(ctx, pev2.create()); HIP_CHK(ctx, pev3.create());
@@ -7411,8 +7461,7 @@ static gx_status q3_orders_motion(gx_q3 *q, const q3_runcols &C,
      * stream to finish */
     HIP_CHK(ctx, hipStreamWaitEvent(ms, dim_done, 0));
     HIP_CHK(ctx, hipMemsetAsync(dhist, 0, n * 8, ms));
-    m2_launch_hist(ms, recv1, (int64_t) recv1_n, q->cset, q->cset_width,
-                   q->cmask, q->bloom, q->bwmask, D.dim_join, n, dhist);
+    m2_launch_hist(ms, recv1, (int64_t) recv1_n, ds, D.dim_join, n, dhist);
     /* Motion-2 count exchange: same single-sync shape */
     tc0 = now_ms();
     RCCL_CHK(ctx, ncclAllGather(dhist, dcnts_all, n, ncclUint64, ctx->comm, ms));
@@ -7421,14 +7470,15 @@ static gx_status q3_orders_motion(gx_q3 *q, const q3_runcols &C,
     HIP_CHK(ctx, hipStreamSynchronize(ms));
     t_counts += now_ms() - tc0;
     const gx_mlayout L2 = m_exchange_layout(cnts_all.data(), n, ctx->seg);
-    if (grow(q->m_send2, q->m_send2_cap, L2.send_n) != GX_OK) return GX_ERR_OOM;
-    gx_qual_row *send2 = q->m_send2;
+    if (q->m_send2.reserve(L2.send_n * sizeof(gx_qual_row)) != hipSuccess)
+        return GX_ERR_OOM;
+    gx_qual_row *send2 = q->m_send2.as<gx_qual_row>();
     HIP_CHK(ctx, hipMemcpyAsync(dcur, L2.soff.data(), n * 8, hipMemcpyHostToDevice, ms));
-    m2_launch_emit(ms, recv1, (int64_t) recv1_n, q->cset, q->cset_width,
-                   q->cmask, q->bloom, q->bwmask, D.dim_join, n, dcur, send2);
+    m2_launch_emit(ms, recv1, (int64_t) recv1_n, ds, D.dim_join, n, dcur, send2);
     unsigned long long recv2_n = L2.recv_n;
-    if (grow(q->m_recv2, q->m_recv2_cap, recv2_n) != GX_OK) return GX_ERR_OOM;
-    gx_qual_row *recv2 = q->m_recv2;
+    if (q->m_recv2.reserve(recv2_n * sizeof(gx_qual_row)) != hipSuccess)
+        return GX_ERR_OOM;
+    gx_qual_row *recv2 = q->m_recv2.as<gx_qual_row>();
     HIP_CHK(ctx, hipEventRecord(pev2, ms));
     {
         gx_status xst = m_exchange_payload(ctx, ms, send2, recv2, L2,
@@ -7440,48 +7490,32 @@ static gx_status q3_orders_motion(gx_q3 *q, const q3_runcols &C,
     int64_t qual = (int64_t) recv2_n;
     /* key stats over the received rows — the motion path then gets the
      * same u32/interpolation table layout as the local path */
-    HIP_CHK(ctx, hipMemsetAsync(q->dhits, 0, 8, ms));
-    HIP_CHK(ctx, hipMemsetAsync(q->dmin, 0xFF, 8, ms));
-    hipLaunchKernelGGL(k_rows_minmax, dim3(GRID), dim3(TPB), 0, ms,
-                       recv2, qual, q->dhits, q->dmin);
-    unsigned long long kmax = 0, kmin = 0;
-    HIP_CHK(ctx, hipMemcpyAsync(&kmax, q->dhits, 8, hipMemcpyDeviceToHost, ms));
-    HIP_CHK(ctx, hipMemcpyAsync(&kmin, q->dmin, 8, hipMemcpyDeviceToHost, ms));
-    HIP_CHK(ctx, hipStreamSynchronize(ms));
-    if (qual > 0 && kmin == 0)
+    q3_keystats ks;
+    gx_tbl_layout TL;
     {
-        set_err(ctx, "mid join key 0 received: 0 is the empty-slot "
-                     "sentinel (gpuexec.h gx_q3_prepare_desc)%s", "");
-        return GX_ERR_INVALID;
+        gx_status lst = m3_recv_layout(ctx, ms, q->sc, recv2, qual, ks, TL);
+        if (lst != GX_OK) return lst;
     }
-    /* same tuned fill factor as the local path (tf=300) */
-    const gx_tbl_layout TL = m3_table_layout(
-        qual, kmin, kmax, ctx->nsegs, env_int("GX_TABLE_FACTOR_PCT", 300));
-    int want_kw = TL.key_width;
-    uint64_t tslots = TL.slots;
+    q3_hashtbl &t = q->tbl;
     /* motion path sizes from the exchanged counts each run; qual can
-     * grow within the same pow2 table size, so rescap is checked too */
-    if (q->tkey == nullptr || tslots > q->tmask + 1 || want_kw != q->key_width ||
-        qual + q->u_cap > q->rescap)
+     * grow within the same pow2 table size, so the result capacity is
+     * checked too */
+    if (!t.keys.p || TL.slots > t.slots() || TL.key_width != t.width ||
+        qual + q->un.cap > q->res.cap)
     {
-        q->key_width = want_kw;
-        gx_status ast = q3_alloc_table(q, tslots, qual);
+        t.width = TL.key_width;
+        gx_status ast = q3_alloc_table(q, TL.slots, qual);
         if (ast != GX_OK) return ast;
     }
     /* keys only: agg/attr slots are initialised at claim (gx_aggslot) */
-    HIP_CHK(ctx, hipMemsetAsync(q->tkey, 0, (q->tmask + 1) * q->key_width, ms));
+    HIP_CHK(ctx, hipMemsetAsync(t.keys.p, 0, t.slots() * t.width, ms));
     if (D.fact_join == 1)
-    {
-        HIP_CHK(ctx, hipMemsetAsync(q->ukey, 0, (q->umask + 1) * 8, ms));
-        HIP_CHK(ctx, hipMemsetAsync(q->urev, 0, (q->umask + 1) * 8, ms));
-        HIP_CHK(ctx, hipMemsetAsync(q->ucnt_u, 0, (q->umask + 1) * 8, ms));
-    }
+        HIP_CHK(ctx, q->un.clear(ms));
     /* a reused cached table may be larger than this run's layout */
-    q->smap = (q->tmask + 1 == TL.slots)
-                  ? TL.smap
-                  : m3_slotmap(qual, kmin, kmax, ctx->nsegs, q->tmask + 1);
-    m3_launch_build(ms, recv2, qual, q->key_width, q->tkey,
-                    q->tattr, q->tagg, q->smap);
+    t.smap = (t.slots() == TL.slots)
+                 ? TL.smap
+                 : q3_slotmap(qual, ks.kmin, ks.kmax, ctx->nsegs, t.slots());
+    m3_launch_build(ms, recv2, qual, t);
     HIP_CHK(ctx, hipEventRecord(mev1, ms));
     HIP_CHK(ctx, hipStreamSynchronize(ms));
     float mms = 0, p01 = 0, p23 = 0;
@@ -7503,15 +7537,17 @@ static gx_status q3_probe_agg(gx_q3 *q, const q3_runcols &C)
     hipStream_t s = ctx->stream;
     const gx_q3_desc &D = q->desc;
     const gx_col &lk = C.lk, &lp = C.lp, &ld = C.ld, &ls = C.ls;
-    unsigned long long *dhits = q->dhits;
+    const q3_hashtbl &t = q->tbl;
+    unsigned long long *dhits = q->sc.word(q3_scratch::HITS);
+    unsigned long long *derr = q->sc.word(q3_scratch::ERR);
     HIP_CHK(ctx, hipMemsetAsync(dhits, 0, 8, s));
     if (lk.format == 1)
     {
         if (q->numeric) { set_err(ctx, "numeric+RLE combo not supported%s", ""); return GX_ERR_INVALID; }
-        HIP_CHK(ctx, hipMemsetAsync(q->dmin, 0, 8, s));   /* borrowed err flag */
+        HIP_CHK(ctx, hipMemsetAsync(derr, 0, 8, s));
         int64_t nb = lk.nblocks;
         int rgrid = (int) std::min<int64_t>(std::max<int64_t>(nb, 1), 16384);
-        by_width(q->key_width, (const void *) q->tkey, [&](auto *keys) {
+        by_width(t.width, (const void *) t.keys.p, [&](auto *keys) {
             by_flag(C.lvm != nullptr, [&](auto vm) {
                 hipLaunchKernelGGL((k_li_probe_agg_rle<std::decay_t<decltype(*keys)>,
                                                        decltype(vm)::value>),
@@ -7519,19 +7555,19 @@ static gx_status q3_probe_agg(gx_q3 *q, const q3_runcols &C)
                                    lk.dstream, lk.ddir, nb, lp.dstream, lp.m,
                                    ld.dstream, ld.m, ls.dstream, ls.m, C.lvm,
                                    D.fact_filter.op, (int32_t) D.fact_filter.literal,
-                                   keys, q->tagg, q->smap, dhits,
-                                   (int *) q->dmin);
+                                   keys, t.aggs.as<gx_aggslot>(), t.smap, dhits,
+                                   (int *) derr);
             });
         });
         int herr = 0;
-        HIP_CHK(ctx, hipMemcpyAsync(&herr, q->dmin, 4, hipMemcpyDeviceToHost, s));
+        HIP_CHK(ctx, hipMemcpyAsync(&herr, derr, 4, hipMemcpyDeviceToHost, s));
         HIP_CHK(ctx, hipStreamSynchronize(s));
         if (herr) { set_err(ctx, "malformed RLE block in fused scan%s", ""); return GX_ERR_INVALID; }
     }
     else if (q->numeric)
     {
-        HIP_CHK(ctx, hipMemsetAsync(q->dmin, 0, 8, s));   /* borrowed err flag */
-        by_width(q->key_width, (const void *) q->tkey, [&](auto *keys) {
+        HIP_CHK(ctx, hipMemsetAsync(derr, 0, 8, s));
+        by_width(t.width, (const void *) t.keys.p, [&](auto *keys) {
             by_flag(C.lvm != nullptr, [&](auto vm) {
                 by_flag(D.fact_join == 1, [&](auto outer) {
                     hipLaunchKernelGGL((k_li_probe_agg_num<std::decay_t<decltype(*keys)>,
@@ -7541,64 +7577,67 @@ static gx_status q3_probe_agg(gx_q3 *q, const q3_runcols &C)
                                        lk.dstream, lk.m, lp.dstream, lp.m, ld.dstream, ld.m,
                                        ls.dstream, ls.m, C.lvm, D.fact_filter.op,
                                        (int32_t) D.fact_filter.literal, keys,
-                                       (gx_aggslot_num *) q->tagg, q->smap,
-                                       dhits, (int *) q->dmin,
-                                       q->ukey, (unsigned long long *) q->urev,
-                                       q->ucnt_u, q->umask);
+                                       t.aggs.as<gx_aggslot_num>(), t.smap,
+                                       dhits, (int *) derr,
+                                       q->un.key.as<unsigned long long>(),
+                                       q->un.rev.as<unsigned long long>(),
+                                       q->un.cnt.as<unsigned long long>(),
+                                       q->un.mask);
                 });
             });
         });
         int herr = 0;
-        HIP_CHK(ctx, hipMemcpyAsync(&herr, q->dmin, 4, hipMemcpyDeviceToHost, s));
+        HIP_CHK(ctx, hipMemcpyAsync(&herr, derr, 4, hipMemcpyDeviceToHost, s));
         HIP_CHK(ctx, hipStreamSynchronize(s));
         if (herr) { set_err(ctx, "numeric overflow in aggregation%s", ""); return GX_ERR_INVALID; }
     }
     else if (q->table_mode == 1)
         q3_launch_probe_rank(
             s, lk, lp, ld, ls, C.lvm, D.fact_filter.op,
-            (int32_t) D.fact_filter.literal, q3_rankview(q),
-            q->dagg, dhits, D.fact_join == 1, q->ukey, q->urev, q->ucnt_u,
-            q->umask);
+            (int32_t) D.fact_filter.literal, q->rank.view(q->local_qual),
+            q->rank.dagg.as<gx_aggslot>(), dhits, D.fact_join == 1, q->un);
     else
         q3_launch_probe(
             s, lk, lp, ld, ls, C.lvm, D.fact_filter.op,
-            (int32_t) D.fact_filter.literal, q->key_width, q->tkey, q->tagg,
-            q->smap, dhits, D.fact_join == 1, q->ukey, q->urev, q->ucnt_u,
-            q->umask);
+            (int32_t) D.fact_filter.literal, t, dhits, D.fact_join == 1, q->un);
     return GX_OK;
 }
 
 /* Stage 4: extract the groups (and the LEFT-OUTER unmatched ones) into the
- * result arrays; the group count lands in q->dcount */
+ * result arrays; the group count lands in the GROUPS scratch word */
 static gx_status q3_extract(gx_q3 *q)
 {
     gx_ctx *ctx = q->ctx;
     hipStream_t s = ctx->stream;
-    unsigned long long *dcount = q->dcount;
+    const q3_results &r = q->res;
+    unsigned long long *dcount = q->sc.word(q3_scratch::GROUPS);
     HIP_CHK(ctx, hipMemsetAsync(dcount, 0, 8, s));
-    if (q->r_flags)
-        HIP_CHK(ctx, hipMemsetAsync(q->r_flags, 0, q->rescap, s));
+    HIP_CHK(ctx, hipMemsetAsync(r.flags.p, 0, r.cap, s));
     /* one block per fixed tile of the table; k_extract_u keeps its own grid */
     const int egrid = 32768;
     {
         /* rank form: the same kernel over the dense arrays, whose slots at
          * or past this run's distinct keys hold key 0 (cleared per run) */
         gx_status est = q->table_mode == 1
-            ? q3_launch_extract(ctx, s, q->rank_kw, q->dkey, q->dattr, q->dagg,
-                                (uint64_t) q->local_qual, q->numeric,
-                                q->r_okey, q->r_odate, q->r_oprio,
-                                q->r_rev, q->r_cnt, dcount)
-            : q3_launch_extract(ctx, s, q->key_width, q->tkey, q->tattr,
-                                q->tagg, q->tmask + 1, q->numeric,
-                                q->r_okey, q->r_odate, q->r_oprio,
-                                q->r_rev, q->r_cnt, dcount);
+            ? q3_launch_extract(ctx, s, q->rank.kw, q->rank.dkey.p,
+                                q->rank.dattr.as<gx_attrpair>(),
+                                q->rank.dagg.as<gx_aggslot>(),
+                                (uint64_t) q->local_qual, q->numeric, r, dcount)
+            : q3_launch_extract(ctx, s, q->tbl.width, q->tbl.keys.p,
+                                q->tbl.attrs.as<gx_attrpair>(),
+                                q->tbl.aggs.as<gx_aggslot>(), q->tbl.slots(),
+                                q->numeric, r, dcount);
         if (est != GX_OK) return est;
     }
     if (q->desc.fact_join == 1)
         hipLaunchKernelGGL(k_extract_u, dim3(egrid), dim3(TPB), 0, s,
-                           q->ukey, q->urev, q->ucnt_u, q->umask + 1,
-                           q->r_okey, q->r_odate, q->r_oprio, q->r_rev,
-                           q->r_cnt, q->r_flags, dcount, q->rescap);
+                           q->un.key.as<unsigned long long>(),
+                           q->un.rev.as<double>(),
+                           q->un.cnt.as<unsigned long long>(), q->un.mask + 1,
+                           r.okey.as<int64_t>(), r.odate.as<int32_t>(),
+                           r.oprio.as<int32_t>(), r.rev.as<double>(),
+                           r.cnt.as<int64_t>(), r.flags.as<uint8_t>(), dcount,
+                           r.cap);
     return GX_OK;
 }
 
@@ -7633,18 +7672,19 @@ extern "C" gx_status gx_q3_run(gx_q3 *q)
         q3_col(q, q->ord, D.mid_filter.col), q3_col(q, q->ord, D.mid_attr2_col),
         q3_col(q, q->li, D.fact_key_col), q3_col(q, q->li, D.fact_a_col),
         q3_col(q, q->li, D.fact_b_col), q3_col(q, q->li, D.fact_filter.col),
-        q->qvm_mid ? q->qvm_mid : q->ord->dvmap,
-        q->qvm_fact ? q->qvm_fact : (q->li ? q->li->dvmap : nullptr)};
+        q->qvm_mid.p ? q->qvm_mid.as<uint8_t>() : q->ord->dvmap,
+        q->qvm_fact.p ? q->qvm_fact.as<uint8_t>()
+                      : (q->li ? q->li->dvmap : nullptr)};
 
     /* ---- stage 1: customer BUILDING membership (rebuilt every run) ----
      * the local path reads the bitmap when sizing chose one; the Motion path
      * reads set+bloom.  Only that one is cleared and filled. */
     bool local_path = ctx->nsegs == 1 && env_int("GX_FORCE_MOTION", 0) == 0;
-    bool use_bitmap = q->dim_bitmap && local_path;
+    bool use_bitmap = q->dim.bitmap && local_path;
     q->dim_mode = use_bitmap ? 1 : 0;
     HIP_CHK(ctx, hipEventRecord(ev[0], s));
     {
-        gx_status st = q3_build_dim(q, use_bitmap);
+        gx_status st = dim_launch_build(ctx, s, q3_dim_scan(q), q->dim, use_bitmap);
         if (st != GX_OK) return st;
     }
     HIP_CHK(ctx, hipEventRecord(ev[1], s));
@@ -7657,14 +7697,14 @@ extern "C" gx_status gx_q3_run(gx_q3 *q)
     double ms_motion = 0.0;
     /* table form of this run: rank for dense keys on the local path under
      * the plain f64 probe over a flat fact key; hash for everything else */
-    q->table_mode = (q->rank_ok && local_path && !q->numeric &&
+    q->table_mode = (q->rank.ok && local_path && !q->numeric &&
                      C.lk.format == 0) ? 1 : 0;
     if (local_path)
     {
         gx_status st = q->table_mode == 1 ? q3_orders_rank(q, C, use_bitmap)
                                           : q3_orders_local(q, C, use_bitmap);
         if (st != GX_OK) return st;
-        qual = q->rescap;
+        qual = q->res.cap;
     }
     else
     {
@@ -7689,18 +7729,20 @@ extern "C" gx_status gx_q3_run(gx_q3 *q)
     HIP_CHK(ctx, hipEventRecord(ev[4], s));
 
     unsigned long long ngroups = 0, hits = 0;
-    HIP_CHK(ctx, hipMemcpyAsync(&ngroups, q->dcount, 8, hipMemcpyDeviceToHost, s));
-    HIP_CHK(ctx, hipMemcpyAsync(&hits, q->dhits, 8, hipMemcpyDeviceToHost, s));
+    HIP_CHK(ctx, hipMemcpyAsync(&ngroups, q->sc.word(q3_scratch::GROUPS), 8,
+                                hipMemcpyDeviceToHost, s));
+    HIP_CHK(ctx, hipMemcpyAsync(&hits, q->sc.word(q3_scratch::HITS), 8,
+                                hipMemcpyDeviceToHost, s));
     HIP_CHK(ctx, hipStreamSynchronize(s));
     HIP_CHK(ctx, hipGetLastError());
-    if (q->desc.fact_join == 1 && (int64_t) ngroups > q->rescap)
+    if (q->desc.fact_join == 1 && (int64_t) ngroups > q->res.cap)
     {
         /* a sizing error must be an error, not a stray write: k_extract_u
-         * stopped writing at rescap */
+         * stopped writing at the result capacity */
         q->ran = false;
         char buf[96];
         snprintf(buf, sizeof buf, "%lld groups, capacity %lld",
-                 (long long) ngroups, (long long) q->rescap);
+                 (long long) ngroups, (long long) q->res.cap);
         set_err(ctx, "q3: extract overflow (%s)", buf);
         return GX_ERR_INVALID;
     }
@@ -7729,8 +7771,6 @@ extern "C" gx_status gx_q3_run(gx_q3 *q)
     gx_table_logical_bytes(q->li, &b); bb += b;
     q->stats.bytes_scanned = bb;
 
-    /* dcount/dhits are cached run-state, freed in gx_q3_free; events are
-     * RAII (evholder) */
     q->ran = true;
     return GX_OK;
 }
@@ -7753,14 +7793,12 @@ extern "C" gx_status gx_q3_result(gx_q3 *q, gx_q3_group **out, int64_t *ngroups)
     std::vector<uint8_t> flags(n, 0);
     if (n)
     {
-        HIP_CHK(ctx, hipMemcpy(okey.data(), q->r_okey, n * 8, hipMemcpyDeviceToHost));
-        HIP_CHK(ctx, hipMemcpy(odate.data(), q->r_odate, n * 4, hipMemcpyDeviceToHost));
-        HIP_CHK(ctx, hipMemcpy(oprio.data(), q->r_oprio, n * 4, hipMemcpyDeviceToHost));
-        HIP_CHK(ctx, hipMemcpy(rev.data(), q->r_rev, n * 8, hipMemcpyDeviceToHost));
-        HIP_CHK(ctx, hipMemcpy(cnt.data(), q->r_cnt, n * 8, hipMemcpyDeviceToHost));
-        if (q->r_flags)
-            HIP_CHK(ctx, hipMemcpy(flags.data(), q->r_flags, n,
-                                   hipMemcpyDeviceToHost));
+        HIP_CHK(ctx, hipMemcpy(okey.data(), q->res.okey.p, n * 8, hipMemcpyDeviceToHost));
+        HIP_CHK(ctx, hipMemcpy(odate.data(), q->res.odate.p, n * 4, hipMemcpyDeviceToHost));
+        HIP_CHK(ctx, hipMemcpy(oprio.data(), q->res.oprio.p, n * 4, hipMemcpyDeviceToHost));
+        HIP_CHK(ctx, hipMemcpy(rev.data(), q->res.rev.p, n * 8, hipMemcpyDeviceToHost));
+        HIP_CHK(ctx, hipMemcpy(cnt.data(), q->res.cnt.p, n * 8, hipMemcpyDeviceToHost));
+        HIP_CHK(ctx, hipMemcpy(flags.data(), q->res.flags.p, n, hipMemcpyDeviceToHost));
     }
     std::vector<int64_t> idx(n);
     for (int64_t i = 0; i < n; i++) idx[i] = i;
@@ -7923,9 +7961,12 @@ static gx_status topn_run(gx_ctx *ctx, const int64_t *okey,
 extern "C" gx_status gx_q3_topn(gx_q3 *q, int topn, gx_q3_group *out, int64_t *nout)
 {
     if (!q || !q->ran || topn <= 0 || topn > TOPK) return GX_ERR_STATE;
-    const uint8_t *gflags = q->desc.fact_join == 1 ? q->r_flags : nullptr;
-    return topn_run(q->ctx, q->r_okey, q->r_odate, q->r_oprio, q->r_rev,
-                    q->r_cnt, gflags, q->ngroups, q->numeric, topn, out, nout);
+    const q3_results &r = q->res;
+    const uint8_t *gflags = q->desc.fact_join == 1 ? r.flags.as<uint8_t>() : nullptr;
+    return topn_run(q->ctx, r.okey.as<int64_t>(), r.odate.as<int32_t>(),
+                    r.oprio.as<int32_t>(), r.rev.as<double>(),
+                    r.cnt.as<int64_t>(), gflags, q->ngroups, q->numeric, topn,
+                    out, nout);
 }
 
 /* test-only: the top-N stage over caller-supplied host SoA arrays (rev holds
@@ -7991,8 +8032,6 @@ extern "C" int gx_selftest_topn_merge(const int64_t *cidx, const int64_t *okey,
 
 extern "C" gx_status gx_q3_free(gx_q3 *q)
 {
-    if (!q) return GX_OK;
-    q3_free_runstate(q);
     delete q;
     return GX_OK;
 }
@@ -9517,22 +9556,22 @@ static gx_status test_m1_impl(gx_ctx *ctx, gx_table *orders, gx_filter f,
     return GX_OK;
 }
 
-/* one rank's dim membership as the Motion path holds it: hash set + bloom,
- * sized as q3_size_and_alloc sizes them.  bwords == 0 takes this rank's own
- * bloom size; a caller-chosen one stands in for the max-over-ranks
- * agreement. */
-struct test_dimset {
-    devbuf set, bloom;
-    uint64_t cmask = 0, bwmask = 0;
-    int width = 8;
-    int64_t nsel = 0;
-};
-
+/* one rank's dim membership as the Motion path holds it: the production
+ * q3_dimset, counted, sized and built by q3_dim_size_build without the
+ * bitmap.  bwords == 0 takes this rank's own bloom size; a caller-chosen one
+ * stands in for the max-over-ranks agreement.  q3_dim_size_build agrees
+ * across ranks on a multi-rank communicator, which one rank calling a test
+ * entry point alone would wait on for ever: such a context is refused. */
 static gx_status test_build_dim(gx_ctx *ctx, gx_table *customer, int32_t op,
                                 int64_t literal, uint64_t bwords,
-                                test_dimset &ds)
+                                q3_dimset &ds, int64_t *nsel = nullptr)
 {
     if (!ctx || !test_cols_are(customer, {8, 1})) return GX_ERR_INVALID;
+    if (ctx->nsegs > 1 && ctx->comm)
+    {
+        set_err(ctx, "test_dim: not on a multi-rank communicator%s", "");
+        return GX_ERR_STATE;
+    }
     if (!gx_fold_filter(1, &op, &literal))
     {
         set_err(ctx, "test_dim: filter op must be in 0..5%s", "");
@@ -9543,41 +9582,13 @@ static gx_status test_build_dim(gx_ctx *ctx, gx_table *customer, int32_t op,
         set_err(ctx, "test_dim: bwords must be a power of two >= 4096%s", "");
         return GX_ERR_INVALID;
     }
-    hipStream_t s = ctx->stream;
-    const gx_col &ck = customer->cols[0], &cm = customer->cols[1];
-    const uint8_t *cvm = customer->dvmap;
-    devbuf cnt_b;
-    HIP_CHK(ctx, cnt_b.alloc(24));
-    unsigned long long *dc = cnt_b.as<unsigned long long>();
-    HIP_CHK(ctx, hipMemsetAsync(dc, 0, 16, s));
-    HIP_CHK(ctx, hipMemsetAsync(dc + 2, 0xFF, 8, s));
-    dim_launch_count(s, ck, nullptr, cm, op, literal, cvm, dc, dc + 1, dc + 2);
-    unsigned long long st[3];
-    HIP_CHK(ctx, hipMemcpyAsync(st, dc, 24, hipMemcpyDeviceToHost, s));
-    HIP_CHK(ctx, hipStreamSynchronize(s));
-    unsigned long long n_building = st[0], cmax = st[1], cmin = st[2];
-    if (n_building > 0 && cmin == 0)
-    {
-        set_err(ctx, "dim join key 0 found: 0 is reserved as the empty-slot "
-                     "sentinel (gpuexec.h gx_q3_prepare_desc)%s", "");
-        return GX_ERR_INVALID;
-    }
-    ds.nsel = (int64_t) n_building;
-    ds.width = (cmax < (1ULL << 32)) ? 4 : 8;
-    uint64_t cslots = (uint64_t) pow2_at_least((int64_t) n_building * 2);
-    if (!bwords)
-        bwords = (uint64_t) pow2_at_least(
-            std::max<int64_t>((int64_t) n_building * 8 / 64, 4096));
-    ds.cmask = cslots - 1;
-    ds.bwmask = bwords - 1;
-    HIP_CHK(ctx, ds.set.alloc(cslots * ds.width));
-    HIP_CHK(ctx, ds.bloom.alloc(bwords * 8));
-    HIP_CHK(ctx, hipMemsetAsync(ds.set.p, 0, cslots * ds.width, s));
-    HIP_CHK(ctx, hipMemsetAsync(ds.bloom.p, 0, bwords * 8, s));
-    dim_launch_build(s, ck, nullptr, cm, op, literal, cvm, ds.set.p, ds.width,
-                     ds.cmask, ds.bloom.as<unsigned long long>(), ds.bwmask,
-                     nullptr, 0, 0);
-    return GX_OK;
+    q3_scratch sc;
+    HIP_CHK(ctx, sc.ensure());
+    int state = 0;
+    return q3_dim_size_build(ctx, ctx->stream, sc,
+                             {customer->cols[0], customer->cols[1], nullptr, op,
+                              literal, customer->dvmap},
+                             false, false, bwords, ds, &state, nsel);
 }
 
 extern "C" gx_status gx_test_dim(gx_ctx *ctx, gx_table *customer, int32_t op,
@@ -9586,14 +9597,13 @@ extern "C" gx_status gx_test_dim(gx_ctx *ctx, gx_table *customer, int32_t op,
                                  int32_t *out_set_width)
 {
     if (!ctx || !out_bloom || !bwords) return GX_ERR_INVALID;
-    test_dimset ds;
-    gx_status st = test_build_dim(ctx, customer, op, literal, bwords, ds);
+    q3_dimset ds;
+    gx_status st = test_build_dim(ctx, customer, op, literal, bwords, ds, out_nsel);
     if (st != GX_OK) return st;
     HIP_CHK(ctx, hipMemcpyAsync(out_bloom, ds.bloom.p, bwords * 8,
                                 hipMemcpyDeviceToHost, ctx->stream));
     HIP_CHK(ctx, hipStreamSynchronize(ctx->stream));
     HIP_CHK(ctx, hipGetLastError());
-    if (out_nsel) *out_nsel = ds.nsel;
     if (out_set_width) *out_set_width = ds.width;
     return GX_OK;
 }
@@ -9611,7 +9621,7 @@ static gx_status test_m2_impl(gx_ctx *ctx, gx_table *customer, int32_t op,
         (n > 0 && !host_rows) || (cap > 0 && !out_rows))
         return GX_ERR_INVALID;
     hipStream_t s = ctx->stream;
-    test_dimset ds;
+    q3_dimset ds;
     gx_status st = test_build_dim(ctx, customer, op, literal, bwords, ds);
     if (st != GX_OK) return st;
     devbuf rows_b, hist_b, cur_b, send_b;
@@ -9622,9 +9632,8 @@ static gx_status test_m2_impl(gx_ctx *ctx, gx_table *customer, int32_t op,
     HIP_CHK(ctx, hist_b.alloc(nsegs * 8));
     HIP_CHK(ctx, cur_b.alloc(nsegs * 8));
     HIP_CHK(ctx, hipMemsetAsync(hist_b.p, 0, nsegs * 8, s));
-    m2_launch_hist(s, rows_b.as<gx_ord_row>(), n, ds.set.p, ds.width, ds.cmask,
-                   ds.bloom.as<unsigned long long>(), ds.bwmask, dim_join,
-                   nsegs, hist_b.as<unsigned long long>());
+    m2_launch_hist(s, rows_b.as<gx_ord_row>(), n, ds, dim_join, nsegs,
+                   hist_b.as<unsigned long long>());
     std::vector<unsigned long long> h(nsegs);
     HIP_CHK(ctx, hipMemcpyAsync(h.data(), hist_b.p, nsegs * 8, hipMemcpyDeviceToHost, s));
     HIP_CHK(ctx, hipStreamSynchronize(s));
@@ -9638,10 +9647,8 @@ static gx_status test_m2_impl(gx_ctx *ctx, gx_table *customer, int32_t op,
     }
     HIP_CHK(ctx, send_b.alloc(std::max<int64_t>(total, 1) * sizeof(gx_qual_row)));
     HIP_CHK(ctx, hipMemcpyAsync(cur_b.p, off.data(), nsegs * 8, hipMemcpyHostToDevice, s));
-    m2_launch_emit(s, rows_b.as<gx_ord_row>(), n, ds.set.p, ds.width, ds.cmask,
-                   ds.bloom.as<unsigned long long>(), ds.bwmask, dim_join,
-                   nsegs, cur_b.as<unsigned long long>(),
-                   send_b.as<gx_qual_row>());
+    m2_launch_emit(s, rows_b.as<gx_ord_row>(), n, ds, dim_join, nsegs,
+                   cur_b.as<unsigned long long>(), send_b.as<gx_qual_row>());
     if (total)
         HIP_CHK(ctx, hipMemcpyAsync(out_rows, send_b.p, total * sizeof(gx_qual_row),
                                     hipMemcpyDeviceToHost, s));
@@ -9683,66 +9690,48 @@ static gx_status test_m3_impl(gx_ctx *ctx, const gx_qual_row_abi *host_rows,
         return GX_ERR_INVALID;
     }
     hipStream_t s = ctx->stream;
-    devbuf rows_b, stat_b, key_b, attr_b, agg_b, cur_b, hit_b;
-    HIP_CHK(ctx, rows_b.alloc(std::max<int64_t>(n, 1) * sizeof(gx_qual_row)));
+    devbuf rows_b;
+    q3_scratch sc;
+    q3_hashtbl t;
+    q3_results r;
+    HIP_CHK(ctx, sc.ensure());
+    HIP_CHK(ctx, rows_b.alloc(n * sizeof(gx_qual_row)));
     if (n)
         HIP_CHK(ctx, hipMemcpyAsync(rows_b.p, host_rows, n * sizeof(gx_qual_row),
                                     hipMemcpyHostToDevice, s));
-    HIP_CHK(ctx, stat_b.alloc(16));
-    HIP_CHK(ctx, hipMemsetAsync(stat_b.p, 0, 8, s));
-    HIP_CHK(ctx, hipMemsetAsync((uint8_t *) stat_b.p + 8, 0xFF, 8, s));
-    hipLaunchKernelGGL(k_rows_minmax, dim3(GRID), dim3(TPB), 0, s,
-                       rows_b.as<gx_qual_row>(), n,
-                       stat_b.as<unsigned long long>(),
-                       stat_b.as<unsigned long long>() + 1);
-    unsigned long long st2[2];
-    HIP_CHK(ctx, hipMemcpyAsync(st2, stat_b.p, 16, hipMemcpyDeviceToHost, s));
-    HIP_CHK(ctx, hipStreamSynchronize(s));
-    unsigned long long kmax = st2[0], kmin = st2[1];
-    if (n > 0 && kmin == 0)
+    q3_keystats ks;
+    gx_tbl_layout TL;
     {
-        set_err(ctx, "mid join key 0 received: 0 is the empty-slot "
-                     "sentinel (gpuexec.h gx_q3_prepare_desc)%s", "");
-        return GX_ERR_INVALID;
+        gx_status lst = m3_recv_layout(ctx, s, sc, rows_b.as<gx_qual_row>(), n,
+                                       ks, TL);
+        if (lst != GX_OK) return lst;
     }
-    const gx_tbl_layout TL = m3_table_layout(
-        n, kmin, kmax, ctx->nsegs, env_int("GX_TABLE_FACTOR_PCT", 300));
-    if (lay) test_fill_layout(lay, TL, kmin, kmax);
-    uint64_t tslots = TL.slots;
-    HIP_CHK(ctx, key_b.alloc(tslots * TL.key_width));
-    HIP_CHK(ctx, attr_b.alloc(tslots * sizeof(gx_attrpair)));
-    HIP_CHK(ctx, agg_b.alloc(tslots * sizeof(gx_aggslot)));
-    HIP_CHK(ctx, hipMemsetAsync(key_b.p, 0, tslots * TL.key_width, s));
-    m3_launch_build(s, rows_b.as<gx_qual_row>(), n, TL.key_width,
-                    key_b.p, attr_b.as<gx_attrpair>(), agg_b.as<gx_aggslot>(),
-                    TL.smap);
+    if (lay) test_fill_layout(lay, TL, ks.kmin, ks.kmax);
+    t.width = TL.key_width;
+    t.smap = TL.smap;
+    {
+        gx_status ast = q3_alloc_hash(ctx, t, TL.slots);
+        if (ast != GX_OK) return ast;
+    }
+    HIP_CHK(ctx, hipMemsetAsync(t.keys.p, 0, t.slots() * t.width, s));
+    m3_launch_build(s, rows_b.as<gx_qual_row>(), n, t);
     const gx_col &lk = lineitem->cols[0], &lp = lineitem->cols[1],
                  &ld = lineitem->cols[2], &ls = lineitem->cols[3];
-    HIP_CHK(ctx, hit_b.alloc(8));
-    HIP_CHK(ctx, hipMemsetAsync(hit_b.p, 0, 8, s));
-    q3_launch_probe(
-        s, lk, lp, ld, ls, lineitem->dvmap, fop, (int32_t) flit,
-        TL.key_width, key_b.p, agg_b.as<gx_aggslot>(), TL.smap,
-        hit_b.as<unsigned long long>(), false, nullptr, nullptr, nullptr, 0);
-    devbuf r_okey, r_odate, r_oprio, r_rev, r_cnt;
-    int64_t cap = std::max<int64_t>(n, 1);
-    HIP_CHK(ctx, r_okey.alloc(cap * 8));
-    HIP_CHK(ctx, r_odate.alloc(cap * 4));
-    HIP_CHK(ctx, r_oprio.alloc(cap * 4));
-    HIP_CHK(ctx, r_rev.alloc(cap * 8));
-    HIP_CHK(ctx, r_cnt.alloc(cap * 8));
-    HIP_CHK(ctx, cur_b.alloc(8));
-    HIP_CHK(ctx, hipMemsetAsync(cur_b.p, 0, 8, s));
+    unsigned long long *dhits = sc.word(q3_scratch::HITS),
+                       *dcount = sc.word(q3_scratch::GROUPS);
+    HIP_CHK(ctx, hipMemsetAsync(dhits, 0, 8, s));
+    q3_launch_probe(s, lk, lp, ld, ls, lineitem->dvmap, fop, (int32_t) flit,
+                    t, dhits, false, q3_unmatched{});
+    HIP_CHK(ctx, r.alloc(std::max<int64_t>(n, 1)));
+    HIP_CHK(ctx, hipMemsetAsync(dcount, 0, 8, s));
     {
         gx_status est = q3_launch_extract(
-            ctx, s, TL.key_width, key_b.p, attr_b.as<gx_attrpair>(),
-            agg_b.as<gx_aggslot>(), tslots, 0, r_okey.as<int64_t>(),
-            r_odate.as<int32_t>(), r_oprio.as<int32_t>(), r_rev.as<double>(),
-            r_cnt.as<int64_t>(), cur_b.as<unsigned long long>());
+            ctx, s, t.width, t.keys.p, t.attrs.as<gx_attrpair>(),
+            t.aggs.as<gx_aggslot>(), t.slots(), 0, r, dcount);
         if (est != GX_OK) return est;
     }
     unsigned long long ng = 0;
-    HIP_CHK(ctx, hipMemcpyAsync(&ng, cur_b.p, 8, hipMemcpyDeviceToHost, s));
+    HIP_CHK(ctx, hipMemcpyAsync(&ng, dcount, 8, hipMemcpyDeviceToHost, s));
     HIP_CHK(ctx, hipStreamSynchronize(s));
     HIP_CHK(ctx, hipGetLastError());
     int64_t m = (int64_t) ng;
@@ -9751,11 +9740,11 @@ static gx_status test_m3_impl(gx_ctx *ctx, const gx_qual_row_abi *host_rows,
     std::vector<double> rev(m);
     if (m)
     {
-        HIP_CHK(ctx, hipMemcpy(okey.data(), r_okey.p, m * 8, hipMemcpyDeviceToHost));
-        HIP_CHK(ctx, hipMemcpy(odate.data(), r_odate.p, m * 4, hipMemcpyDeviceToHost));
-        HIP_CHK(ctx, hipMemcpy(oprio.data(), r_oprio.p, m * 4, hipMemcpyDeviceToHost));
-        HIP_CHK(ctx, hipMemcpy(rev.data(), r_rev.p, m * 8, hipMemcpyDeviceToHost));
-        HIP_CHK(ctx, hipMemcpy(cnt.data(), r_cnt.p, m * 8, hipMemcpyDeviceToHost));
+        HIP_CHK(ctx, hipMemcpy(okey.data(), r.okey.p, m * 8, hipMemcpyDeviceToHost));
+        HIP_CHK(ctx, hipMemcpy(odate.data(), r.odate.p, m * 4, hipMemcpyDeviceToHost));
+        HIP_CHK(ctx, hipMemcpy(oprio.data(), r.oprio.p, m * 4, hipMemcpyDeviceToHost));
+        HIP_CHK(ctx, hipMemcpy(rev.data(), r.rev.p, m * 8, hipMemcpyDeviceToHost));
+        HIP_CHK(ctx, hipMemcpy(cnt.data(), r.cnt.p, m * 8, hipMemcpyDeviceToHost));
     }
     std::vector<int64_t> idx(m);
     for (int64_t i = 0; i < m; i++) idx[i] = i;
@@ -9870,7 +9859,7 @@ extern "C" int gx_selftest_motion_layout(const uint64_t *cnts_all, int n, int se
     {
         if (qual < 0 || nsegs < 1 || tf_pct < 0) return 1;
         test_fill_layout(layout,
-                         m3_table_layout(qual, kmin, kmax, nsegs, tf_pct),
+                         q3_table_layout(qual, kmin, kmax, nsegs, tf_pct),
                          kmin, kmax);
     }
     return 0;

@@ -1058,15 +1058,23 @@ def test_hbm_budget_guard(ctx, orc, monkeypatch):
     cust = ctx.tpch_gen(gx.TPCH_CUSTOMER, 0.1)
     ordr = ctx.tpch_gen(gx.TPCH_ORDERS, 0.1)
     li = ctx.tpch_gen(gx.TPCH_LINEITEM, 0.1)
+    refused = ctx.q3(cust, ordr, li)
     with pytest.raises(gx.GxError) as ei:
-        ctx.q3(cust, ordr, li).run()
+        refused.run()
     assert ei.value.status == 5            # GX_ERR_OOM
     msg = str(ei.value)
     assert "HBM budget" in msg and "GB" in msg
     monkeypatch.delenv("GX_HBM_BUDGET_MB")
     # same tables run fine without the cap
-    r = ctx.q3(cust, ordr, li).run().result()
+    fresh = ctx.q3(cust, ordr, li)
+    r = fresh.run().result()
     assert len(r["l_orderkey"]) > 0
+    # and so does the refused q itself: sizing starts over on the retry
+    rr = refused.run().result()
+    np.testing.assert_array_equal(rr["l_orderkey"], r["l_orderkey"])
+    np.testing.assert_array_equal(rr["nitems"], r["nitems"])
+    np.testing.assert_allclose(rr["revenue"], r["revenue"], rtol=1e-9)
+    refused.free(); fresh.free()
     li.free(); ordr.free(); cust.free()
 
 
